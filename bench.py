@@ -2,7 +2,7 @@
 """bench.py -- PDA BPR-MF hot path on MI355X: full-catalogue score + mask + top-K@50 users/s (headline `value`)
 and BPR triplets/s (reported beside it), on synthetic Douban-shaped data (pda_amd/synthetic.py).
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is one pass of the evaluation hot path over one block of `--eval-block` users against the WHOLE item
 catalogue: score + history mask + top-K on every rank's item shard (bf16 MFMA pre-filter, exact fp32 rescoring of the
@@ -11,13 +11,16 @@ receives every shard's list for ITS slice of the users) and the merge.  Inputs a
 region.  Scaling is STRONG: the catalogue and the users per step are fixed while N grows (item-parallel sharding of
 BASELINE config 3 -> 4).
 
-The headline is a DENSE sweep: every user x item pair is scored, the catalogue being visited most popular first.  Beside
-it: `dense_natural_order` (the same in item-id order), `ordered_sweep` (the product default for the PDA head: the same
-visiting order with exact early termination on a popularity bound -- same results, most of the catalogue never scored),
-`roofline` (dominant kernel = the score kernel, bound = bf16 MFMA; achieved from the algorithmic flops 2*Bu*I_local*d per
-launch and the kernel's HIP-event duration), `cpu_baseline` (torch-CPU restatement of the reference op sequence,
-oracle/cpu_baseline.py, bounded sample, rank 0, N=1 only) and `train` (fused BPR step throughput on BASELINE config 2,
-N=1 only).
+The headline is a DENSE sweep: every user x item pair is scored, the catalogue being visited most popular first.  A plain
+run measures only that: set-up, W warm-up steps, K timed steps, the result line with `roofline` (dominant kernel = the score
+kernel, bound = bf16 MFMA; achieved from the algorithmic flops 2*Bu*I_local*d per launch and the kernel's HIP-event
+duration in the timed steps).  --full adds everything beside it: `dense_natural_order` (the same in item-id order),
+`ordered_sweep` (the product default for the PDA head: the same visiting order with exact early termination on a
+popularity bound -- same results, most of the catalogue never scored), `raw_head`, `prep`, the measured peaks and the
+box's clocks in `roofline`, `cpu_baseline` (torch-CPU restatement of the reference op sequence, oracle/cpu_baseline.py,
+bounded sample, rank 0, N=1 only), `train` (fused BPR step throughput on BASELINE config 2, N=1 only), `per_config`,
+`eval_block_2048` and, from four ranks on, `user_groups_grid`.
+--dump-outputs DIR writes what the headline path returned in its last timed step as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -59,6 +62,11 @@ def parse():
     p.add_argument("--extras-path", default=None, help="where the full record goes (default: bench_extras.json in the cwd)")
     p.add_argument("--headline-only", action="store_true",
                    help="time only the headline sweep (PMC passes: the other sweep modes launch the same kernel template)")
+    p.add_argument("--full", action="store_true",
+                   help="measure everything beside the headline too (the other sweeps, training, CPU baseline, per_config, ...); "
+                        "a plain run sets up, warms up, times the headline steps and prints the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the top-K lists of the last timed step to DIR/*.npy (rank 0)")
     p.add_argument("--train-sharded", action="store_true",
                    help="N>1 only: also time the item-parallel SGD step (pda_amd.dist.ItemShardedBPR); off by default -- "
                         "it is latency-bound by its per-step all-gather and buys capacity, not speed")
@@ -289,14 +297,14 @@ def bench_eval(args, rank, world, dev, workload=None, light=False, user_groups=N
         del W.I                                           # every rank keeps only its shard of the item table
     sink = []
 
-    last = [None]
+    last = [None, None]
     last_spread = [None]
 
     def run(bl, hd):
         # N > 1: the all-to-all exchange -- every rank merges and keeps the lists of its slice of the users
         for idx, val in ev.topk_blocks(bl, args.K, hd, hist, sharded=world > 1):
             sink.append(idx[0, 0])                        # keep the result alive without a sync
-            last[0] = idx
+            last[0], last[1] = idx, val
 
     def timed_pass(prune, hd=None):
         """W untimed + K timed steps, barrier + synchronize on both sides, MAX over ranks."""
@@ -329,13 +337,14 @@ def bench_eval(args, rank, world, dev, workload=None, light=False, user_groups=N
     v2 = ops.score_impl(W.d, args.K, W.n_items) == "v2"
     use_order = head == ops.HEAD_POP and v2
     natural = None
-    if use_order and not args.headline_only and not light:
+    if args.full and use_order and not args.headline_only and not light:
         dt_n, k_ms_n, _ = timed_pass(False)
         natural = {"value": Bu * steps / dt_n, "unit": "users/s", "ms_per_step": dt_n / steps * 1e3, "kernel_ms": k_ms_n}
-    clocks_before = gpu_clocks() if (world_all == 1 and not light) else None
+    clocks_before = gpu_clocks() if (args.full and world_all == 1 and not light) else None
     dt, k_ms, st_d = timed_pass("order" if use_order else False)
     headline_spread = last_spread[0]
-    clocks_after = gpu_clocks() if (world_all == 1 and not light) else None
+    outputs = {"idx": last[0], "val": last[1], "users": blocks[-1] if world_all == 1 else None}
+    clocks_after = gpu_clocks() if (args.full and world_all == 1 and not light) else None
     if os.environ.get("PDA_BENCH_DUMP") and user_groups is None:      # (N > 1: the replicated-hot-items path of pda_amd.dist)
         torch.save(last[0].cpu(), os.path.join(os.environ["PDA_BENCH_DUMP"], "topk_dense_w%d_r%d.pt" % (world_all, rank)))
     if use_order and "tiles_scored" in st_d:
@@ -343,7 +352,7 @@ def bench_eval(args, rank, world, dev, workload=None, light=False, user_groups=N
         assert int(st_d["tiles_scored"][0]) >= st_d["tiles_dense"], "the dense sweep must score every tile"
     # beside it: the product default for the PDA head -- ordered sweep WITH exact early termination (same keys).
     ordered = None
-    if use_order and not args.headline_only:
+    if args.full and use_order and not args.headline_only:
         dt_o, k_ms_o, st = timed_pass(True)
         frac = float(st["tiles_scored"][0]) / st["tiles_dense"] if "tiles_scored" in st else None
         ordered = {"value": Bu * steps / dt_o, "unit": "users/s", "ms_per_step": dt_o / steps * 1e3,
@@ -356,7 +365,7 @@ def bench_eval(args, rank, world, dev, workload=None, light=False, user_groups=N
     # the raw head ('main_branch'): the reference evaluates it in EVERY evaluation epoch before the two PDA passes
     # (MF/train_new_api.py:1139-1141, head at :597-598) and it is the only head of --train normal.  Product-default sweep mode.
     raw = None
-    if head == ops.HEAD_POP and v2 and not args.headline_only and world_all == 1:
+    if args.full and head == ops.HEAD_POP and v2 and not args.headline_only and world_all == 1:
         rp = ops.prune_default(ops.HEAD_RAW, W.d)
         dt_r, k_ms_r, st_r = timed_pass(rp, ops.HEAD_RAW)
         fl_r = 2.0 * blocks[0].numel() * ev.I_shard.shape[0] * W.d
@@ -438,7 +447,7 @@ def bench_eval(args, rank, world, dev, workload=None, light=False, user_groups=N
     # visiting order + test pieces + bounds; the visiting order and the reordered history depend on pop only and survive)
     # plus ceil(U / Bu) steps.
     prep = None
-    if impl == "v2" and world_all == 1:
+    if args.full and impl == "v2" and world_all == 1:
         pop_h = ev.pop_shard if head == ops.HEAD_POP else None
         order = ops.visiting_order(ev.I_shard, pop_h) if use_order else None
         def do_prep():
@@ -464,7 +473,7 @@ def bench_eval(args, rank, world, dev, workload=None, light=False, user_groups=N
                 "note": "one pass over all %d users after a weight update = item prep + %d steps of the headline sweep" % (W.n_users, n_steps_all)}
     res = {"users_per_s": Bu * steps / dt, "ms_per_step": dt / steps * 1e3, "Bu": Bu, "W": W, "steps": steps, "table_dtype": td_name,
            "layout": {"user_groups": ugroups, "item_shards": gsize, "users_per_rank_and_step": Bu_rank, "items_per_rank": n_local},
-           "roofline": roof, "hist": hist, "ordered": ordered, "natural": natural, "prep": prep, "raw_head": raw}
+           "roofline": roof, "hist": hist, "ordered": ordered, "natural": natural, "prep": prep, "raw_head": raw, "outputs": outputs}
     return res
 
 
@@ -1000,6 +1009,26 @@ def cpu_baseline(args, ev_res, train_pack, budget=None, full=True):
     return out
 
 
+DUMP_BYTES = 48 << 20              # a dump stays below 64 MB: item ids as float64, scores as float32, user ids as float64
+
+
+def dump_outputs(path, out):
+    """What the headline path returned for the last timed step, as its caller receives it: the top-K item ids (float64, exact
+    for any int32 id) and their fp32 scores, row r belonging to user users[r].  A block larger than DUMP_BYTES allows is
+    sampled: a fixed set of rows (seed 0), the same in every run with the same arguments."""
+    import numpy as np
+    idx, val, users = out["idx"], out["val"], out["users"]
+    n, K = idx.shape
+    cap = DUMP_BYTES // (K * 12 + 8)
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    sel = torch.as_tensor(rows, device=idx.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "topk_items.npy"), idx.index_select(0, sel).double().cpu().numpy())
+    np.save(os.path.join(path, "topk_scores.npy"), val.index_select(0, sel).float().cpu().numpy())
+    if users is not None:
+        np.save(os.path.join(path, "users.npy"), users.index_select(0, sel).double().cpu().numpy())
+
+
 def main():
     args = parse()
     if os.environ.get("PDA_BENCH_WATCHDOG"):           # debugging aid: every thread's stack to stderr after N seconds, then exit
@@ -1024,11 +1053,13 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)  # backend "nccl" IS RCCL on ROCm
     ev = bench_eval(args, rank, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ev["outputs"])
     # `value` is BASELINE config 4's layout: the catalogue item-sharded over ALL ranks, one list exchange among them.  Beside it, from four
     # ranks on: the two-dimensional layout of rounds 2 - 4 (user groups x item shards of 2)
     ev_grid = None
     from pda_amd.dist import grid_user_groups
-    if world >= 4 and ev["layout"]["user_groups"] == 1 and grid_user_groups(world) != 1 and not args.headline_only:
+    if args.full and world >= 4 and ev["layout"]["user_groups"] == 1 and grid_user_groups(world) != 1 and not args.headline_only:
         e2 = bench_eval(args, rank, world, dev, light=True, user_groups=grid_user_groups(world))
         ev_grid = {"value": e2["users_per_s"], "unit": "users/s", "ms_per_step": e2["ms_per_step"], "layout": e2["layout"],
                    "early_terminating_sweep": e2["ordered"],
@@ -1037,9 +1068,9 @@ def main():
                            % grid_user_groups(world)}
         del e2
         torch.cuda.empty_cache()
-    sharded_train = bench_train_sharded(args, rank, world, dev) if (world > 1 and args.train_sharded) else None
+    sharded_train = bench_train_sharded(args, rank, world, dev) if (args.full and world > 1 and args.train_sharded) else None
     train_pack = None
-    if world == 1 and not args.no_train:
+    if args.full and world == 1 and not args.no_train:
         train_pack = bench_train(args, dev)
         if not args.headline_only and args.workload in ("c3", "tiny"):
             train_pack[0]["adam_on_headline_tables"] = bench_adam_big_tables(args, dev, args.workload)
@@ -1051,15 +1082,15 @@ def main():
             train_pack[0][key] = sgd_rates_on_tables(args, dev, _syn.make_workload(args.workload, dev, table_dtype=td))
             torch.cuda.empty_cache()
     block2048 = None
-    if world == 1 and not args.headline_only and args.workload in ("c3", "c2", "c1", "tiny") and args.head == "condition":
+    if args.full and world == 1 and not args.headline_only and args.workload in ("c3", "c2", "c1", "tiny") and args.head == "condition":
         block2048 = bench_reference_block_protocol(args, dev, args.workload)
         torch.cuda.empty_cache()
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, ev, train_pack)
     # roofs measured on this box, beside the datasheet's (north_star: "measured roofline")
     from pda_amd import ops as _ops
-    peaks = _ops.measured_peaks(dev) if rank == 0 else None
+    peaks = _ops.measured_peaks(dev) if (args.full and rank == 0) else None
     if peaks:
         r = ev["roofline"]
         r["peak_measured"] = peaks["bf16_mfma_TFLOPs"] if r["peak"] == PEAK_BF16_MFMA_TFLOPS else None
@@ -1069,7 +1100,7 @@ def main():
         r["peaks_measured"] = peaks
     # the smaller BASELINE configs beside the headline: evaluation (headline sweep + early-terminating sweep) and training
     per_config = None
-    if world == 1 and rank == 0 and not args.no_per_config and not args.headline_only and args.workload == "c3":
+    if args.full and world == 1 and rank == 0 and not args.no_per_config and not args.headline_only and args.workload == "c3":
         per_config = {}
         for wl in ("c1", "c2"):
             e = bench_eval(args, rank, world, dev, workload=wl, light=True)

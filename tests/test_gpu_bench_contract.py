@@ -26,7 +26,7 @@ def contract_line(stdout):
 
 def run_bench(tmp_path, *flags):
     extras = os.path.join(str(tmp_path), "extras.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--extras-path", extras] + list(flags),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--extras-path", extras] + list(flags),
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = contract_line(out.stdout)
@@ -105,3 +105,39 @@ def test_bench_bf16_train_keys(dev, tmp_path):
     assert sb["bytes_per_triplet"] == 6 * 64 * 2 + 20
     for B in ("B2048",):
         assert sb[B]["exact_planned"]["triplets_per_s"] > 0 and sb[B]["fused_hogwild"]["triplets_per_s"] > 0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_lists(dev, tmp_path):
+    """A plain run (no --full): the headline steps and the result line, nothing measured beside them.  --dump-outputs writes the lists
+    of the last timed step -- the same in two runs with the same arguments, and the oracle's lists for those users."""
+    import numpy as np
+    from oracle import c_oracle
+    from pda_amd import synthetic
+    dumps = []
+    for i in range(2):
+        extras, dump = os.path.join(str(tmp_path), "extras%d.json" % i), os.path.join(str(tmp_path), "out%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                              "--eval-block", "1024", "--extras-path", extras, "--dump-outputs", dump],
+                             capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line, full = contract_line(out.stdout), json.load(open(extras))
+        assert line["steps"] == 3 and line["roofline"]["kernel_ms_spread"]["calls"] == 3       # one score call per timed step
+        assert line["unit"] == "users/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 1024) < 1e-6 * 1024
+        for k in ("cpu_baseline", "train", "per_config", "eval_block_2048", "raw_head", "ordered_sweep", "dense_natural_order", "prep"):
+            assert full[k] is None, k
+        assert "peaks_measured" not in full["roofline"] and full["roofline"]["box"] == {"before": None, "after": None}
+        dumps.append([np.load(os.path.join(dump, n + ".npy")) for n in ("topk_items", "topk_scores", "users")])
+    items, scores, users = dumps[0]
+    assert items.shape == scores.shape == (1024, 50) and users.shape == (1024,)
+    assert items.dtype == users.dtype == np.float64 and scores.dtype == np.float32
+    for a, b in zip(dumps[0], dumps[1]):
+        np.testing.assert_array_equal(a, b)
+    W = synthetic.make_workload("tiny", dev)
+    ip, ix, u = W.hist_indptr.cpu().numpy(), W.hist_indices.cpu().numpy(), users.astype(np.int64)
+    bptr = np.concatenate([[0], np.cumsum(ip[u + 1] - ip[u])])                 # the oracle's history rows are the block's rows
+    bind = np.concatenate([ix[ip[x]:ip[x + 1]] for x in u])
+    ridx, rval = c_oracle.score_topk(W.U.cpu().numpy(), W.I.cpu().numpy(), u.astype(np.int32), 50, 1, W.pop_last.cpu().numpy(),
+                                     bptr, bind, order=1)
+    np.testing.assert_allclose(scores, rval, rtol=2e-6, atol=1e-6)
+    assert (items == ridx).mean() > 0.99          # (two items of a last-ulp near-tie may swap places, as smoke() allows)

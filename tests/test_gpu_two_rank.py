@@ -20,7 +20,7 @@ def _run(cmd, env):
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         extras = os.path.join(td, "extras.json")
-        p = subprocess.run(cmd + ["--extras-path", extras], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+        p = subprocess.run(cmd + ["--full", "--extras-path", extras], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
         assert len([ln for ln in lines if ln.startswith("{")]) == 1, p.stdout[-2000:]

@@ -5,8 +5,8 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 shift; X="$*"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py $X > $O/bench_under_rocprof.log 2>&1
-python $R/bench.py $X --extras-path $O/bench_extras.json > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --full $X > $O/bench_under_rocprof.log 2>&1
+python $R/bench.py --full $X --extras-path $O/bench_extras.json > $O/bench.json 2> $O/bench.err
 python $R/tools/check_contract_line.py $O/bench.json | tee $O/contract_line_check.txt
 # the early-terminating sweep launches the SAME kernel template as the headline sweep: a second summary with the headline alone
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -o bench -- python $R/bench.py $X --headline-only --no-train --no-cpu-baseline --extras-path /dev/null > $O/bench_headline_under_rocprof.log 2>&1

@@ -1,4 +1,4 @@
-"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h).
+"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h and pda_hip_temp_pop.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -129,6 +129,16 @@ SIGNATURES = {
     "pda_sample_triplets": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_temp_pop.h (BPRMF(t)-pop, `--train temp_pop`)
+HEAD_BIAS = 2
+TEMP_POP_SIGNATURES = {
+    "pda_temp_pop_step_f32": (_i, [_vp] * 8 + [_i, _i, _i, _f, _f] + [_vp] * 6 + [_i, _vp, _vp]),
+    "pda_temp_pop_sweep_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 8 + [_i, _i, _i, _f, _f, _f, _f, _vp]),
+    "pda_temp_pop_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 12 + [_i, _i, _i, _f, _f, _i, _f, _f, _f, _f, _vp, _vp]),
+    "pda_temp_pop_score_workspace_bytes": (_sz, [_i]),
+    "pda_temp_pop_score_topk_f32": (_i, [_vp] * 6 + [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -146,7 +156,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

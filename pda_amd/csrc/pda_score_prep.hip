@@ -296,6 +296,26 @@ int run_score_prepped(const void* U, const void* I_shard, bool bf16, const void*
 }
 }  // namespace
 
+int pda_topk::run_score_bias_prefiltered(const float* U, const float* I_shard, const void* prep, const float* alpha, const float* beta,
+                                         const int32_t* users, int n_users_blk, int item_offset, int n_items_local, int d,
+                                         const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int K, int n_splits,
+                                         uint64_t* out_keys, void* workspace, hipStream_t s) {
+    if (K > PDA_TOPK_CAP - 4) return PDA_ERR_UNSUPPORTED;
+    const bool v3_fits = (uint64_t)item_offset + (uint64_t)n_items_local <= (1ull << 27) && (uint64_t)n_items_local * (uint64_t)d < (1ull << 32);
+    if (!v3_fits) return PDA_ERR_UNSUPPORTED;
+    const PrepLayout L = prep_layout(n_items_local, d, false, planes_of(false, false));
+    const char* pb = reinterpret_cast<const char*>(prep);
+    int* ws = reinterpret_cast<int*>(workspace);
+    if (hipMemsetAsync(workspace, 0, pda_score_topk_workspace_bytes(n_users_blk), s) != hipSuccess) return PDA_ERR_LAUNCH;
+    ScoreArgs2 aa{{U, I_shard, beta, users, hist_indptr, hist_indices, out_keys, n_users_blk, item_offset, n_items_local, hist_row_mode, K,
+                   n_splits, nullptr},
+                  reinterpret_cast<const uint16_t*>(pb + L.hi), reinterpret_cast<const uint16_t*>(pb + L.lo),
+                  reinterpret_cast<const float*>(pb + L.norm), reinterpret_cast<const float*>(pb + L.nmax),
+                  reinterpret_cast<const float*>(ws), ws + 4, nullptr, nullptr, nullptr, nullptr,
+                  reinterpret_cast<unsigned long long*>(ws + 2), reinterpret_cast<const uint16_t*>(pb + L.bex), hist_indices, alpha};
+    return pda_topk::launch_score_v3_bias(aa, d, s);
+}
+
 extern "C" size_t pda_item_prep_bytes(int n_items_local, int d) { return prep_layout(n_items_local, d, false, 2).total; }
 extern "C" size_t pda_item_prep_ordered_bytes(int n_items_local, int d) { return prep_layout(n_items_local, d, true, 2).total; }
 extern "C" size_t pda_item_prep_bf16_bytes(int n_items_local, int d) { return prep_layout(n_items_local, d, false, 0).total; }

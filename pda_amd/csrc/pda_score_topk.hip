@@ -27,6 +27,7 @@
 //   mask       = history CSR rows sorted by item id; each user row keeps a cursor, producing a
 //                32-bit mask per (user, tile) that is consulted only on the slow path.
 #include "pda_topk_common.h"
+#include "pda_hip_temp_pop.h"
 #include <cstdlib>
 
 namespace {
@@ -36,6 +37,8 @@ using namespace pda_topk;
 // ABL: profiling-only ablation bits (0 in the shipped instantiations): 1 skip slow path, 2 skip threshold test,
 // 4 skip history cursor, 8 skip item-tile global loads.  Enabled by building with -DPDA_ABLATION.
 // BF: the tables are bf16 (pda_score_topk_bf16's exact fallback); rows are widened to fp32 on load -- same arithmetic.
+// HEAD = PDA_HEAD_BIAS (temp_pop, include/pda_hip_temp_pop.h): h = fl(s + fl(alpha_u beta_i)), beta behind a.pop; this head has no fallback
+// mode, and a.tile_flags carries its workspace instead: the identity word is written at +16, alpha (per block row) is read from +64.
 template <int D, int HEAD, int ABL = 0, bool BF = false>
 __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kernel(ScoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -52,7 +55,8 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
     const int j = lane & 31, h = lane >> 5;
     const int split = blockIdx.x % a.n_splits, utile = blockIdx.x / a.n_splits;
     const int K = a.K;
-    if (a.tile_flags != nullptr && a.tile_flags[utile] == 0) return;   // v2 fallback mode: only flagged user tiles
+    if constexpr (HEAD != PDA_HEAD_BIAS)
+        if (a.tile_flags != nullptr && a.tile_flags[utile] == 0) return;   // v2 fallback mode: only flagged user tiles
 
     const int tiles_total = (a.n_items_local + 31) >> 5;
     const int tiles_per = (tiles_total + a.n_splits - 1) / a.n_splits;
@@ -111,6 +115,17 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
         for (int r = 0; r < 16; ++r) thr[r] = taul[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hv];
     };
     refresh_thr();
+    f32x16 alr;   // PDA_HEAD_BIAS: alpha of the row of accumulator register r (the layout of thr)
+    if constexpr (HEAD == PDA_HEAD_BIAS) {
+        unsigned char* ws = reinterpret_cast<unsigned char*>(const_cast<int*>(a.tile_flags));
+        const float* alpha = reinterpret_cast<const float*>(ws + 64);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rb = utile * kUserTile + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            alr[r] = alpha[min(rb, a.n_users_blk - 1)];
+        }
+        if (blockIdx.x == 0 && tid == 0) *reinterpret_cast<unsigned*>(ws + 16) = (1u << 28) | (1u << 15) | (unsigned)(D >> 6);
+    }
 
     // ---- item tile staging -------------------------------------------------------------------
     f32x4 pre[NLD];
@@ -135,7 +150,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
         }
     };
     auto pop_load = [&](int t) -> float {
-        if constexpr (HEAD == PDA_HEAD_POP) return a.pop[min(t * 32 + j, a.n_items_local - 1)];
+        if constexpr (HEAD == PDA_HEAD_POP || HEAD == PDA_HEAD_BIAS) return a.pop[min(t * 32 + j, a.n_items_local - 1)];
         return 1.0f;
     };
     // History bits of tile t for my row.  Branch-free for the common case (at most one train item of the row
@@ -196,6 +211,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
                 rm &= rm - 1u;
                 float tt = accv[r];   // exact head value (the fast test only saw an upper bound)
                 if constexpr (HEAD == PDA_HEAD_POP) tt = (tt > 0.0f ? tt + 1.0f : __expf(tt)) * popv;
+                if constexpr (HEAD == PDA_HEAD_BIAS) tt = tt + alr[r] * popv;
                 bool p = lane_ok && ((still >> r) & 1u) && (tt > thr[r]);
                 const int rowb = (r & 3) + 8 * (r >> 2);
                 if (any_hb) {   // train items never enter
@@ -230,15 +246,17 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
 
     // Threshold test on an UPPER BOUND of the head: ub = (max(s,0)+1)*pop equals the exact (elu(s)+1)*pop for
     // s > 0 (bitwise) and is >= it for s <= 0, so no candidate is missed and the exp is only paid on the slow path.
-    auto head_ub = [&](float sc, float popv) -> float {
+    // (PDA_HEAD_BIAS: the exact head itself, two VALU per score)
+    auto head_ub = [&](float sc, float popv, int r) -> float {
         if constexpr (HEAD == PDA_HEAD_POP) return (fmaxf(sc, 0.0f) + 1.0f) * popv;
+        if constexpr (HEAD == PDA_HEAD_BIAS) return sc + alr[r] * popv;
         return sc;
     };
     auto fast_test = [&](const f32x16& accv, float popv, uint64_t vmask) -> uint32_t {
         uint32_t regmask = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            regmask |= (__ballot(head_ub(accv[r], popv) > thr[r]) & vmask) ? (1u << r) : 0u;
+            regmask |= (__ballot(head_ub(accv[r], popv, r) > thr[r]) & vmask) ? (1u << r) : 0u;
         return regmask;
     };
 
@@ -288,7 +306,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
             if constexpr (!(ABL & 2)) {
 #pragma unroll
                 for (int r = (16 * c) / NC; r < (16 * (c + 2)) / NC; ++r)
-                    regmask |= (__ballot(head_ub(acc_prev[r], popj_prev) > thr[r]) & vmask_prev) ? (1u << r) : 0u;
+                    regmask |= (__ballot(head_ub(acc_prev[r], popj_prev, r) > thr[r]) & vmask_prev) ? (1u << r) : 0u;
             }
         }
         if constexpr (ABL & 2) asm volatile("" ::"v"(acc_prev[0]), "v"(acc_prev[7]), "v"(acc_prev[15]));
@@ -299,7 +317,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, (HEAD == PDA_HEAD_POP ? 64 : 16) / (4 * NC) + 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, (HEAD == PDA_HEAD_RAW ? 16 : 64) / (4 * NC) + 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x004, 1, 0);
             }
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -452,6 +470,15 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(MergeArgs a) {
 }
 
 }  // namespace
+
+int pda_topk::launch_score_bias(const ScoreArgs& a, int d, hipStream_t s) {
+    switch (d) {
+        case 64: return launch_score<64, PDA_HEAD_BIAS>(a, s);
+        case 128: return launch_score<128, PDA_HEAD_BIAS>(a, s);
+        case 256: return launch_score<256, PDA_HEAD_BIAS>(a, s);
+        default: return PDA_ERR_UNSUPPORTED;
+    }
+}
 
 int pda_topk::launch_score_v1(const ScoreArgs& a, int d, int head, hipStream_t s, bool bf16) {
     if (bf16) {

@@ -19,7 +19,18 @@
 //   u_k i_k - uh_k ih_k = du_k i_k + uh_k di_k,  |.| <= 2^-8 (2 + 2^-8) |u_k i_k|;  summed, Cauchy-Schwarz: 2^-7 (1 + 2^-9) ||u|| ||i||.
 //   bf16 products are exact in fp32; fp32 accumulation of d terms (any order) and the rounding of the exact chain add
 //   <= 2 d 2^-24 sum|u_k i_k| <= 2^-15 ||u|| ||i|| for d <= 256.  Norms are padded by (1+2^-10)(1+1e-4).  Used: 2^-7 * 1.01.
+//
+// Bias head (PDA_HEAD_BIAS, temp_pop; natural order, fp32 tables): h = fl(s + fl(a b)), a = alpha of the row, b = beta of the item.  The
+// filter value is  v = fma(a, b, s~ + m_i)  against the lowered threshold thr - 2^-20 |thr| - 1e-30, with per-item margin
+//   m_i = eps(u_max, i) + 2^-20 (1.01 ||u||_max ||i|| + |a|_max |b_i|)          (||.||: the padded norms above; maxima over the wave's rows)
+// Claim: h >= thr  =>  v > thr_lowered.  |s~ - s| <= eps (above).  |fl(a b) - a b| <= 2^-24 |a b|.  h = fl(s + fl(a b)) is within 2^-24 |h| of
+// s + fl(a b).  The two roundings inside v (s~ + m_i, then the fma) are each <= 2^-24 of |s~| + m_i + |a b| + |v|, with |s~| <= 1.01 ||u|| ||i||.
+// So v >= h - 2^-24 |h| - 2^-24 |v| - 3 2^-24 (1.01 ||u|| ||i|| + |a b|) + (m_i - eps) >= h - 2^-24 (|h| + |v|), and near the threshold
+// (h ~ thr, v ~ thr) the lowering 2^-20 |thr| covers the relative terms; 1e-30 covers underflow.  Candidates are then rescored by the exact
+// chain plus fl(a b) added once, the keys of generation 1's bias instance bit for bit.  The test costs 3 VALU per score (add, fma, compare)
+// instead of the folded k-step (the extra MFMA would need bf16 pieces of a and b).
 #include "pda_topk_common.h"
+#include "pda_hip_temp_pop.h"
 #include <cstdlib>
 #ifndef PDA_KWARM
 #define PDA_KWARM 4
@@ -183,7 +194,20 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
     float nu_max = nu_row;                     // ONE norm per wave (the largest): eps scale of the filter, and the
 #pragma unroll                                 // termination bound of the ordered sweep
     for (int o = 32; o > 0; o >>= 1) nu_max = fmaxf(nu_max, __shfl_xor(nu_max, o, 64));
+    const float nu_raw_max = nu_max * 1.01f;    // (PDA_HEAD_BIAS margin)
     nu_max *= kEps * 1.001f;
+    // PDA_HEAD_BIAS: alpha of the lane's own row, of the row of each accumulator register, and the largest |alpha| of the wave
+    [[maybe_unused]] float alpha_own = 0.f, alpha_max = 0.f;
+    [[maybe_unused]] f32x16 alr = zero16w(), thrb = zero16w();
+    if constexpr (HEAD == PDA_HEAD_BIAS) {
+        alpha_own = row_ok ? aa.alpha[row_blk] : 0.f;
+        float am = fabsf(alpha_own);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));
+        alpha_max = am;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) alr[r] = __shfl(alpha_own, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
+    }
     // lowered threshold of row (r in accumulator layout of lane half hv); strictly below tau (also for tau == 0): an item
     // that TIES the K-th value must get through -- in visiting order it may carry the lower id and win
     auto thr_of = [&](int r, int hv) __attribute__((always_inline)) -> float {
@@ -216,6 +240,10 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
             aex[1] = h ? nnu : (t2 | (t2 << 16));
             aex[2] = h ? 0u : (t1 | (t3 << 16));
             aex[3] = h ? 0u : (t2 | (t3 << 16));
+        }
+        if constexpr (HEAD == PDA_HEAD_BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) thrb[r] = thr_of(r, h);
         }
     };
     refresh_thr();
@@ -257,6 +285,7 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
             const int it = min(t * TW + 32 * cb + j, a.n_items_local - 1);
             popv[cb] = 1.0f;
             if constexpr (HEAD == PDA_HEAD_POP) popv[cb] = ORD ? aa.pop_p[it] : a.pop[it];
+            if constexpr (HEAD == PDA_HEAD_BIAS) popv[cb] = a.pop[it];
             if constexpr (ORD) idv[cb] = a.item_offset + aa.order[it];      // the ring keeps the item's real id
             else idv[cb] = a.item_offset + t * TW + 32 * cb + j;
         }
@@ -287,7 +316,8 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
                 ii[c] = pda_load4<BF>(a.I, ib + 4 * c);
             }
             float pv = 1.0f;
-            if constexpr (HEAD == PDA_HEAD_POP) pv = a.pop[item - a.item_offset];
+            if constexpr (HEAD == PDA_HEAD_POP || HEAD == PDA_HEAD_BIAS) pv = a.pop[item - a.item_offset];
+            [[maybe_unused]] const float al = __shfl(alpha_own, row, 64);
             float c0 = 0.f, c1 = 0.f, o0 = 0.f, o1 = 0.f;
 #pragma unroll
             for (int ph = 0; ph < LPC; ++ph) {
@@ -316,6 +346,7 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
             }
             float sc = o0 + o1;                               // meaningful on the candidate's last lane
             if constexpr (HEAD == PDA_HEAD_POP) sc = (sc > 0.0f ? sc + 1.0f : __expf(sc)) * pv;
+            if constexpr (HEAD == PDA_HEAD_BIAS) sc = sc + al * pv;
             const float tt = (valid && q == LPC - 1) ? sc : -INFINITY;
             const int lrow = wave * 32 + row;
             // ">=": equal scores are decided by the key (lower item id wins) at the next compaction, so ties must get in
@@ -467,6 +498,7 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
                     const int lrow = wave * 32 + row;
                     float sc = accx[r];
                     if constexpr (HEAD == PDA_HEAD_POP) sc = (sc > 0.0f ? sc + 1.0f : __expf(sc)) * popw[cb];
+                    if constexpr (HEAD == PDA_HEAD_BIAS) sc = sc + alr[r] * popw[cb];
                     bool p = okw && (sc >= taul[lrow]);
                     if (any_hb) {
                         const uint32_t hbr = (uint32_t)__shfl((int)hbits, row, 64);          // train items never enter
@@ -556,11 +588,25 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
         }
         uint64_t okm[NB], many = 0;
         bool clampy[NB];
+        [[maybe_unused]] uint32_t bmask[NB];
 #pragma unroll
         for (int cb = 0; cb < NB; ++cb) {
             uint64_t mc = 0;
             clampy[cb] = false;
-            {
+            if constexpr (HEAD == PDA_HEAD_BIAS) {
+                // the bias-head filter (header): v = fma(alpha, beta, s~ + m_i) > lowered threshold, register r at bit 15 - r
+                const int it = min(tile_of(k) * TW + 32 * cb + j, a.n_items_local - 1);
+                const float ni = aa.I_norm[it];
+                const float mg = nu_max * ni + 9.5367431640625e-7f * (nu_raw_max * ni + alpha_max * fabsf(pop_cur[cb])) + 1e-30f;
+                uint32_t bits = 0;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = __builtin_fmaf(alr[r], pop_cur[cb], sc[cb][r] + mg);
+                    bits |= (v > thrb[r]) ? (1u << (15 - r)) : 0u;
+                }
+                bmask[cb] = bits;
+                mc = __ballot(bits != 0u);
+            } else {
                 u32x4 bx = bex_cur[cb];
                 if constexpr (HEAD == PDA_HEAD_POP && !ORD) {
                     // natural order: the prep never saw the popularity (raw-type pieces) -- the 1/pop pieces and the constant
@@ -624,7 +670,9 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
 #pragma unroll
             for (int cb = NB - 1; cb >= 0; --cb) {
                 uint32_t mcb = 0;
-                {
+                if constexpr (HEAD == PDA_HEAD_BIAS) {
+                    mcb = bmask[cb];
+                } else {
                     // "register is a positive float" = sign bit of (0 - bits); one v_sub + one v_alignbit per register.
                     // (-0.0 counts as positive: a false candidate at worst)
 #pragma unroll
@@ -675,7 +723,9 @@ __global__ void __launch_bounds__(kThreads, 2) score_topk_v3_kernel(ScoreArgs2 a
     }
     if (tid == 0) atomicAdd(aa.visited, (unsigned long long)n32);
     // kernel identity (workspace + 16; tests read it back to prove WHICH kernel a call ran): generation 3 | ORD | HEAD | BF | d / 64
-    if (tid == 0 && blockIdx.x == 0)
+    if constexpr (HEAD == PDA_HEAD_BIAS) {
+        if (tid == 0 && blockIdx.x == 0) reinterpret_cast<unsigned*>(aa.visited)[2] = (3u << 28) | (1u << 15) | (unsigned)(D >> 6);
+    } else if (tid == 0 && blockIdx.x == 0)
         reinterpret_cast<unsigned*>(aa.visited)[2] = (3u << 28) | ((ORD ? 1u : 0u) << 12) | ((unsigned)HEAD << 13) | ((BF ? 1u : 0u) << 14) | (unsigned)(D >> 6);
     if (ring_cnt > 0) process_ring();
     if (lane == 0) atomicAdd(reinterpret_cast<unsigned*>(aa.visited) - 1, n_cand);   // workspace + 4: u32 "pairs rescored"
@@ -710,6 +760,17 @@ int launch_v3(const ScoreArgs2& aa, hipStream_t stream) {
 }
 
 }  // namespace
+
+int pda_topk::launch_score_v3_bias(const ScoreArgs2& aa, int d, hipStream_t s) {
+    if ((uint64_t)aa.a.item_offset + (uint64_t)aa.a.n_items_local > (1ull << 27)) return PDA_ERR_UNSUPPORTED;   // ring: 27-bit item ids
+    if ((uint64_t)aa.a.n_items_local * (uint64_t)d >= (1ull << 32)) return PDA_ERR_UNSUPPORTED;                  // 32-bit plane offsets
+    switch (d) {
+        case 64: return launch_v3<64, PDA_HEAD_BIAS, false, false>(aa, s);
+        case 128: return launch_v3<128, PDA_HEAD_BIAS, false, false>(aa, s);
+        case 256: return launch_v3<256, PDA_HEAD_BIAS, false, false>(aa, s);
+        default: return PDA_ERR_UNSUPPORTED;
+    }
+}
 
 int pda_topk::launch_score_v3(const ScoreArgs2& aa, int d, int head, bool ordered, bool bf16, hipStream_t s) {
     if ((uint64_t)aa.a.item_offset + (uint64_t)aa.a.n_items_local > (1ull << 27)) return PDA_ERR_UNSUPPORTED;   // ring: 27-bit item ids

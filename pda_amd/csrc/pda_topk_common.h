@@ -23,7 +23,8 @@ struct ScoreArgs {
     int hist_row_mode;
     int K;
     int n_splits;
-    const int* tile_flags;   // optional [n_user_tiles]: only flagged tiles are computed (v2's exact fallback)
+    const int* tile_flags;   // optional [n_user_tiles]: only flagged tiles are computed (v2's exact fallback).  Generation 1's bias head
+                             // (PDA_HEAD_BIAS) has no fallback mode and receives its workspace here instead (alpha at +64, identity at +16)
 };
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -47,6 +48,7 @@ struct ScoreArgs2 {
     // v3 "folded test": 16 bf16 per item (one extra MFMA k-step) that subtract threshold/pop + 1 + eps inside the matrix pipe
     const uint16_t* I_bex;  // [n_items_local][16]: k 0..7 pieces of 1/pop (1 for PDA_HEAD_RAW), k 8..10 constants and ||i||
     const int32_t* hist_nat;   // the caller's history (item ids ascending per row) also for ordered sweeps: v3 masks at the candidate stage
+    const float* alpha = nullptr;   // PDA_HEAD_BIAS (temp_pop, natural order only): alpha per block row; beta is behind a.pop
 };
 
 __device__ __forceinline__ uint32_t bf16_rne(float x) {
@@ -97,6 +99,15 @@ int launch_score_v3(const ScoreArgs2& aa, int d, int head, bool ordered, bool bf
 
 // defined in pda_score_topk.hip
 int launch_score_v1(const ScoreArgs& a, int d, int head, hipStream_t stream, bool bf16_tables = false);
+// generation 1 with the temp_pop bias head (PDA_HEAD_BIAS of include/pda_hip_temp_pop.h): beta behind a.pop, a.tile_flags = the workspace
+// (identity word at +16, alpha per block row from +64)
+int launch_score_bias(const ScoreArgs& a, int d, hipStream_t stream);
+// generation 3 with the bias head, natural order, fp32 tables (pda_score_topk_v3.hip)
+int launch_score_v3_bias(const ScoreArgs2& aa, int d, hipStream_t stream);
+// the bias head through generation 3 from a pda_item_prep_f32 prep (pda_score_prep.hip): PDA_ERR_UNSUPPORTED where generation 3 cannot run
+int run_score_bias_prefiltered(const float* U, const float* I_shard, const void* prep, const float* alpha, const float* beta, const int32_t* users,
+                               int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr, const int32_t* hist_indices,
+                               int hist_row_mode, int K, int n_splits, uint64_t* out_keys, void* workspace, hipStream_t s);
 
 template <int D>
 __device__ __forceinline__ int swz(int row) {

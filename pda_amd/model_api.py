@@ -1,6 +1,7 @@
 """Model objects with the reference's names and constructor arguments (MF/model_api.py), backed by HIP kernels.
 
     ConditionalBPRMF   PD / PDA            MF/model_api.py:14-185
+    BPRMFTempPop       BPRMF(t)-pop        MF/model_api.py:300-416   (temporal popularity bias; Adam sweep only)
     BPRMF              plain BPR-MF        MF/model_api.py:419-757   (only :419-471, :521-536, :695-706 are live)
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
@@ -296,6 +297,8 @@ class _MFBase:
         (best_ckpt.ckpt ...) but are torch pickles: a TF checkpoint of the reference cannot be read here, nor the reverse."""
         if not isinstance(sd, dict) or "user_embedding" not in sd:
             raise ValueError("not a pda_amd checkpoint (a tf.train.Saver checkpoint of the reference cannot be loaded)")
+        if sd.get("model", "mf") != "mf":
+            raise ValueError("checkpoint of a %s model cannot be loaded into %s" % (sd["model"], type(self).__name__))
         for key, mine in (("embed_size", self.emb_dim), ("n_users", self.n_users), ("n_items", self.n_items)):
             if key in sd and int(sd[key]) != int(mine):
                 raise ValueError("checkpoint %s = %s, model has %s" % (key, sd[key], mine))
@@ -345,3 +348,114 @@ class ConditionalBPRMF(_MFBase):
         self.mf_loss_pop_global, self.reg_loss_pop_global = Fetch(self, "mf_loss"), Fetch(self, "reg_loss")
         self.batch_ratings = Fetch(self, "batch_ratings")
         self.condition_ratings = Fetch(self, "condition_ratings")
+
+
+class BPRMFTempPop(_MFBase):
+    """BPRMF(t)-pop (MF/model_api.py:300-416).  Fetchables: opt, loss, mf_loss, reg_loss, batch_ratings.
+
+    weights: user_embedding [n_users, d], item_embedding [n_items, d], user_temp_bias [n_users, 1], item_temp_init_bias [n_items, T + 1]
+    (column t < T: the bias of time slot t, column T: the init bias), all Xavier-uniform, drawn in this order.  A step is
+    pda_temp_pop_adam_step_f32: the gradients of the four tables, then TF-1.14's dense-decay Adam over all of them ("BPRMF(t)-pop",
+    for the two quirks of the reference this keeps: the user bias trains on stage-0 triplets only, and one alpha per 2 048-user block)."""
+    with_pop = False
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, temp_api=None,
+                 raw_api=None, **kw):
+        if torch.device(kw.get("device") or "cuda").type != "cuda":
+            raise NotImplementedError("temp_pop runs on the GPU kernels only (pda_amd has no CPU path)")
+        self.temp_num = int(data_config["temp_num"])
+        if self.temp_num < 1:
+            raise ValueError("temp_pop needs at least one time slot (temp_num >= 1)")
+        if getattr(args, "optimizer", "adam") != "adam":
+            raise NotImplementedError("temp_pop runs the reference's Adam only (--optimizer adam)")
+        if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+            raise NotImplementedError("temp_pop runs the dense Adam sweep only (--adam_sweep auto | sweep)")
+        if getattr(args, "table_dtype", "f32") != "f32":
+            raise NotImplementedError("temp_pop runs fp32 tables only (--table_dtype f32)")
+        if int(getattr(args, "gpus", 1) or 1) > 1:
+            raise NotImplementedError("temp_pop runs on one GPU")
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        if self.emb_dim not in (64, 128, 256):
+            raise NotImplementedError("temp_pop: embed_size 64 / 128 / 256 (the bias-head score kernels)")
+        self.adam_exact_lazy = False
+        self._tp = None
+        self.opt, self.loss = Fetch(self, "opt"), Fetch(self, "loss")
+        self.mf_loss, self.reg_loss = Fetch(self, "mf_loss"), Fetch(self, "reg_loss")
+        self.batch_ratings = Fetch(self, "batch_ratings")
+
+    def init_weights(self, gen):
+        w = super().init_weights(gen)
+        w["user_temp_bias"] = xavier_uniform_(torch.empty(self.n_users, 1, device=self.device), gen)
+        w["item_temp_init_bias"] = xavier_uniform_(torch.empty(self.n_items, self.temp_num + 1, device=self.device), gen)
+        return w
+
+    def _tables(self):
+        w = self.weights
+        return w["user_embedding"], w["item_embedding"], w["user_temp_bias"], w["item_temp_init_bias"]
+
+    def _tp_state(self):
+        if self._tp is None:
+            self._tp = ops.TempPopState(*self._tables())
+        return self._tp
+
+    def item_beta(self) -> torch.Tensor:
+        """beta_i = fl(C[i, T-1] + C[i, T]): the most recent stage plus the init column (:390-393), float32 [n_items]."""
+        C = self.weights["item_temp_init_bias"]
+        return (C[:, self.temp_num - 1] + C[:, self.temp_num]).contiguous()
+
+    def user_alpha(self, first_users: torch.Tensor) -> torch.Tensor:
+        """alpha = fl(1 + bu[u]) for the given users (the first user of each user's evaluation block: quirk 2), float32."""
+        bu = self.weights["user_temp_bias"].view(-1)
+        return (bu.index_select(0, first_users.long()) + 1.0).contiguous()
+
+    def train_step(self, users, pos, neg, temps=None, raw=None, plan=None) -> torch.Tensor:
+        """One BPRMF(t)-pop step.  temps: float32 (or integer) time slot of each positive; raw (= arange(B) in the reference) is not needed.
+        Returns the float32[3] device tensor (loss, mf_loss, reg_loss) of this step, as the other models do."""
+        if temps is None:
+            raise ValueError("temp_pop needs the time slot of every positive (temps)")
+        if not temps.dtype == torch.float32:
+            temps = temps.to(torch.float32)
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._tp_state()
+        self._t += 1
+        ops.temp_pop_adam_step(*self._tables(), users, pos, neg, temps.contiguous(), st, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                               lr_t=ops.adam_lr_t(self.lr, self._t), loss_acc=self._loss)
+        return self._loss
+
+    CKPT_MOMENTS = ("mU", "mI", "mbu", "mC"), ("vU", "vI", "vbu", "vC")
+
+    def state_dict(self):
+        U, I, bu, C = self._tables()
+        sd = {"format": self.CKPT_FORMAT, "model": "temp_pop", "embed_size": self.emb_dim, "n_users": self.n_users, "n_items": self.n_items,
+              "temp_num": self.temp_num, "optimizer": self.optimizer, "table_dtype": self.table_dtype, "user_embedding": U, "item_embedding": I,
+              "user_temp_bias": bu, "item_temp_init_bias": C, "adam_t": self._t}
+        if self._tp is not None:
+            for names, tabs in zip(self.CKPT_MOMENTS, (self._tp.m, self._tp.v)):
+                sd.update(dict(zip(names, tabs)))
+        return sd
+
+    def load_state_dict(self, sd):
+        if not isinstance(sd, dict) or "user_embedding" not in sd:
+            raise ValueError("not a pda_amd checkpoint (a tf.train.Saver checkpoint of the reference cannot be loaded)")
+        if sd.get("model", "mf") != "temp_pop":
+            raise ValueError("checkpoint of a %s model cannot be loaded into BPRMFTempPop" % sd.get("model", "mf"))
+        for key, mine in (("embed_size", self.emb_dim), ("n_users", self.n_users), ("n_items", self.n_items), ("temp_num", self.temp_num)):
+            if int(sd[key]) != int(mine):
+                raise ValueError("checkpoint %s = %s, model has %s" % (key, sd[key], mine))
+        for k, t in zip(("user_embedding", "item_embedding", "user_temp_bias", "item_temp_init_bias"), self._tables()):
+            if tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError("checkpoint table %s does not have the model's shape" % k)
+            t.copy_(sd[k])
+        self._t = int(sd.get("adam_t", 0))
+        if "mU" in sd:
+            st = self._tp_state()
+            for names, tabs in zip(self.CKPT_MOMENTS, (st.m, st.v)):
+                for n, t in zip(names, tabs):
+                    t.copy_(sd[n])

@@ -1400,3 +1400,114 @@ def unpack_keys(keys: torch.Tensor):
     idx[empty] = -1
     val[empty] = -np.inf
     return idx, val
+
+
+# ---- BPRMF(t)-pop (include/pda_hip_temp_pop.h) ----------------------------------------------------------------------------------------------
+HEAD_BIAS = _lib.HEAD_BIAS
+
+
+class TempPopState:
+    """Adam state of the four BPRMF(t)-pop tables: m, v and the dense gradient accumulator of each, and the per-row step tags (a user tag
+    covers U and bu, an item tag covers I and C)."""
+
+    def __init__(self, U, I, bu, C):
+        z = torch.zeros_like
+        self.m = [z(U), z(I), z(bu), z(C)]
+        self.v = [z(U), z(I), z(bu), z(C)]
+        self.g = [z(U), z(I), z(bu), z(C)]
+        self.tagU = torch.zeros(U.shape[0], dtype=torch.int32, device=U.device)
+        self.tagI = torch.zeros(I.shape[0], dtype=torch.int32, device=U.device)
+
+
+def _temp_pop_tables(U, I, bu, C):
+    for t, n in ((U, "U"), (I, "I"), (bu, "bu"), (C, "C")):
+        _need(t, torch.float32, n)
+    if bu.numel() != U.shape[0] or C.dim() != 2 or C.shape[0] != I.shape[0] or C.shape[1] < 2 or U.shape[1] != I.shape[1]:
+        raise ValueError("temp_pop tables: U [n_users, d], I [n_items, d], bu [n_users(, 1)], C [n_items, T + 1] with T >= 1")
+    return U.shape[1], C.shape[1] - 1
+
+
+def _temp_pop_batch(users, pos, neg, temps):
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    temps = _need(temps, torch.float32, "temps")
+    B = users.numel()
+    if pos.numel() != B or neg.numel() != B or temps.numel() != B:
+        raise ValueError("users/pos/neg/temps must have the same length")
+    return users, pos, neg, temps, B
+
+
+def temp_pop_grads(U, I, bu, C, users, pos, neg, temps, st: TempPopState, *, regs: float, reg_div: float, step: int,
+                   loss_acc: Optional[torch.Tensor] = None):
+    """pda_temp_pop_step_f32: the batch's gradients summed into st.g (and the rows tagged with `step`), no update."""
+    d, T = _temp_pop_tables(U, I, bu, C)
+    users, pos, neg, temps, B = _temp_pop_batch(users, pos, neg, temps)
+    loss_acc = _need(loss_acc, torch.float32, "loss_acc", optional=True)
+    g = st.g
+    check(_lib.load().pda_temp_pop_step_f32(ptr(U), ptr(I), ptr(bu), ptr(C), ptr(users), ptr(pos), ptr(neg), ptr(temps), B, d, T, float(regs),
+                                            float(reg_div), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(st.tagU), ptr(st.tagI), int(step),
+                                            ptr(loss_acc), stream_ptr()), "pda_temp_pop_step_f32")
+
+
+def temp_pop_sweep(U, I, bu, C, st: TempPopState, *, step: int, lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS):
+    """pda_temp_pop_sweep_f32: TF-1.14 dense-decay Adam over the four tables (g read on the rows tagged `step`, cleared behind)."""
+    d, T = _temp_pop_tables(U, I, bu, C)
+    m, v, g = st.m, st.v, st.g
+    check(_lib.load().pda_temp_pop_sweep_f32(ptr(U), ptr(m[0]), ptr(v[0]), ptr(g[0]), ptr(st.tagU), U.shape[0], ptr(I), ptr(m[1]), ptr(v[1]),
+                                             ptr(g[1]), ptr(st.tagI), I.shape[0], ptr(bu), ptr(m[2]), ptr(v[2]), ptr(g[2]), ptr(C), ptr(m[3]),
+                                             ptr(v[3]), ptr(g[3]), d, T, int(step), float(lr_t), beta1, beta2, eps, stream_ptr()),
+          "pda_temp_pop_sweep_f32")
+    mark_modified(U, I, bu, C)
+
+
+def temp_pop_adam_step(U, I, bu, C, users, pos, neg, temps, st: TempPopState, *, regs: float, reg_div: float, step: int, lr_t: float,
+                       beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, loss_acc: Optional[torch.Tensor] = None):
+    """pda_temp_pop_adam_step_f32: one reference BPRMF(t)-pop step (gradients + Adam over the four tables) in two launches."""
+    d, T = _temp_pop_tables(U, I, bu, C)
+    users, pos, neg, temps, B = _temp_pop_batch(users, pos, neg, temps)
+    loss_acc = _need(loss_acc, torch.float32, "loss_acc", optional=True)
+    m, v, g = st.m, st.v, st.g
+    check(_lib.load().pda_temp_pop_adam_step_f32(ptr(U), ptr(m[0]), ptr(v[0]), ptr(g[0]), ptr(st.tagU), U.shape[0], ptr(I), ptr(m[1]), ptr(v[1]),
+                                                 ptr(g[1]), ptr(st.tagI), I.shape[0], ptr(bu), ptr(m[2]), ptr(v[2]), ptr(g[2]), ptr(C), ptr(m[3]),
+                                                 ptr(v[3]), ptr(g[3]), ptr(users), ptr(pos), ptr(neg), ptr(temps), B, d, T, float(regs),
+                                                 float(reg_div), int(step), float(lr_t), beta1, beta2, eps, ptr(loss_acc), stream_ptr()),
+          "pda_temp_pop_adam_step_f32")
+    mark_modified(U, I, bu, C)
+
+
+def score_topk_bias_keys(U, I_shard, users, alpha, beta, K=50, hist: Optional[HistoryCSR] = None, item_offset=0, n_splits=0,
+                         stats: Optional[dict] = None) -> torch.Tensor:
+    """pda_temp_pop_score_topk_f32: the bias head h = fl(s + fl(alpha_u beta_i)) -> packed keys int64 [n_splits, Bu, K].
+    alpha float32 [Bu] per block row, beta float32 [n_items_local].  The library picks the kernel (the pre-filtered one, given the item
+    prep, wherever it can run; PDA_TEMP_POP_KERNEL=exact | prefiltered forces one); stats["kernel_id"]: bias_kernel_identity()."""
+    lib = _lib.load()
+    U, I_shard = _need(U, torch.float32, "U"), _need(I_shard, torch.float32, "I_shard")
+    users = _need(users, torch.int32, "users")
+    alpha, beta = _need(alpha, torch.float32, "alpha"), _need(beta, torch.float32, "beta")
+    nu, nloc, d = users.numel(), I_shard.shape[0], I_shard.shape[1]
+    if alpha.numel() != nu or beta.numel() != nloc or U.shape[1] != d:
+        raise ValueError("alpha: one value per block row, beta: one per local item row; U and I_shard share the embed dim")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    if n_splits <= 0:
+        n_splits = lib.pda_score_topk_auto_splits(nu, nloc)
+    out = torch.empty((n_splits, nu, K), dtype=torch.int64, device=U.device)
+    ws = torch.empty(lib.pda_temp_pop_score_workspace_bytes(nu), dtype=torch.uint8, device=U.device)
+    prep = item_prep(I_shard)
+    check(lib.pda_temp_pop_score_topk_f32(ptr(U), ptr(I_shard), ptr(prep), ptr(alpha), ptr(beta), ptr(users), nu, item_offset, nloc, d,
+                                          ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
+                                          K, n_splits, ptr(out), ptr(ws), stream_ptr()), "pda_temp_pop_score_topk_f32")
+    if stats is not None:
+        stats["kernel_id"] = ws[16:20].view(torch.int32)
+    return out
+
+
+def bias_kernel_identity(word) -> dict:
+    """Decodes the identity word of a bias-head score call (stats["kernel_id"] of score_topk_bias_keys)."""
+    w = int(word) & 0xFFFFFFFF
+    return {"generation": w >> 28, "bias_head": bool((w >> 15) & 1), "d": (w & 15) * 64}
+
+
+def recommend_topk_bias(U, I_shard, users, alpha, beta, K=50, hist: Optional[HistoryCSR] = None, stats: Optional[dict] = None):
+    """Bias-head score + mask + top-K, merged -> (int32 [Bu, K] item ids, float32 [Bu, K] head values)."""
+    keys = score_topk_bias_keys(U, I_shard, users, alpha, beta, K, hist, stats=stats)
+    return topk_merge(keys, users, hist)

@@ -4,6 +4,7 @@ Sampler protocol of the reference (MF/train_new_api.py:178-220, 260-288, 366-412
 yielding, per step, a tuple of sequences of length batch_size -- (users, pos, neg) for BPRMF or
 (users, pos, neg, pos_pop, neg_pop) for PD/PDA -- exactly `n_train // batch_size + 1` times per epoch (:190).
 
+    host_generator_with_temp   the same for BPRMF(t)-pop (:415-455): (users, pos, neg, temp, raw).
     host_generator   single-process restatement of the reference's Python generators (same distribution:
                      rd.sample users, uniform positive with its time slot, rejection-sampled negative);
                      yields python lists like the reference, for drop-in use and for injecting fixed batches.
@@ -55,6 +56,35 @@ def host_generator(data, with_pop: bool):
         yield (users, pos, neg, ppop, npop) if with_pop else (users, pos, neg)
 
 
+def host_generator_with_temp(data):
+    """generator_n_batch_with_temp (:415-455), one process, one epoch: (users, pos, neg, temp, raw) -- temp is the time slot of the drawn
+    positive (a user without clicks: pos 0 and a slot drawn from unique_times), raw = arange(batch_size)."""
+    all_users = list(data.train_user_list.keys())
+    bs = data.batch_size
+    raw = np.arange(bs)
+    for _ in range(n_batches(data)):
+        if bs <= data.n_users:
+            users = rd.sample(all_users, bs)
+        else:
+            users = [rd.choice(all_users) for _ in range(bs)]
+        pos, neg, temp = [], [], []
+        for u in users:
+            clicked = data.train_user_list[u]
+            if not clicked:
+                p, t = 0, rd.choice(data.unique_times)
+            else:
+                idx = np.random.randint(len(clicked))
+                p, t = clicked[idx], data.train_user_list_time[u][idx]
+            while True:
+                n = rd.choice(data.items)
+                if n not in clicked:
+                    break
+            pos.append(p)
+            neg.append(n)
+            temp.append(t)
+        yield (users, pos, neg, temp, raw)
+
+
 def to_device_batch(batch, device):
     """Tuple of python lists / numpy arrays (sampler protocol) -> int32/float32 device tensors."""
     out = [torch.as_tensor(np.asarray(b, dtype=np.int32), device=device) for b in batch[:3]]
@@ -68,13 +98,18 @@ class DeviceSampler:
     batches as well, :178-220).  The batches are bit for bit those of ahead = 1 (one pda_sample_triplets launch per step); a
     batch handed out is a row view of the queue and stays valid until `ahead` further batches have been taken."""
 
-    def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32):
-        self.data, self.device, self.with_pop, self.seed = data, torch.device(device), with_pop, seed
+    def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0):
+        self.data, self.device, self.with_pop, self.seed = data, torch.device(device), with_pop or temp_slots > 0, seed
         self.indptr, self.indices, self.slots = data.train_csr(self.device)
         pool = np.fromiter(data.train_user_list.keys(), dtype=np.int32)   # all_users = users with train rows
         self.pool = torch.from_numpy(pool).to(self.device)
         self.pop = None
-        if with_pop:
+        if temp_slots > 0:
+            # BPRMF(t)-pop: the batch's 4th / 5th outputs carry the positive's time slot as a float, like the reference's placeholder
+            # (MF/train_new_api.py:575): the sampler reads a [n_items, T] matrix whose column t holds t.  A user without clicks draws its
+            # slot uniformly from [0, T) (the reference: from unique_times, the same set when every slot occurs in train)
+            self.pop = torch.arange(temp_slots, dtype=torch.float32, device=self.device).repeat(data.n_items, 1).contiguous()
+        elif with_pop:
             self.pop = torch.as_tensor(np.ascontiguousarray(data.expo_popularity, dtype=np.float32), device=self.device)
         self.neg_range = neg_range or (0, data.n_items)
         self.step = 0

@@ -28,9 +28,9 @@ import torch
 
 from . import ops
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import BPRMF, ConditionalBPRMF, Fetch
+from .model_api import BPRMF, BPRMFTempPop, ConditionalBPRMF, Fetch
 from .parse import parse_args
-from .sampler import DeviceSampler, host_generator, to_device_batch
+from .sampler import DeviceSampler, host_generator, host_generator_with_temp, to_device_batch
 
 # module-level singletons of the reference (MF/batch_test.py:6-19), filled by configure()/main()
 args = None
@@ -75,6 +75,13 @@ class Session:
         return [pick[f.name] for f in fetches]
 
 
+def reference_block_first(eval_pos: int, n: int, device=None, block: int = 2048) -> torch.Tensor:
+    """Evaluation-list positions eval_pos .. eval_pos + n - 1 -> the position of the first user of the reference's evaluation block of
+    `block` users each of them falls into (int64).  BPRMF(t)-pop's alpha comes from that user (quirk 2)."""
+    posn = torch.arange(eval_pos, eval_pos + n, device=device, dtype=torch.int64)
+    return torch.div(posn, block, rounding_mode="floor") * block
+
+
 class DatasetApi_Model:
     def __init__(self, args, data_config, test_batch, generator_sampler, device=None, topk_shard=None):
         self.args = args
@@ -90,6 +97,10 @@ class DatasetApi_Model:
             self.input_type = "with_pop"                                     # :547-549
             print("dataset api with pop or temp")
             self.Recommender = ConditionalBPRMF(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train == "temp_pop":
+            self.input_type = "with_temp"                                    # :547-551, :570-575
+            print("dataset api with pop or temp")
+            self.Recommender = BPRMFTempPop(args, data_config, use_dataset_api=True, device=self.device)
         elif args.train == "normal":
             self.input_type = "without_pop"                                  # :558-559
             print("dataset api without pop")
@@ -176,8 +187,25 @@ class DatasetApi_Model:
         idx, _ = self.recommend_device(batch_users, items, rec_type, pos_pop, sparse_cliked_matrix)
         return idx.cpu().numpy()
 
-    def recommend_device(self, batch_users, items, rec_type, pos_pop=None, mask=None, K=None):
-        if rec_type == "main_branch":
+    # the reference scores its evaluation users in blocks of this many (MF/train_new_api.py:703); BPRMF(t)-pop's alpha depends on it (quirk 2)
+    REFERENCE_EVAL_BLOCK = 2048
+
+    def temp_pop_alpha(self, users, eval_pos=None, eval_users=None):
+        """alpha of BPRMF(t)-pop's bias head for a block of users (quirk 2): do_recommendation feeds temp = raw = [[0]], so every
+        user of a reference block of 2 048 evaluation users gets 1 + bu of that block's FIRST user.  eval_pos: the position of users[0] in the
+        evaluation list eval_users -- any block size then gives the reference's alpha; without it the block itself is one reference block."""
+        n = users.numel()
+        if eval_pos is None:
+            first = users[:1].expand(n)
+        else:
+            first = eval_users.index_select(0, reference_block_first(eval_pos, n, users.device))
+        return self.Recommender.user_alpha(first)
+
+    def recommend_device(self, batch_users, items, rec_type, pos_pop=None, mask=None, K=None, eval_pos=None, eval_users=None):
+        if self.input_type == "with_temp":
+            if rec_type != "main_branch":
+                raise NotImplementedError("temp_pop evaluates the main_branch head only (--test temp_pop)")
+        elif rec_type == "main_branch":
             head, pos_pop = ops.HEAD_RAW, None
         elif rec_type in ("main_with_pop", "condition"):
             if rec_type == "condition" and self.input_type != "with_pop":
@@ -197,6 +225,12 @@ class DatasetApi_Model:
             pop_t = pos_pop if torch.is_tensor(pos_pop) else self._pop_on_device(pos_pop)
         K = K or self.topk_max
         I, _sel = self._tables(items)
+        if self.input_type == "with_temp":
+            beta = self.Recommender.item_beta()
+            if _sel is not None:
+                beta = beta.index_select(0, _sel).contiguous()
+            alpha = self.temp_pop_alpha(users, eval_pos, eval_users)
+            return ops.recommend_topk_bias(self.Recommender.score_tables()[0], I, users, alpha, beta, K, hist)
         if self._shard is not None and _sel is None:
             self._shard.set_popularity(pop_t)
             return self._shard.topk(users, K, head, hist)
@@ -218,6 +252,17 @@ class DatasetApi_Model:
         pop = None
         if model_type == "condition":
             pop = torch.as_tensor(np.asarray(pos_pop, dtype=np.float32).reshape(-1), device=self.device)
+        if self.input_type == "with_temp":
+            if model_type != "main_branch":
+                raise NotImplementedError("temp_pop has the main_branch ratings only")
+            # batch_ratings of BPRMFTempPop (:380-396) for a batch fed like do_recommendation feeds it (temp = raw = [[0]]): the first user's
+            # alpha for every row.  The reference's own testing() feeds no temp / raw and cannot run this model.
+            beta = self.Recommender.item_beta()
+            if it_t is not None:
+                beta = beta.index_select(0, it_t.long())
+            alpha = self.temp_pop_alpha(users)
+            s = ops.score_dense(U, I, users, ops.HEAD_RAW, None, it_t)
+            return (s + alpha[:, None] * beta[None, :]).cpu().numpy()
         return ops.score_dense(U, I, users, ops.HEAD_POP if model_type == "condition" else ops.HEAD_RAW, pop, it_t).cpu().numpy()
 
     def switch_to_testing_or_reinit(self, sess=None, feed_dict=None):
@@ -294,7 +339,7 @@ class evaluation:
         sums = torch.zeros((4, len(self.Ks)), dtype=torch.float64, device=self.device)
         for i in range(0, self.tot_user, self.batch_size):
             ub = self.users_dev[i:i + self.batch_size]
-            idx, _ = model.recommend_device(ub, None, rec_type, pop, self._hist)
+            idx, _ = model.recommend_device(ub, None, rec_type, pop, self._hist, eval_pos=i, eval_users=self.users_dev)
             tp = self._tp_host[i:i + ub.numel() + 1]
             tptr = torch.from_numpy(tp - tp[0]).to(self.device)
             ops.metrics_sums(idx, tptr, self.tgt_indices[int(tp[0]):int(tp[-1])], ks, sums)
@@ -325,6 +370,20 @@ def configure(argv=None):
     Ks = eval(args.Ks)            # the reference evals this literal too (batch_test.py:16)
     ITEM_NUM, USER_NUM = data.n_items, data.n_users
     return args, data
+
+
+def check_temp_slots(data_, T: int):
+    """BPRMF(t)-pop reads C[i, t] for the slot t of every train interaction: a slot >= T would read the init column (t == T) or past the
+    table (the reference: silently 0 on a GPU).  Refused here, when the data is loaded."""
+    top = -1
+    for ts in data_.train_user_list_time.values():
+        if ts:
+            top = max(top, max(ts))
+    lo = min((min(ts) for ts in data_.train_user_list_time.values() if ts), default=0)
+    if top >= T or lo < 0:
+        raise ValueError("train time slots span [%d, %d], the popularity file has T = %d stages: temp_pop needs 0 <= slot < T" % (lo, top, T))
+    if any(t < 0 or t >= T for t in getattr(data_, "unique_times", [])):
+        raise ValueError("unique_times holds a slot outside [0, %d)" % T)
 
 
 def _print_result(ret):   # :1118-1123
@@ -376,10 +435,22 @@ def main(argv=None):
         print("   each stage min:", popularity_matrix.min(axis=0))
         data.add_expo_popularity(popularity_matrix)
         with_pop = True
+    elif args.model == "mf" and args.train == "temp_pop":                        # :999-1005
+        print("-------    running temproal pop MF  ----------------")
+        config["temp_num"] = pop_item_all.shape[1] - 1
+        args.saveID += "temp_pop"
+        print("save_ID", args.saveID)
+        data.add_expo_popularity(None)
+        check_temp_slots(data, config["temp_num"])
     else:
         raise NotImplementedError("do not implement this method")               # :1008
 
-    if args.sampler == "device":
+    if args.train == "temp_pop":
+        if args.sampler == "device":
+            sampler = DeviceSampler(data, device, False, temp_slots=config["temp_num"])
+        else:
+            sampler = (lambda: host_generator_with_temp(data))
+    elif args.sampler == "device":
         sampler = DeviceSampler(data, device, with_pop)
     else:
         sampler = (lambda: host_generator(data, with_pop))
@@ -463,6 +534,14 @@ def main(argv=None):
             print("||------------PDA/PDGA injecting linear predicted popularity testing : time: ", int(time() - ttt1))
             _print_result(ret2)
             ret = ret1
+        elif args.test == "temp_pop":                                            # :1192-1200
+            print(perf_str)
+            ttt1 = time()
+            evaluation_model.set_testing_popularity(None)
+            ret_main = evaluation_model.eval(model, sess, rec_type="main_branch")
+            print("test: time:", time() - ttt1)
+            _print_result(ret_main)
+            ret = ret_main
         elif args.test == "normal":                                              # :1159-1191
             print(perf_str)
             ttt1 = time()
@@ -553,6 +632,11 @@ def main(argv=None):
             print("|||---BPRMF-A with injecting %s:" % name)
             _print_result(r)
         print("----------------------------")
+    elif args.test == "temp_pop":                                                # :1310-1314
+        evaluation_model.set_testing_popularity(None)
+        ret = evaluation_model.eval(model, sess, rec_type="main_branch")
+        print("---- result with last pop bias for temp_pop model:")
+        _print_result(ret)
     print("training and testing end!!!!")
     print("|||  ------------------------ best performance for model selected by PD/PDG/BPRMF ------------------- |||")
     print("main best epoch:", config_main["best_epoch"])

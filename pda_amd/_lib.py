@@ -1,4 +1,4 @@
-"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h and pda_hip_temp_pop.h).
+"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h and pda_hip_pc.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -139,6 +139,18 @@ TEMP_POP_SIGNATURES = {
     "pda_temp_pop_score_topk_f32": (_i, [_vp] * 6 + [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_pc.h (BPR-PC)
+HEAD_PC = 3
+PC_MAX_K = 50
+_d = C.c_double
+PC_SIGNATURES = {
+    "pda_pc_moments_workspace_bytes": (_sz, [_i, _i]),
+    "pda_pc_item_moments_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "pda_pc_user_stats_f32": (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp]),
+    "pda_pc_score_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pda_pc_score_topk_f32": (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp, _i, _d, _d, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -156,7 +168,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

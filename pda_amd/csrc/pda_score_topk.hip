@@ -28,6 +28,7 @@
 //                32-bit mask per (user, tile) that is consulted only on the slow path.
 #include "pda_topk_common.h"
 #include "pda_hip_temp_pop.h"
+#include "pda_hip_pc.h"
 #include <cstdlib>
 
 namespace {
@@ -39,6 +40,9 @@ using namespace pda_topk;
 // BF: the tables are bf16 (pda_score_topk_bf16's exact fallback); rows are widened to fp32 on load -- same arithmetic.
 // HEAD = PDA_HEAD_BIAS (temp_pop, include/pda_hip_temp_pop.h): h = fl(s + fl(alpha_u beta_i)), beta behind a.pop; this head has no fallback
 // mode, and a.tile_flags carries its workspace instead: the identity word is written at +16, alpha (per block row) is read from +64.
+// HEAD = PDA_HEAD_PC (BPR-PC, include/pda_hip_pc.h): r = fl(s + fl(a fl(C k_u))), C = fl(fl(fl(s b) + w) p_i), p behind a.pop; ranks by r and
+// writes the per-row minimum of r over every item of the split (listed ones included).  HEAD = kHeadPcG: ranks by g = fl(fl(r - m_u) + e).
+// Both read their constants, k_u (and m_u) from the sweep block behind a.tile_flags (pda_topk_common.h).
 template <int D, int HEAD, int ABL = 0, bool BF = false>
 __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kernel(ScoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -55,7 +59,8 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
     const int j = lane & 31, h = lane >> 5;
     const int split = blockIdx.x % a.n_splits, utile = blockIdx.x / a.n_splits;
     const int K = a.K;
-    if constexpr (HEAD != PDA_HEAD_BIAS)
+    constexpr bool kPc = HEAD == PDA_HEAD_PC || HEAD == kHeadPcG;
+    if constexpr (HEAD != PDA_HEAD_BIAS && !kPc)
         if (a.tile_flags != nullptr && a.tile_flags[utile] == 0) return;   // v2 fallback mode: only flagged user tiles
 
     const int tiles_total = (a.n_items_local + 31) >> 5;
@@ -126,6 +131,34 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
         }
         if (blockIdx.x == 0 && tid == 0) *reinterpret_cast<unsigned*>(ws + 16) = (1u << 28) | (1u << 15) | (unsigned)(D >> 6);
     }
+    f32x16 pck, pcm, rmin;   // PC heads: k_u and m_u of the row of accumulator register r (the layout of thr); the running minimum of r
+    float pca = 0.f, pcb = 0.f, pcw = 0.f, pce = 0.f;
+    if constexpr (kPc) {
+        unsigned char* ws = reinterpret_cast<unsigned char*>(const_cast<int*>(a.tile_flags));
+        const float* cst = reinterpret_cast<const float*>(ws + 32);
+        pca = cst[0];
+        pcb = cst[1];
+        pcw = cst[2];
+        pce = cst[3];
+        const int cap = *reinterpret_cast<const int*>(ws + 48);
+        const float* kk = reinterpret_cast<const float*>(ws + kPcBlockHdr);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rb = min(utile * kUserTile + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, a.n_users_blk - 1);
+            pck[r] = kk[rb];
+            pcm[r] = HEAD == kHeadPcG ? kk[cap + rb] : 0.f;
+            rmin[r] = INFINITY;
+        }
+        if (HEAD == PDA_HEAD_PC && blockIdx.x == 0 && tid == 0)
+            *reinterpret_cast<unsigned*>(ws + 16) = (1u << 28) | (1u << 16) | (unsigned)(D >> 6);
+    }
+    // PC heads: r of score sc (popv = p_i), in TF's op order; kHeadPcG: g of it
+    auto pc_head = [&](float sc, float popv, int r) -> float {
+        const float C = (sc * pcb + pcw) * popv;
+        const float rr = sc + pca * (C * pck[r]);
+        if constexpr (HEAD == kHeadPcG) return (rr - pcm[r]) + pce;
+        return rr;
+    };
 
     // ---- item tile staging -------------------------------------------------------------------
     f32x4 pre[NLD];
@@ -150,7 +183,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
         }
     };
     auto pop_load = [&](int t) -> float {
-        if constexpr (HEAD == PDA_HEAD_POP || HEAD == PDA_HEAD_BIAS) return a.pop[min(t * 32 + j, a.n_items_local - 1)];
+        if constexpr (HEAD == PDA_HEAD_POP || HEAD == PDA_HEAD_BIAS || kPc) return a.pop[min(t * 32 + j, a.n_items_local - 1)];
         return 1.0f;
     };
     // History bits of tile t for my row.  Branch-free for the common case (at most one train item of the row
@@ -212,6 +245,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
                 float tt = accv[r];   // exact head value (the fast test only saw an upper bound)
                 if constexpr (HEAD == PDA_HEAD_POP) tt = (tt > 0.0f ? tt + 1.0f : __expf(tt)) * popv;
                 if constexpr (HEAD == PDA_HEAD_BIAS) tt = tt + alr[r] * popv;
+                if constexpr (kPc) tt = pc_head(tt, popv, r);
                 bool p = lane_ok && ((still >> r) & 1u) && (tt > thr[r]);
                 const int rowb = (r & 3) + 8 * (r >> 2);
                 if (any_hb) {   // train items never enter
@@ -250,13 +284,22 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
     auto head_ub = [&](float sc, float popv, int r) -> float {
         if constexpr (HEAD == PDA_HEAD_POP) return (fmaxf(sc, 0.0f) + 1.0f) * popv;
         if constexpr (HEAD == PDA_HEAD_BIAS) return sc + alr[r] * popv;
+        if constexpr (kPc) return pc_head(sc, popv, r);
         return sc;
+    };
+    // PDA_HEAD_PC: the exact head, tested, and folded into the row's running minimum.  Every lane takes part: listed items count, and
+    // lanes past the end of the catalogue score the last item again (clamped loads), which leaves the minimum as it is.  `live` is
+    // false for the empty accumulator ahead of the first tile.
+    auto head_test = [&](float sc, float popv, int r, bool live) -> float {
+        const float hv = head_ub(sc, popv, r);
+        if constexpr (HEAD == PDA_HEAD_PC) rmin[r] = fminf(rmin[r], live ? hv : INFINITY);
+        return hv;
     };
     auto fast_test = [&](const f32x16& accv, float popv, uint64_t vmask) -> uint32_t {
         uint32_t regmask = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            regmask |= (__ballot(head_ub(accv[r], popv, r) > thr[r]) & vmask) ? (1u << r) : 0u;
+            regmask |= (__ballot(head_test(accv[r], popv, r, true) > thr[r]) & vmask) ? (1u << r) : 0u;
         return regmask;
     };
 
@@ -306,7 +349,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
             if constexpr (!(ABL & 2)) {
 #pragma unroll
                 for (int r = (16 * c) / NC; r < (16 * (c + 2)) / NC; ++r)
-                    regmask |= (__ballot(head_ub(acc_prev[r], popj_prev, r) > thr[r]) & vmask_prev) ? (1u << r) : 0u;
+                    regmask |= (__ballot(head_test(acc_prev[r], popj_prev, r, t > t0) > thr[r]) & vmask_prev) ? (1u << r) : 0u;
             }
         }
         if constexpr (ABL & 2) asm volatile("" ::"v"(acc_prev[0]), "v"(acc_prev[7]), "v"(acc_prev[15]));
@@ -317,7 +360,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, (HEAD == PDA_HEAD_RAW ? 16 : 64) / (4 * NC) + 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, (HEAD == PDA_HEAD_RAW ? 16 : kPc ? 144 : 64) / (4 * NC) + 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x004, 1, 0);
             }
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -348,6 +391,26 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) score_topk_kerne
     if (t0 < t1) {   // drain: threshold test + slow path of the last tile
         const uint32_t regmask = fast_test(acc_prev, popj_prev, vmask_prev);
         if (!(ABL & 1) && regmask) slow_path(regmask, acc_prev, popj_prev, vmask_prev, hb_prev, a.item_offset + (t1 - 1) * 32);
+    }
+
+    if constexpr (HEAD == PDA_HEAD_PC) {   // the per-row minimum of r over this split: lanes j of each half hold one row's items
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = rmin[r];
+#pragma unroll
+            for (int o = 1; o < 32; o <<= 1) v = fminf(v, __shfl_xor(v, o, 64));
+            rmin[r] = v;
+        }
+        unsigned char* ws = reinterpret_cast<unsigned char*>(const_cast<int*>(a.tile_flags));
+        const int cap = *reinterpret_cast<const int*>(ws + 48);
+        float* rm_out = reinterpret_cast<float*>(ws + kPcBlockHdr) + 2 * (size_t)cap + (size_t)split * cap;
+        if (j == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rb = utile * kUserTile + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (rb < a.n_users_blk) rm_out[rb] = rmin[r];
+            }
+        }
     }
 
     // ---- finalise: sort every row's list, emit K packed keys (0 = empty) -------------------------
@@ -476,6 +539,15 @@ int pda_topk::launch_score_bias(const ScoreArgs& a, int d, hipStream_t s) {
         case 64: return launch_score<64, PDA_HEAD_BIAS>(a, s);
         case 128: return launch_score<128, PDA_HEAD_BIAS>(a, s);
         case 256: return launch_score<256, PDA_HEAD_BIAS>(a, s);
+        default: return PDA_ERR_UNSUPPORTED;
+    }
+}
+
+int pda_topk::launch_score_pc(const ScoreArgs& a, int d, bool by_g, hipStream_t s) {
+    switch (d) {
+        case 64: return by_g ? launch_score<64, kHeadPcG>(a, s) : launch_score<64, PDA_HEAD_PC>(a, s);
+        case 128: return by_g ? launch_score<128, kHeadPcG>(a, s) : launch_score<128, PDA_HEAD_PC>(a, s);
+        case 256: return by_g ? launch_score<256, kHeadPcG>(a, s) : launch_score<256, PDA_HEAD_PC>(a, s);
         default: return PDA_ERR_UNSUPPORTED;
     }
 }

@@ -24,8 +24,16 @@ struct ScoreArgs {
     int K;
     int n_splits;
     const int* tile_flags;   // optional [n_user_tiles]: only flagged tiles are computed (v2's exact fallback).  Generation 1's bias head
-                             // (PDA_HEAD_BIAS) has no fallback mode and receives its workspace here instead (alpha at +64, identity at +16)
+                             // (PDA_HEAD_BIAS) has no fallback mode and receives its workspace here instead (alpha at +64, identity at +16);
+                             // so do the PC heads (PDA_HEAD_PC, kHeadPcG: the sweep block of pda_pc.hip, layout below)
 };
+
+// BPR-PC (include/pda_hip_pc.h): generation 1's second PC mode ranks by g = RN32(RN32(r - m) + e) with m given per row (the fallback
+// of pda_pc_score_topk_f32 only).  Both PC heads read the "sweep block" behind a.tile_flags:
+//   +16 identity word (written), +32 a, +36 b, +40 w, +44 e (f32), +48 cap (int),
+//   +256 k f32 [cap] (per block row), then m f32 [cap] (kHeadPcG), then the per-row minimum of r f32 [n_splits][cap] (PDA_HEAD_PC, written)
+constexpr int kHeadPcG = 4;
+constexpr int kPcBlockHdr = 256;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -102,6 +110,8 @@ int launch_score_v1(const ScoreArgs& a, int d, int head, hipStream_t stream, boo
 // generation 1 with the temp_pop bias head (PDA_HEAD_BIAS of include/pda_hip_temp_pop.h): beta behind a.pop, a.tile_flags = the workspace
 // (identity word at +16, alpha per block row from +64)
 int launch_score_bias(const ScoreArgs& a, int d, hipStream_t stream);
+// generation 1 with a PC head (PDA_HEAD_PC: rank by r, or kHeadPcG: rank by g): a.pop = p_i, a.tile_flags = the sweep block
+int launch_score_pc(const ScoreArgs& a, int d, bool by_g, hipStream_t stream);
 // generation 3 with the bias head, natural order, fp32 tables (pda_score_topk_v3.hip)
 int launch_score_v3_bias(const ScoreArgs2& aa, int d, hipStream_t stream);
 // the bias head through generation 3 from a pda_item_prep_f32 prep (pda_score_prep.hip): PDA_ERR_UNSUPPORTED where generation 3 cannot run

@@ -1511,3 +1511,113 @@ def recommend_topk_bias(U, I_shard, users, alpha, beta, K=50, hist: Optional[His
     """Bias-head score + mask + top-K, merged -> (int32 [Bu, K] item ids, float32 [Bu, K] head values)."""
     keys = score_topk_bias_keys(U, I_shard, users, alpha, beta, K, hist, stats=stats)
     return topk_merge(keys, users, hist)
+
+
+# ---- BPR-PC (include/pda_hip_pc.h) ------------------------------------------------------------------------------------------------------
+HEAD_PC = _lib.HEAD_PC
+PC_MAX_K = _lib.PC_MAX_K
+
+
+def _pc_check(I, pop):
+    if I is not None and I.dtype == torch.bfloat16:
+        raise TypeError("BPR-PC runs on fp32 tables only (bf16 tables are not supported)")
+    I = _need(I, torch.float32, "I")
+    d = I.shape[1]
+    if d not in (64, 128, 256):
+        raise ValueError(f"BPR-PC supports embed sizes 64, 128 and 256, not {d}")
+    pop = _need(pop, torch.float32, "pop")
+    if pop.numel() != I.shape[0]:
+        raise ValueError("pop: one value per item of the full catalogue")
+    if not bool(torch.isfinite(pop).all()) or not bool((pop > 0).all()):
+        raise ValueError("pop must be finite and > 0 (p_i = 1 / pop_i)")
+    return I, pop, d
+
+
+def _pc_finite(name, x):
+    if not math.isfinite(float(x)):
+        raise ValueError(f"{name} must be finite, got {x}")
+    return float(x)
+
+
+def pc_item_moments(I, pop) -> torch.Tensor:
+    """pda_pc_item_moments_f32: float64 [2 d^2 + d + 1] = G (sum v v^T), H (sum p^2 v v^T), h (sum p^2 v), P (sum p^2), p = RN32(1 / pop)."""
+    lib = _lib.load()
+    I, pop, d = _pc_check(I, pop)
+    n = I.shape[0]
+    out = torch.empty(2 * d * d + d + 1, dtype=torch.float64, device=I.device)
+    ws = torch.empty(lib.pda_pc_moments_workspace_bytes(n, d), dtype=torch.uint8, device=I.device)
+    check(lib.pda_pc_item_moments_f32(ptr(I), ptr(pop), n, d, ptr(out), ptr(ws), stream_ptr()), "pda_pc_item_moments_f32")
+    return out
+
+
+def split_moments(mom: torch.Tensor, d: int):
+    """-> (G [d, d], H [d, d], h [d], P) views of a pc_item_moments vector."""
+    return (mom[:d * d].view(d, d), mom[d * d:2 * d * d].view(d, d), mom[2 * d * d:2 * d * d + d], mom[2 * d * d + d])
+
+
+def pc_user_stats(U, I, users, pop, beta, hist: Optional[HistoryCSR] = None, moments: Optional[torch.Tensor] = None):
+    """pda_pc_user_stats_f32 -> (U_n, U_c, k) float32 [Bu] each: the per-row norms of BPR-PC and k_u = U_n / U_c (0 where n_u or U_c is 0)."""
+    lib = _lib.load()
+    I, pop, d = _pc_check(I, pop)
+    if U is not None and U.dtype == torch.bfloat16:
+        raise TypeError("BPR-PC runs on fp32 tables only (bf16 tables are not supported)")
+    U = _need(U, torch.float32, "U")
+    users = _need(users, torch.int32, "users")
+    if U.shape[1] != d:
+        raise ValueError("U and I must share the embed dim")
+    beta = _pc_finite("beta", beta)
+    if moments is None:
+        moments = pc_item_moments(I, pop)
+    moments = _need(moments, torch.float64, "moments")
+    nu = users.numel()
+    out = torch.empty((3, nu), dtype=torch.float32, device=U.device)
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    check(lib.pda_pc_user_stats_f32(ptr(U), ptr(I), ptr(pop), ptr(moments), ptr(users), nu, I.shape[0], d,
+                                    ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
+                                    beta, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()), "pda_pc_user_stats_f32")
+    return out[0], out[1], out[2]
+
+
+def pc_kernel_identity(word) -> dict:
+    """Decodes the identity word of a BPR-PC score call (stats["kernel_id"] of recommend_topk_pc)."""
+    w = int(word) & 0xFFFFFFFF
+    return {"generation": w >> 28, "pc_head": bool((w >> 16) & 1), "d": (w & 15) * 64}
+
+
+def recommend_topk_pc(U, I, users, pop, scale, alpha, beta, K=50, hist: Optional[HistoryCSR] = None, rows_per_min: int = 2048,
+                      stats: Optional[dict] = None):
+    """pda_pc_score_topk_f32: BPR-PC's ranking of a block of users over the full catalogue -> (idx int32 [Bu, K], val float32 [Bu, K] = g).
+    scale float32 [Bu]: k_u of each row (pc_user_stats); m is the minimum of r over each group of rows_per_min rows.  stats (optional)
+    receives "kernel_id" (pc_kernel_identity) and "pc_fallback_rows" (rows the ranking by r could not settle, swept again by g)."""
+    lib = _lib.load()
+    I, pop, d = _pc_check(I, pop)
+    if U is not None and U.dtype == torch.bfloat16:
+        raise TypeError("BPR-PC runs on fp32 tables only (bf16 tables are not supported)")
+    U = _need(U, torch.float32, "U")
+    users = _need(users, torch.int32, "users")
+    scale = _need(scale, torch.float32, "scale")
+    nu, n = users.numel(), I.shape[0]
+    if U.shape[1] != d or scale.numel() != nu:
+        raise ValueError("U and I share the embed dim; scale has one value per block row")
+    if not 1 <= K <= PC_MAX_K:
+        raise ValueError(f"BPR-PC needs 1 <= K <= {PC_MAX_K}, got {K}")
+    if K > n:
+        raise ValueError(f"K = {K} exceeds the catalogue ({n} items)")
+    alpha, beta = _pc_finite("alpha", alpha), _pc_finite("beta", beta)
+    if int(rows_per_min) < 1:
+        raise ValueError("rows_per_min must be >= 1")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    idx = torch.empty((nu, K), dtype=torch.int32, device=U.device)
+    val = torch.empty((nu, K), dtype=torch.float32, device=U.device)
+    ws = torch.empty(lib.pda_pc_score_workspace_bytes(nu, n, d, K) + 256, dtype=torch.uint8, device=U.device)
+    off = (-ws.data_ptr()) % 256
+    wsa = ws[off:]
+    check(lib.pda_pc_score_topk_f32(ptr(U), ptr(I), ptr(pop), ptr(scale), ptr(users), nu, n, d, ptr(hist.indptr) if hist else None,
+                                    ptr(hist.indices) if hist else None, hist.mode if hist else 0, alpha, beta, int(rows_per_min), K,
+                                    ptr(idx), ptr(val), ptr(wsa), stream_ptr()), "pda_pc_score_topk_f32")
+    if stats is not None:
+        stats["kernel_id"] = wsa[16:20].view(torch.int32)
+        stats["pc_fallback_rows"] = int(wsa[20:24].view(torch.int32).item())
+    return idx, val

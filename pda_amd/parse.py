@@ -19,8 +19,8 @@ _REFERENCE_FLAGS = [
     ("save_dir", None, "/data/zyang/save_model/", "checkpoint root"),
     ("alpha", float, 1e-3, "(unused; appears in the checkpoint directory name)"),
     ("beta", float, 1e-3, "(unused)"),
-    ("pc_alpha", float, 0.1, "(unused)"),
-    ("pc_beta", float, 0.1, "(unused)"),
+    ("pc_alpha", float, 0.1, "BPR-PC (python -m pda_amd.bpr_pc): weight alpha of the popularity compensation"),
+    ("pc_beta", float, 0.1, "BPR-PC: beta of the compensation C = (beta s + 1 - beta) / pop"),
     ("exp_init_values", float, 0.1, "(unused)"),
     ("pop_exp", float, 0.1, "popularity exponent gamma"),
     ("early_stop", int, 1, "1: stop when recall@Ks[0] stalls"),

@@ -297,6 +297,13 @@ class evaluation:
     def set_evaluate_obj(self, eval_who="test"):
         self.eval_who = eval_who
 
+    def set_clicked_value_type(self, value_type):
+        """MF/BPR_PC.py's evaluation feeds the history mask with -inf ('inf') or 1.0 ('pc', BPR-PC).  The CSR masks used here carry no
+        values: the model that ranks decides what a listed item is worth, so this records the choice and changes nothing else."""
+        if value_type not in ("inf", "pc"):
+            raise ValueError("clicked value type must be 'inf' or 'pc', not %r" % (value_type,))
+        self.value_type = value_type
+
     def set_testing_popularity(self, popularity):
         """MF/train_new_api.py:710.  The reference indexes testing_popularity[range(ITEM_NUM)] (:788): a vector longer than the
         catalogue is cut to n_items here, a shorter one is an error (there: IndexError at the first evaluation)."""

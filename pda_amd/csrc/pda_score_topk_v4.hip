@@ -109,6 +109,13 @@ struct Args4 {
                                  // case, workgroups whose user tile lies beyond the count leave at once; rows beyond it inside a tile score the padding user)
     int lists_empty;             // phase 4: no warm-up ran on this catalogue -- every split starts with empty lists and sweeps ALL its tiles against
                                  // the caller's seed (the warm-up ran elsewhere: on replicated hot items, pda_amd.dist)
+    // the huge geometry's decided half-tile (pda_v5_sweep.h): the prep's suffix maxima per 64-item tile of the visiting order, max |pop| and
+    // max |pop| ||i|| over everything at or behind the tile (tile_bound4_kernel / suffix_max4_kernel) -- ALWAYS set for the popularity head,
+    // dense sweeps included: sufA / sufB above stay NULL there, that is what selects the dense path.  sweep5_kernel runs only for the
+    // popularity head on a prep built with the caller's pop_shard (prep_hdr_pop; ops.item_prep4 keys its cached prep on that vector), so
+    // these are the maxima of the very popularities being ranked.  NULL: the sweep tests every half-tile.
+    const float* tailA;
+    const float* tailB;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2076,6 +2083,10 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     g.warm_final = (geometry >= 4 && phase == 3 && g.handover != nullptr && g.prep_hdr_pop && !early_stop) ? 1 : 0;
     g.lists_empty = from_empty ? 1 : 0;
     g.n_users_dev = n_users_dev;
+    if (g.prep_hdr_pop) {                // the suffix bounds of the popularities being ranked: the huge geometry's decided half-tile
+        g.tailA = reinterpret_cast<const float*>(pb + L.sufA);
+        g.tailB = reinterpret_cast<const float*>(pb + L.sufB);
+    }
     // one call over several item splits: ONE exact warm-up per user instead of one per split (warm_tiles_of; PDA_SWEEP_WARM_PER_SPLIT)
     if (phase == 3 && n_splits > 1 && seed == nullptr && !warm_per_split && L.n_tiles > n_splits * warm_tiles) {
         g.warm_shared = 1;

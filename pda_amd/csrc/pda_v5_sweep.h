@@ -20,6 +20,16 @@
 //     loop together, score that half-tile (and the one behind it) again with compiler-visible MFMAs, rescore the candidates exactly
 //     (the fp32 chain of the oracle, generation 4's lists and compaction) and re-enter.  In a dense sweep in visiting order that is a
 //     fraction of a candidate per user behind the exact warm-up.
+//   * TWO loop bodies (tools/gen_v6_loop_asm.py): the tested one above, and a TEST-FREE one (Loop6Free::run) for the half-tiles behind
+//     the workgroup's DECIDED half-tile -- the first from which the suffix bound of the visiting order (Args4::tailA / tailB: the maxima
+//     of |pop| and |pop| ||i|| over everything at or behind a 64-item tile) lies below every threshold of the workgroup:
+//         fmaf(nw, tailB[T], tailA[T]) * 1.000002f < tw      (nw: the largest padded norm, tw: the lowest lowered threshold of its rows)
+//     -- the criterion that ENDS generation 4's early-terminating sweeps.  Behind it the outcome of every threshold test is known to be
+//     "no flag"; a dense sweep goes on scoring (the same LDS-DMA pieces, fragment reads, barrier per half-tile and MFMAs on the same
+//     operands: tiles_scored counts them as before) without the maxima, compares, clamp, publish, flag word, meta entry and ct.  The
+//     decided half-tile is worked out at every (re-)entry from the thresholds as they are then (they only rise); the tested body gets it as
+//     its end, so every flag below it has been acted on when it returns, and Loop6Free::run takes over from there to the end of the split.
+//     In config 3 that is 94 % of the half-tiles (workspace + 28 counts them: stats["huge_free_halftiles"]).  -DPDA_V5_NO_FREE: never.
 // Everything else is generation 4's: warm4_kernel's exact lists (handed over through the workspace), the packed keys, the epilogue.
 // Popularity head, d = 64 / 128, dense sweeps (no early termination); selected by the caller's hint PDA_SWEEP_HUGE.
 #pragma once
@@ -28,6 +38,7 @@
 #else
 #include "pda_v6_loop_asm.h"           // the loop, on v_mfma_f32_16x16x32_bf16 (tools/gen_v6_loop_asm.py)
 #endif
+#include "pda_v6_free_asm.h"           // its test-free bodies (tools/gen_v6_loop_asm.py --free: made by the Makefile, not kept in the repository)
 
 #ifdef PDA_V5_LOG
 __device__ unsigned pda_v5_log[1 << 18];      // debug build: [0] = entries used; then (block << 8 | wave, kind, a, b) per event
@@ -157,6 +168,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) eu = fmaxf(eu, __shfl_xor(eu, o, 64));
+        const float numax = eu;                                          // the wave's largest padded ||u|| (the decided half-tile)
         eu = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(eu * (kEps5 * 1.001f))));       // eps x the wave's largest ||u||, wave-uniform
         const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)tiles;
         const unsigned flags_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(sync);
@@ -340,11 +352,33 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             }
         };
 
-        unsigned h = 0, issued = 0, n_entries = 0;
+        // ---- the workgroup's DECIDED half-tile: the first local half-tile from which no pair of the rest of the split can reach ANY row's
+        // threshold -- the criterion that ends generation 4's early-terminating sweeps (stop_predict4_kernel, the votes of sweep4_kernel),
+        //     fmaf(nu, tailB[T], tailA[T]) * 1.000002f < tau        (T: the 64-item tile of the whole visiting order, conservative for a split)
+        // taken once per workgroup on (nw: the largest padded norm of its rows, tw: its lowest LOWERED threshold -- below the exact one,
+        // +1e30 for the rows of the padding, -1e30 while a list is shorter than K: never).  The suffix maxima fall along the order: a binary
+        // search.  Every operand is workgroup-uniform, so the four waves agree; thresholds only rise, so a value stays valid and a later
+        // one is at most as large.
+        auto decided = [&](float tw, float nw, unsigned h_now) __attribute__((always_inline)) -> unsigned {
+#ifdef PDA_V5_NO_FREE
+            return hend;                                                 // A/B build: every half-tile is tested (tools/build_variant.sh nofree -DPDA_V5_NO_FREE)
+#else
+            if (g.tailA == nullptr || !(tw > -1.0e30f)) return hend;
+            int lo = (int)(h_now >> 1), hi = n_it;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                const size_t T = (size_t)t0 + (size_t)mid * (size_t)g.n_splits;
+                if (__builtin_fmaf(nw, g.tailB[T], g.tailA[T]) * 1.000002f < tw) hi = mid; else lo = mid + 1;
+            }
+            return 2u * (unsigned)lo;
+#endif
+        };
+        float* xch = reinterpret_cast<float*>(sync + 72);                // [8] the waves' lowest thresholds and largest norms
+        unsigned h = 0, issued = 0, n_entries = 0, n_free = 0;
+        unsigned hlim = hend;            // the end handed to the tested body: what it issued for half-tiles >= hlim are clamped copies
         bool hend_ok = true;
         if ((ring_lds & (D == 256 ? 511u : 255u)) != 0u) { if (lane == 0) g.stats[0] = 6u; hend_ok = false; }      // (the slots must start at multiples of 256 / 512)
         for (unsigned guard = 0; hend_ok && guard < 2u * hend + 8u; ++guard) {
-            ++n_entries;
             float thr[NU];
 #pragma unroll
             for (int u = 0; u < NU; ++u) thr[u] = thr_of(u);
@@ -356,14 +390,39 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) tmin = fminf(tmin, __shfl_xor(tmin, o, 64));
             tmin = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tmin)));
-            Loop6<D, NU>::run(h, issued, reason, hend, ring_lds, flags_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits,
+            // the workgroup's decided half-tile, from the thresholds as they are now (all four waves are here: every flag raised so far has
+            // been acted on, nobody reads a slot)
+            if (lane == 0) { xch[wave] = tmin; xch[4 + wave] = numax; }
+            __syncthreads();
+            const float tw = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fminf(fminf(xch[0], xch[1]), fminf(xch[2], xch[3])))));
+            const float nw = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(xch[4], xch[5]), fmaxf(xch[6], xch[7])))));
+            const unsigned hf = decided(tw, nw, h);
+            if (h >= min(hlim, hf)) {
+                // ---- the rest of the split, test-free.  The tested body runs two half-tiles past the end it was given, on clamped copies:
+                // back to that end, and whatever it issued from there on is issued again (Loop6Free::run catches up at entry)
+                if (h > hlim) h = hlim;
+                if (issued > hlim) issued = hlim;
+                if (h < hend) {
+                    ++n_entries;
+                    n_free = hend - h;
+                    Loop6Free<D, NU>::run(h, issued, hend, ring_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits, (unsigned)img, (unsigned)(img >> 32), my_ufrag, lane16);
+                    V5LOG(14u, h, n_free);
+                }
+                break;
+            }
+            hlim = min(hlim, hf);
+            ++n_entries;
+            Loop6<D, NU>::run(h, issued, reason, hlim, ring_lds, flags_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits,
                               (unsigned)img, (unsigned)(img >> 32), (unsigned)meta, (unsigned)(meta >> 32), eu, tmin, my_ufrag, thr, lane16);
             V5LOG(reason, h, issued);
-            if (reason == 0u) break;
+            if (reason == 0u) {
+                if (hlim == hend) break;
+                continue;                                                // (the flags of every half-tile below hlim have been looked at: test-free from hlim on)
+            }
             if (reason != 1u) { if (lane == 0) g.stats[0] = 5u; break; }
 #ifdef PDA_V5_LOG
             // LDS integrity: the half-tiles about to be scored again and the one in progress, in their slots, against the image
-            for (unsigned tq = (h >= 2u ? h - 2u : 0u); tq <= h && tq < hend; ++tq) {
+            for (unsigned tq = (h >= 2u ? h - 2u : 0u); tq <= h && tq < hlim; ++tq) {
                 const unsigned Tq = t0 + (tq >> 1) * (unsigned)g.n_splits;
                 const unsigned char* gsrc = g.rows5 + ((size_t)(2u * Tq + (tq & 1u))) * HB;
                 const unsigned char* lsrc = tiles + (tq & (kNSlot5 - 1)) * SS;
@@ -379,8 +438,9 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             // every wave of the workgroup left at half-tile h because SOME wave's lanes flagged h - 2; the flags of h - 1 were still being
             // worked out: both are scored again here (a half-tile without a candidate of this wave costs its 8 NK MFMAs)
             [[maybe_unused]] const unsigned before = ring_n + n_cand;
-            if (h >= 2u && h - 2u < hend) extract(h - 2u);
-            if (h >= 1u && h - 1u < hend) extract(h - 1u);
+            // (below hlim: what the tested body scored behind its end are copies of half-tile hlim - 1)
+            if (h >= 2u && h - 2u < hlim) extract(h - 2u);
+            if (h >= 1u && h - 1u < hlim) extract(h - 1u);
             V5LOG(10u, h, ring_n + n_cand - before);
             // (thresholds rise only through the lists: rescoring a ring that holds a pass's worth keeps them fresh enough)
             if (ring_n >= (unsigned)CPP) rescore_ring();
@@ -388,6 +448,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
         if (ring_n > 0u) rescore_ring();
         if (lane == 0) atomicAdd(g.stats + 1, n_cand);
         if (lane == 0) atomicAdd(g.stats + 5, n_entries);                  // (workspace + 20: entries of the asm loop, summed over the waves)
+        if (lane == 0 && wave == 0 && n_free > 0u) atomicAdd(g.stats + 7, n_free);      // (workspace + 28: half-tiles run test-free, summed over the workgroups)
         if (lane == 0 && wave == 0) atomicAdd(reinterpret_cast<unsigned long long*>(g.stats + 2), (unsigned long long)(2 * n_it * (UT / kUserTile)));
     }
     // ================================== all waves: sort and emit ==================================

@@ -511,6 +511,8 @@ def sweep_from_seed(U, I_shard, users, K, head, pop_shard, hist, item_offset, se
     if stats is not None:
         stats["pairs_rescored"] = ws[4:8].view(torch.int32)
         stats["kernel_id"] = ws[16:20].view(torch.int32)
+        stats["huge_entries"] = ws[20:24].view(torch.int32)
+        stats["huge_free_halftiles"] = ws[28:32].view(torch.int32)
         stats["error"] = ws[0:4].view(torch.int32)
     return out
 
@@ -637,6 +639,7 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
             stats["tiles_dense"] = ((nloc + 31) // 32) * ((nu + 127) // 128)
             stats["kernel_id"] = ws[16:20].view(torch.int32)     # written by the sweep kernel itself: see kernel_identity()
             stats["huge_entries"] = ws[20:24].view(torch.int32)  # huge geometry: entries of its asm loop, summed over the waves (1 per wave + 1 per flagged half-tile)
+            stats["huge_free_halftiles"] = ws[28:32].view(torch.int32)  # huge geometry: 32-item half-tiles run without threshold tests (behind the decided half-tile), summed over the workgroups
             stats["error"] = ws[0:4].view(torch.int32)           # 0, or which bounded wait of the sweep ran out (1 .. 4: hand-over words; 5, 6: huge geometry)
         return out
     if impl == "v2" and prune:

@@ -18,9 +18,17 @@ Order of the 32 NK MFMAs of a half-tile: two GROUPS of eight user blocks; for g:
 feeds EIGHT MFMAs in a row, a chain is touched every 16 slots and idle n_half - 16 (NK - 1) slots before its restart (80 of 128 at d = 128):
 its maxima are spread over that window.
 
-    python tools/gen_v6_loop_asm.py > pda_amd/csrc/pda_v6_loop_asm.h
+TWO bodies per instance.  Loop6<D, UB>::run is the tested body described above.  Loop6Free<D, UB>::run is the same half-tile without
+anything that serves the test -- the maxima, compares and s_or, the clamp compare, the publish (ds_max_u32), the flag-word read and its
+branch, the meta DMA, the meta-pair read and the ct quad (zeros instead: the accumulators are dead) -- and with the same LDS-DMA pieces,
+fragment reads, one s_barrier per half-tile and the same 32 NK MFMAs on the same operands.  sweep5_kernel enters it once, behind the
+first half-tile from which the suffix bound of the visiting order says that no pair can reach any threshold of the workgroup
+(pda_v5_sweep.h: the decided half-tile); it runs to hend and has no other exit.
 
-V5_VARIANT=<list> builds timing-only variants as in gen_v5_loop_asm.py.  V5_LOADS=1 prints the fillers per MFMA slot.
+    python tools/gen_v6_loop_asm.py > pda_amd/csrc/pda_v6_loop_asm.h                 (the tested bodies: kept in the repository)
+    python tools/gen_v6_loop_asm.py --free > pda_amd/csrc/pda_v6_free_asm.h          (the test-free bodies: pda_amd/csrc/Makefile runs this)
+
+V5_VARIANT=<list> builds timing-only variants as in gen_v5_loop_asm.py.  V5_LOADS=1 prints the fillers per MFMA slot of both bodies.
 """
 import os
 import sys
@@ -33,9 +41,12 @@ PFD = int(os.environ.get("V5_PFD", "4"))     # half-tile h issues the pieces of 
 RD = int(os.environ.get("V6_RD", "10"))      # slots between a chain's last MFMA and the first VALU read of its accumulator
 
 
-def gen(D, UB):
+def gen(D, UB, free=False):
     """UB = 16: a wave owns 256 users (one 1 024-user workgroup per CU, 512 registers per wave).  UB = 8: 128 users (512-user
-    workgroups, TWO per CU, 256 registers per wave: while one wave's VALU tests run, the other wave of the SIMD has the matrix pipe)."""
+    workgroups, TWO per CU, 256 registers per wave: while one wave's VALU tests run, the other wave of the SIMD has the matrix pipe).
+    free: the test-free body (Loop6Free::run) for the half-tiles behind the workgroup's decided half-tile -- the same LDS-DMA pieces, fragment
+    reads, barrier and MFMAs on the same operands; no maxima, compares, clamp, publish, flag word, meta entry or ct (the accumulators
+    are dead: the C operand of a chain's first MFMA is a quad of zeros).  It ends AT hend, not two half-tiles behind it."""
     NK = D // 32
     if UB == 16:
         ACC0, FRAG0, THR0, M0T, MISC0 = 128, 96, 80, 64, 34
@@ -66,7 +77,8 @@ def gen(D, UB):
     # fragment addresses are formed by XOR with k << 6 (frag_read), which reaches bit 8 from k = 4 on
     SS = HB + (512 if D == 256 else 256)
     PW = HB // 1024 // 4                 # LDS-DMA pieces per wave and half-tile (2 at d = 128, 1 at d = 64)
-    OPS = 0 if "nodma" in VARIANT else PW + 1   # vector-memory operations per half-tile, ALL of them LDS-DMA (in order among themselves)
+    # vector-memory operations per half-tile, ALL of them LDS-DMA (in order among themselves); the test-free body loads no meta entry
+    OPS = 0 if "nodma" in VARIANT else PW + (0 if free else 1)
     G = UB // GU
     n_half = NK * IB * UB                # MFMA slots per half-tile (16 cycles each)
     usr = lambda u, k: "a[%d:%d]" % (4 * (u * NK + k), 4 * (u * NK + k) + 3)
@@ -104,8 +116,8 @@ def gen(D, UB):
         the end, and every half-tile issues the same number of operations)"""
         return ["s_sub_u32 s81, %[hend], 1", "s_min_u32 s81, %[issued], s81", "s_lshr_b32 s82, s81, 1", "s_mul_i32 s82, s82, %[nsplit]", "s_add_u32 s82, s82, %[t0]",
                 "s_lshl_b32 s82, s82, 1", "s_and_b32 s81, s81, 1", "s_add_u32 s82, s82, s81",          # the global half-tile index
-                "s_mul_hi_u32 s85, s82, %d" % HB, "s_mul_i32 s84, s82, %d" % HB, "s_add_u32 s84, s84, %[imglo]", "s_addc_u32 s85, s85, %[imghi]",
-                "s_lshl_b32 s82, s82, 4", "s_add_u32 s88, %[metalo], s82", "s_addc_u32 s89, %[metahi], 0"]
+                "s_mul_hi_u32 s85, s82, %d" % HB, "s_mul_i32 s84, s82, %d" % HB, "s_add_u32 s84, s84, %[imglo]", "s_addc_u32 s85, s85, %[imghi]"] + \
+               ([] if free else ["s_lshl_b32 s82, s82, 4", "s_add_u32 s88, %[metalo], s82", "s_addc_u32 s89, %[metahi], 0"])
 
     def dma_ops(x_sgpr):
         """the wave's PW pieces of the half-tile at s[84:85] into LDS slot x & 7, and its meta entry behind the slot's rows (every wave
@@ -115,7 +127,8 @@ def gen(D, UB):
             return Gs
         for j in range(PW):
             Gs.append([("s_add_u32 m0, s83, %[w1024]" if j == 0 else "s_add_u32 m0, m0, 4096"), "s_nop 0", "global_load_lds_dwordx4 %s, s[84:85]" % vgoff(j)])
-        Gs.append(["s_add_u32 m0, s83, %d" % HB, "s_mov_b64 exec, 1", "global_load_lds_dwordx4 %s, s[88:89]" % vzero, "s_mov_b64 exec, -1"])
+        if not free:
+            Gs.append(["s_add_u32 m0, s83, %d" % HB, "s_mov_b64 exec, 1", "global_load_lds_dwordx4 %s, s[88:89]" % vzero, "s_mov_b64 exec, -1"])
         return Gs
 
     flat = lambda Gs: [l for g in Gs for l in g]
@@ -125,7 +138,7 @@ def gen(D, UB):
     LOAD = [[0] * n_half, [0] * n_half]
 
     def ev(p, s, kind, tag, lines, cat=None):
-        if not lines or (cat is not None and ("no" + cat) in VARIANT):
+        if not lines or (cat is not None and (("no" + cat) in VARIANT or (free and cat in ("test", "flag")))):
             return
         p, s = (p + s // n_half) % 2, s % n_half
         EV[p].setdefault(s, []).append((kind, tag, lines))
@@ -201,7 +214,7 @@ def gen(D, UB):
         # the clamp of THIS half-tile (its pmax is in the parity's meta pair until slot 2 of the next half-tile reads h + 2's)
         ev(p, PUB + 2, "valu", None, ["v_cmp_lt_f32 vcc, %%[tmin], %s" % metap(p), "s_or_b64 s[92:93], s[92:93], vcc"], "test")
     # ---- the tests (tight windows: before what may move): every operation into the least loaded slot of its window (in order within a user block)
-    if "notest" not in VARIANT:
+    if "notest" not in VARIANT and not free:
         for p in range(2):
             for seq in sorted(TESTS[p], key=lambda q_: q_[0][0]):
                 prev = -1
@@ -222,9 +235,9 @@ def gen(D, UB):
         # the flag word: it holds h + 1 <=> half-tile h - 2 raised a flag in some wave -> everybody leaves here (h - 2 and h - 1 are scored
         # again outside); parity 1 only: the sweep is over once the flags of its last half-tile (hend - 1, looked at in hend + 1) are in
         chk = ["v_readfirstlane_b32 s98, %s" % vflag, "s_add_u32 s97, %[h], 1", "s_cmp_eq_u32 s98, s97"] + ([] if "noexit" in VARIANT else ["s_cbranch_scc1 91f"])
-        if "noflag" in VARIANT:
+        if "noflag" in VARIANT or free:
             chk = []
-        if p == 1:
+        if p == 1 and not free:
             chk += ["s_cmp_gt_u32 %[h], %[hend]", "s_cbranch_scc1 92f"]
         s0 = 10
         ev(p, s0, "check", ("flag", p), chk)
@@ -241,6 +254,9 @@ def gen(D, UB):
         step = ["s_add_u32 s80, %%[h], %d" % (PFD + 1), "s_cmp_lt_u32 s80, %[hend]", "s_cselect_b32 s86, %s, 0" % ("s90" if x_odd else "%d" % HB),
                 "s_cselect_b32 s87, %s, 0" % ("s91" if x_odd else "16")]
         adv = [["s_add_u32 s84, s84, s86", "s_addc_u32 s85, s85, 0"], ["s_add_u32 s88, s88, s87", "s_addc_u32 s89, s89, 0", "s_mov_b32 %[issued], s80"]]
+        if free:                             # (no meta entry: no pointer to it)
+            step = step[:3]
+            adv = [adv[0], ["s_mov_b32 %[issued], s80"]]
         lastdma = n_half - 3
         assert lastdma > s1 + 4 and s0 not in (PUB, PUB + 1)
         spread(p, s1, lastdma, [] if "nosalu" in VARIANT else [["s_add_u32 s81, %%[h], %d" % PFD]] + dma_ops("s81") + [step[:2], step[2:]] + adv)
@@ -285,6 +301,8 @@ def gen(D, UB):
             # end of the half-tile: my pieces of h + 2 have landed (everything but the operations of the PFD - 2 half-tiles behind it), and so
             # will everybody's behind the barrier.  The next half-tile becomes current.
             out += ["s_waitcnt vmcnt(%d)" % ((PFD - 2) * OPS)] + ([] if "nobarrier" in VARIANT else ["s_barrier"]) + ["s_add_u32 %[h], %[h], 1"]
+            if free:                                          # nothing to wait for behind the last half-tile: the sweep ends at hend
+                out += ["s_cmp_ge_u32 %[h], %[hend]", "s_cbranch_scc1 92f"]
         out.append("s_branch 20b")
         return out, lg
 
@@ -297,7 +315,7 @@ def gen(D, UB):
 
     # ---- prologue (every entry) ------------------------------------------------------------------------------------------------
     P = []
-    P += ["s_mov_b32 %[m0save], m0", "s_waitcnt vmcnt(0) lgkmcnt(0)", "v_mov_b32 %s, 0" % vzero, "v_mov_b32 %s, %%[flags]" % vfb]
+    P += ["s_mov_b32 %[m0save], m0", "s_waitcnt vmcnt(0) lgkmcnt(0)", "v_mov_b32 %s, 0" % vzero] + ([] if free else ["v_mov_b32 %s, %%[flags]" % vfb])
     # (the thresholds come in in v[THR0 : THR0 + UB): physical-register inputs)
     for j in range(PW):
         P.append("v_add_u32 %s, %d, %%[lane16]" % (vgoff(j), 4096 * j))
@@ -321,7 +339,8 @@ def gen(D, UB):
         P.append("global_load_dwordx4 a[%d:%d], %%[lane16], s[88:89] offset:%d" % (4 * i, 4 * i + 3, 1024 * (i % 4)))
     P.append("s_waitcnt vmcnt(0)")
     # the flag words are dealt with outside: clear them (every wave; the barrier below orders it)
-    P += ["ds_write_b32 %s, %s" % (vfb, vzero), "ds_write_b32 %s, %s offset:4" % (vfb, vzero)]
+    if not free:
+        P += ["ds_write_b32 %s, %s" % (vfb, vzero), "ds_write_b32 %s, %s offset:4" % (vfb, vzero)]
     # catch up with the loads: the pieces of half-tiles issued .. h + PFD - 1 (first entry: all of them; their slots are free)
     P += ["5:", "s_add_u32 s97, %%[h], %d" % PFD, "s_cmp_ge_u32 %[issued], s97", "s_cbranch_scc1 6f"]
     P += pointers_from_scratch() + flat(dma_ops("%[issued]")) + ["s_add_u32 %[issued], %[issued], 1", "s_branch 5b", "6:"]
@@ -329,11 +348,15 @@ def gen(D, UB):
     # everything issued has landed; behind the barrier everybody's has
     P += ["s_waitcnt vmcnt(0) lgkmcnt(0)", "s_barrier"]
     P += slot_addr("s97", "%[h]") + ["v_add_u32 %s, s97, %s" % (vrdb, voff0), "v_mov_b32 %s, s97" % vsb, "s_add_u32 s97, %[h], 1"] + slot_addr("s95", "s97")
-    P += ["s_mov_b64 s[92:93], 0", "s_mov_b32 s94, 0"]
-    # the entry half-tile's ct quad (both parities' registers: the branch below picks the parity), from its meta pair
-    P += ["ds_read_b64 %s, %s offset:%d" % (metapair(0), vsb, HB), "s_waitcnt lgkmcnt(0)", "v_fma_f32 %s, %%[eu], %s, %s" % (ctr(0, 0), metan(0), metap(0))]
-    P += ["v_mov_b32 %s, %s" % (ctr(0, r), ctr(0, 0)) for r in (1, 2, 3)] + ["v_mov_b32 %s, %s" % (ctr(1, r), ctr(0, 0)) for r in range(4)]
-    P += ["v_mov_b32 %s, %s" % (metap(1), metap(0))]
+    if free:
+        # the C operand of every chain's first MFMA: zeros (both parities' quads)
+        P += ["v_mov_b32 %s, 0" % ctr(p, r) for p in range(2) for r in range(4)]
+    else:
+        P += ["s_mov_b64 s[92:93], 0", "s_mov_b32 s94, 0"]
+        # the entry half-tile's ct quad (both parities' registers: the branch below picks the parity), from its meta pair
+        P += ["ds_read_b64 %s, %s offset:%d" % (metapair(0), vsb, HB), "s_waitcnt lgkmcnt(0)", "v_fma_f32 %s, %%[eu], %s, %s" % (ctr(0, 0), metan(0), metap(0))]
+        P += ["v_mov_b32 %s, %s" % (ctr(0, r), ctr(0, 0)) for r in (1, 2, 3)] + ["v_mov_b32 %s, %s" % (ctr(1, r), ctr(0, 0)) for r in range(4)]
+        P += ["v_mov_b32 %s, %s" % (metap(1), metap(0))]
     # every fragment the body reads AHEAD of the half-tile it belongs to
     for i, (k, ib) in enumerate(AHEAD):
         P += frag_read(k, ib, i, vrdb)
@@ -346,11 +369,15 @@ def gen(D, UB):
     # ---- exits ------------------------------------------------------------------------------------------------------------------
     drain = ["s_waitcnt vmcnt(0) lgkmcnt(0)", "s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15", "s_mov_b32 m0, %[m0save]"]
     E = []
-    E += ["91:", "s_mov_b32 %[reason], 1"] + drain + ["s_branch 99f"]          # half-tile h - 2 raised a flag in some wave (h - 1 has not been looked at)
-    E += ["92:", "s_mov_b32 %[reason], 0"] + drain + ["99:"]                   # the sweep is over
+    if free:
+        E += ["92:"] + drain                                                       # the sweep is over (h == hend)
+    else:
+        E += ["91:", "s_mov_b32 %[reason], 1"] + drain + ["s_branch 99f"]          # half-tile h - 2 raised a flag in some wave (h - 1 has not been looked at)
+        E += ["92:", "s_mov_b32 %[reason], 0"] + drain + ["99:"]                   # the sweep is over
     if os.environ.get("V5_LOADS"):
         for p in range(2):
-            print("D=%d UB=%d parity %d fillers per slot: %s" % (D, UB, p, " ".join("%d" % x for x in LOAD[p])), file=sys.stderr)
+            print("D=%d UB=%d %s parity %d fillers per slot (sum %d): %s" % (D, UB, "test-free" if free else "tested", p, sum(LOAD[p]), " ".join("%d" % x for x in LOAD[p])),
+                  file=sys.stderr)
     return P + b2 + E, THR0, LO_CLOBBER
 
 
@@ -386,14 +413,44 @@ def emit(D, UB):
     return "\n".join(out)
 
 
+def emit_free(D, UB):
+    """Loop6Free<D, UB>::run: the test-free body -- no thresholds, flag words, meta entries; no reason (it ends at hend and nowhere else)"""
+    Lf, THR0, LO = gen(D, UB, free=True)
+    out = []
+    out.append("template <>")
+    out.append("struct Loop6Free<%d, %d> {" % (D, UB))
+    out.append("    // The half-tiles of Loop6<%d, %d>::run WITHOUT the threshold tests, for the half-tiles no pair of which can enter a list of the workgroup" % (D, UB))
+    out.append("    // (pda_v5_sweep.h: the decided half-tile): the same LDS-DMA pieces, fragment reads, barrier per half-tile and MFMAs on the same operands.  Runs local")
+    out.append("    // half-tiles h .. hend - 1 (h < hend on entry, h == hend behind it); the pieces of half-tiles issued .. h + kPfd - 1 are issued at entry.")
+    out.append("    static __device__ __forceinline__ void run(unsigned& h, unsigned& issued, unsigned hend, unsigned ring, unsigned w1024, unsigned t0, unsigned nsplit,")
+    out.append("                                               unsigned imglo, unsigned imghi, const void* ufrag, unsigned lane16) {")
+    out.append("#if defined(__HIP_DEVICE_COMPILE__)")
+    out.append("        unsigned m0save;")
+    out.append("        asm volatile(")
+    for l in Lf:
+        out.append('            "%s\\n\\t"' % l)
+    out.append('            : [h] "+&s"(h), [issued] "+&s"(issued), [m0save] "=&s"(m0save)')
+    out.append('            : [hend] "s"(hend), [ring] "s"(ring), [w1024] "s"(w1024), [t0] "s"(t0), [nsplit] "s"(nsplit), [imglo] "s"(imglo), [imghi] "s"(imghi), '
+               '[ufrag] "s"(ufrag), [lane16] "v"(lane16)')
+    clob = ['"memory"', '"vcc"', '"scc"'] + ['"s%d"' % r for r in range(80, 100)] + \
+           ['"v%d"' % r for r in range(LO, 16 * UB) if not THR0 <= r < THR0 + UB] + ['"a%d"' % r for r in range(4 * UB * (D // 32))] + \
+           (['"v%d"' % r for r in range(128, 132)] if D == 256 else [])
+    out.append("            : " + ", ".join(clob) + ");")
+    out.append("#endif")
+    out.append("    }")
+    out.append("};")
+    return "\n".join(out)
+
+
 def main():
-    print("// GENERATED by tools/gen_v6_loop_asm.py -- do not edit.")
+    free = "--free" in sys.argv[1:]
+    print("// GENERATED by tools/gen_v6_loop_asm.py%s -- do not edit." % (" --free" if free else ""))
     print("#pragma once")
-    print("template <int D, int UB> struct Loop6;")
+    print("template <int D, int UB> struct %s;" % ("Loop6Free" if free else "Loop6"))
     for UB in (16, 8):
         for D in (64, 128):
-            print(emit(D, UB))
-    print(emit(256, 8))
+            print((emit_free if free else emit)(D, UB))
+    print((emit_free if free else emit)(256, 8))
 
 
 if __name__ == "__main__":

@@ -37,5 +37,9 @@ for geo in geos:
     ref = keys if ref is None else ref
     fl = 2.0 * Bu * W.n_items * W.d / (ms * 1e-3) / 1e12
     wgs = -(-Bu // 1024) * k.shape[0]
-    print("%s %d users %-6s splits %d: %.3f ms  %.0f TF (%.3f of 2.5 PF)  cand/user %.3f  loop entries per wave %.2f  error %d%s" %
-          (wl, Bu, geo, k.shape[0], ms, fl, fl / 2500, float(st["pairs_rescored"][0]) / Bu, float(st["huge_entries"][0]) / (4 * wgs), int(st["error"][0]), same), flush=True)
+    # share of the sweep's half-tiles (everything behind the 4 tiles of the warm-up, shared by the splits) that ran without threshold tests
+    UT = 512 if W.d == 256 else 1024
+    ht = 2.0 * -(-Bu // UT) * max(1, -(-W.n_items // 64) - 4)
+    free = float(st["huge_free_halftiles"][0]) if "huge_free_halftiles" in st else 0.0
+    print("%s %d users %-6s splits %d: %.3f ms  %.0f TF (%.3f of 2.5 PF)  cand/user %.3f  loop entries per wave %.2f  test-free half-tiles %.3f  error %d%s" %
+          (wl, Bu, geo, k.shape[0], ms, fl, fl / 2500, float(st["pairs_rescored"][0]) / Bu, float(st["huge_entries"][0]) / (4 * wgs), free / ht, int(st["error"][0]), same), flush=True)

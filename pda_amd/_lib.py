@@ -1,4 +1,4 @@
-"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h and pda_hip_pc.h).
+"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h and pda_hip_det.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -151,6 +151,15 @@ PC_SIGNATURES = {
     "pda_pc_score_topk_f32": (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp, _i, _d, _d, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_det.h (the bit-reproducible path, `--deterministic 1`)
+DET_SIGNATURES = {
+    "pda_bpr_grad_plan_scratch_bytes": (_sz, [_i, _i]),
+    "pda_bpr_grad_plan_f32": (_i, [_vp] * 7 + [_i, _i, _f, _f] + [_vp] * 6 + [_i, _vp, _vp]),
+    "pda_adam_step_plan_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 5 + [_i, _i, _f, _f, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "pda_metrics_ordered_workspace_bytes": (_sz, [_i, _i]),
+    "pda_metrics_ordered": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -168,7 +177,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
+            list(DET_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,11 +1,15 @@
 // Ranking metrics and the device-side triplet sampler (the steps right after / right before the hot path).
 #include "pda_common.h"
+#include "pda_hip_det.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
 // Metrics: one thread per user row.  MF/used_metric.py:4-80, reduction of MF/train_new_api.py:741-778.
 // ------------------------------------------------------------------------------------------------
+// ORDERED (pda_metrics_ordered): every wave leaves its partial sums in `sums` = a workspace [4 n_ks][waves] with plain stores, and
+// metrics_ordered_sum_kernel adds them in a fixed order -- no float atomics, the same bits run after run.
+template <bool ORDERED = false>
 __global__ void __launch_bounds__(256) metrics_kernel(const int32_t* topk, int n_rows, int k_cols,
                                                       const int64_t* tgt_indptr, const int32_t* tgt_indices,
                                                       const int32_t* Ks, int n_ks, double* sums) {
@@ -48,11 +52,36 @@ __global__ void __launch_bounds__(256) metrics_kernel(const int32_t* topk, int n
             hit += __shfl_xor(hit, o, 64);
         }
         if ((threadIdx.x & 63) == 0) {
-            atomicAdd(sums + 0 * n_ks + q, prec);
-            atomicAdd(sums + 1 * n_ks + q, rec);
-            atomicAdd(sums + 2 * n_ks + q, ndcg);
-            atomicAdd(sums + 3 * n_ks + q, hit);
+            if constexpr (ORDERED) {
+                const size_t n_waves = (size_t)gridDim.x * (blockDim.x / 64), w = (size_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+                sums[(size_t)(0 * n_ks + q) * n_waves + w] = prec;
+                sums[(size_t)(1 * n_ks + q) * n_waves + w] = rec;
+                sums[(size_t)(2 * n_ks + q) * n_waves + w] = ndcg;
+                sums[(size_t)(3 * n_ks + q) * n_waves + w] = hit;
+            } else {
+                atomicAdd(sums + 0 * n_ks + q, prec);
+                atomicAdd(sums + 1 * n_ks + q, rec);
+                atomicAdd(sums + 2 * n_ks + q, ndcg);
+                atomicAdd(sums + 3 * n_ks + q, hit);
+            }
         }
+    }
+}
+
+// One workgroup per sum: thread t adds the waves t, t + 256, ... in that order, thread 0 the 256 partial sums in thread order; then ONE plain
+// read-modify-write of sums[j] (the caller's stream orders the calls that share `sums`).
+__global__ void __launch_bounds__(256) metrics_ordered_sum_kernel(const double* __restrict__ partial, int n_waves, double* __restrict__ sums) {
+    __shared__ double s_acc[256];
+    const int j = (int)blockIdx.x, tid = threadIdx.x;
+    const double* p = partial + (size_t)j * n_waves;
+    double acc = 0;
+    for (int w = tid; w < n_waves; w += 256) acc += p[w];
+    s_acc[tid] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0;
+        for (int t = 0; t < 256; ++t) tot += s_acc[t];
+        sums[j] += tot;
     }
 }
 
@@ -187,8 +216,27 @@ extern "C" int pda_metrics(const int32_t* topk, int n_rows, int k_cols, const in
                            const int32_t* tgt_indices, const int32_t* Ks, int n_ks, double* sums, void* stream) {
     if (!topk || !tgt_indptr || !tgt_indices || !Ks || !sums || n_rows <= 0 || n_ks <= 0) return PDA_ERR_ARG;
     if (k_cols < 1 || k_cols > 64) return PDA_ERR_ARG;
-    hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(metrics_kernel<false>, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), topk, n_rows, k_cols, tgt_indptr, tgt_indices, Ks, n_ks, sums);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
+extern "C" size_t pda_metrics_ordered_workspace_bytes(int n_rows, int n_ks) {
+    return (n_rows > 0 && n_ks > 0) ? (size_t)4 * n_ks * (size_t)((n_rows + 255) / 256) * 4 * sizeof(double) : 0;
+}
+
+extern "C" int pda_metrics_ordered(const int32_t* topk, int n_rows, int k_cols, const int64_t* tgt_indptr, const int32_t* tgt_indices,
+                                   const int32_t* Ks, int n_ks, double* sums, void* workspace, void* stream) {
+    if (!topk || !tgt_indptr || !tgt_indices || !Ks || !sums || !workspace || n_rows <= 0 || n_ks <= 0) return PDA_ERR_ARG;
+    if (k_cols < 1 || k_cols > 64) return PDA_ERR_ARG;
+    const int n_blocks = (n_rows + 255) / 256;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* partial = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(metrics_kernel<true>, dim3((unsigned)n_blocks), dim3(256), 0, s, topk, n_rows, k_cols, tgt_indptr, tgt_indices, Ks, n_ks,
+                       partial);
+    PDA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(metrics_ordered_sum_kernel, dim3((unsigned)(4 * n_ks)), dim3(256), 0, s, partial, 4 * n_blocks, sums);
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }

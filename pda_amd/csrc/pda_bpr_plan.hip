@@ -30,6 +30,7 @@
 // stores, the shared item rows keep the atomics of the fused step (hogwild on those rows only).
 #include <cstdlib>
 #include "pda_common.h"
+#include "pda_hip_det.h"
 #include "pda_plan_common.h"
 
 namespace {
@@ -237,6 +238,21 @@ struct PlanStepArgs {
     int strided;           // launch B: lane group g of workgroup w takes segment g W + w (W workgroups with work) instead of w G + g
 };
 
+// The planned GRADIENT of a batch (pda_bpr_grad_plan_f32, include/pda_hip_det.h): the same two launches with GRAD = true store the summed
+// gradients -- gU[user], gI[item row], the rows' step tags -- instead of moving the tables.  Same sums in the same order, no float atomics.
+// The launches are instantiated on the argument block: PlanStepArgs = the step (every pre-existing instance, its code untouched), GradStepArgs = the gradient.
+struct GradStepArgs : PlanStepArgs {
+    float* gU;
+    float* gI;
+    int32_t* tagU;         // NULL (both): the caller does not sweep by tag
+    int32_t* tagI;
+    int tag;
+};
+template <typename Args>
+constexpr bool kGrad = false;
+template <>
+constexpr bool kGrad<GradStepArgs> = true;
+
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 __device__ __forceinline__ void atomic_add4(float* p, f32x4 v) {
     unsafeAtomicAdd(p + 0, v[0]);
@@ -256,8 +272,9 @@ __device__ __forceinline__ void store_bf16x4(uint16_t* p, f32x4 v) {
 }
 
 // launch A: one triplet per D/4 lanes
-template <int D, bool BF>
-__global__ void __launch_bounds__(512) plan_triplets_kernel(PlanStepArgs a) {
+template <int D, bool BF, typename Args = PlanStepArgs>
+__global__ void __launch_bounds__(512) plan_triplets_kernel(Args a) {
+    constexpr bool GRAD = kGrad<Args>;
     constexpr int L = D / 4, TPB = 512 / L;
     __shared__ float red[2][8];
     __shared__ int s_pos[TPB];
@@ -315,10 +332,16 @@ __global__ void __launch_bounds__(512) plan_triplets_kernel(PlanStepArgs a) {
             dpe[k] = gp * ue[k] + c * pe[k];
             dne[k] = -gn * ue[k] + c * ne[k];
         }
-        // the user row: distinct inside the batch, one plain store
-        const f32x4 un = um + due * nlr;
-        *reinterpret_cast<f32x4*>(a.U + (size_t)u * D + 4 * e) = un;
-        if constexpr (BF) store_bf16x4(a.Ush + (size_t)u * D + 4 * e, un);
+        if constexpr (GRAD) {
+            // the user row's gradient: users are distinct inside the batch, one plain store; no table row is written
+            *reinterpret_cast<f32x4*>(a.gU + (size_t)u * D + 4 * e) = due;
+            if (a.tagU && e == 0) a.tagU[u] = a.tag;
+        } else {
+            // the user row: distinct inside the batch, one plain store
+            const f32x4 un = um + due * nlr;
+            *reinterpret_cast<f32x4*>(a.U + (size_t)u * D + 4 * e) = un;
+            if constexpr (BF) store_bf16x4(a.Ush + (size_t)u * D + 4 * e, un);
+        }
         if (a.exact) {
             *reinterpret_cast<f32x4*>(a.scratch + (size_t)t * D + 4 * e) = ue;
             if (e == 0) *reinterpret_cast<float2*>(a.scratch + (size_t)a.B * D + 2 * (size_t)t) = make_float2(gp, gn);
@@ -396,8 +419,9 @@ __global__ void __launch_bounds__(512) plan_triplets_kernel(PlanStepArgs a) {
 
 // launch B, extra workgroups (large batches): workgroup j sums piece j % kXlPieces of very long segment j / kXlPieces; the last of a
 // segment's kXlPieces workgroups to arrive adds the partial sums in piece order and stores the row.
-template <int D, bool BF>
-__device__ __forceinline__ void plan_items_xl(const PlanStepArgs& a, int j, float* s_part) {
+template <int D, bool BF, typename Args>
+__device__ __forceinline__ void plan_items_xl(const Args& a, int j, float* s_part) {
+    constexpr bool GRAD = kGrad<Args>;
     constexpr int L = D / 4, G = 256 / L, LONGU = PDA_PLAN_LONGU, STEP = G * LONGU;
     __shared__ int s_last;
     const int tid = threadIdx.x, g = tid / L, e = tid % L;
@@ -454,17 +478,23 @@ __device__ __forceinline__ void plan_items_xl(const PlanStepArgs& a, int j, floa
         f32x4 old = row;
         if constexpr (BF) old = *reinterpret_cast<const f32x4*>(a.I + (size_t)x * D + 4 * e);
         const float cc = a.reg_c * (float)len;
-        const f32x4 nw = old - (sum + row * cc) * a.lr;
-        *reinterpret_cast<f32x4*>(a.I + (size_t)x * D + 4 * e) = nw;
-        if constexpr (BF) store_bf16x4(a.Ish + (size_t)x * D + 4 * e, nw);
+        if constexpr (GRAD) {
+            *reinterpret_cast<f32x4*>(a.gI + (size_t)x * D + 4 * e) = sum + row * cc;
+            if (a.tagI && e == 0) a.tagI[x] = a.tag;
+        } else {
+            const f32x4 nw = old - (sum + row * cc) * a.lr;
+            *reinterpret_cast<f32x4*>(a.I + (size_t)x * D + 4 * e) = nw;
+            if constexpr (BF) store_bf16x4(a.Ish + (size_t)x * D + 4 * e, nw);
+        }
     }
 }
 
 // launch B: one segment (one distinct item row) per D/4 lanes.  The launch is a chain of dependent loads -- segment -> entries ->
 // coefficients and old user rows -> the row's store --, so every level is issued for ALL of a lane group's entries at once
 // (branch-free, clamped indices): three round trips for a segment of up to 8 entries, one more per 4 further entries and group.
-template <int D, bool BF>
-__global__ void __launch_bounds__(256) plan_items_kernel(PlanStepArgs a, int n_parts, int n_normal) {
+template <int D, bool BF, typename Args = PlanStepArgs>
+__global__ void __launch_bounds__(256) plan_items_kernel(Args a, int n_parts, int n_normal) {
+    constexpr bool GRAD = kGrad<Args>;
     constexpr int L = D / 4, G = 256 / L, SHORT = 8, LONGU = PDA_PLAN_LONGU;
     __shared__ __attribute__((aligned(16))) float s_part[G * D];
     __shared__ int s_long[G];
@@ -504,9 +534,15 @@ __global__ void __launch_bounds__(256) plan_items_kernel(PlanStepArgs a, int n_p
             rg += __shfl_xor(rg, o, 64);
         }
         if (tid == 0) {           // (one writer per launch, launches of a stream in order: plain adds would do; atomics keep other streams safe)
-            unsafeAtomicAdd(a.loss_acc + 0, mf + rg);
-            unsafeAtomicAdd(a.loss_acc + 1, mf);
-            unsafeAtomicAdd(a.loss_acc + 2, rg);
+            if constexpr (GRAD) {         // (the gradient path holds no float atomic at all: loss_acc belongs to the caller's stream)
+                a.loss_acc[0] += mf + rg;
+                a.loss_acc[1] += mf;
+                a.loss_acc[2] += rg;
+            } else {
+                unsafeAtomicAdd(a.loss_acc + 0, mf + rg);
+                unsafeAtomicAdd(a.loss_acc + 1, mf);
+                unsafeAtomicAdd(a.loss_acc + 2, rg);
+            }
         }
     }
     if (rejected != 0) return;                        // rejected batch (uniform over the grid)
@@ -603,9 +639,14 @@ __global__ void __launch_bounds__(256) plan_items_kernel(PlanStepArgs a, int n_p
     }
     if (have && !is_xl) {
         const float cc = a.reg_c * (float)(b1 - b0);
-        const f32x4 nw = old - (sum + row * cc) * a.lr;
-        *reinterpret_cast<f32x4*>(a.I + (size_t)x * D + 4 * e) = nw;
-        if constexpr (BF) store_bf16x4(a.Ish + (size_t)x * D + 4 * e, nw);
+        if constexpr (GRAD) {
+            *reinterpret_cast<f32x4*>(a.gI + (size_t)x * D + 4 * e) = sum + row * cc;
+            if (a.tagI && e == 0) a.tagI[x] = a.tag;
+        } else {
+            const f32x4 nw = old - (sum + row * cc) * a.lr;
+            *reinterpret_cast<f32x4*>(a.I + (size_t)x * D + 4 * e) = nw;
+            if constexpr (BF) store_bf16x4(a.Ish + (size_t)x * D + 4 * e, nw);
+        }
     }
 }
 
@@ -674,6 +715,44 @@ extern "C" int pda_bpr_step_plan_f32(float* U, float* I, const int32_t* users, c
                                      int exact, float* loss_acc, void* stream) {
     return run_plan_step(U, I, U, I, nullptr, nullptr, false, users, pos, neg, pos_pop, neg_pop, B, d, regs, reg_div, lr, plan, scratch, exact,
                          loss_acc, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- the planned gradient (include/pda_hip_det.h; pda_adam_step_plan_f32 on top of it sits next to the sweep, pda_bpr_step.hip) ----
+namespace {
+template <int D>
+int launch_grad_plan(const GradStepArgs& a, hipStream_t s) {
+    constexpr int TPB = 512 / (D / 4), G = 256 / (D / 4);
+    const int n_parts = (a.B + TPB - 1) / TPB;
+    hipLaunchKernelGGL((plan_triplets_kernel<D, false, GradStepArgs>), dim3((unsigned)n_parts), dim3(512), 0, s, a);
+    PDA_CHECK_LAUNCH();
+    const int n_normal = (2 * a.B + G - 1) / G, n_xl_wg = a.strided ? xl_max(a.B) * kXlPieces : 0;
+    hipLaunchKernelGGL((plan_items_kernel<D, false, GradStepArgs>), dim3((unsigned)(n_normal + n_xl_wg)), dim3(256), 0, s, a, n_parts, n_normal);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+}  // namespace
+
+extern "C" size_t pda_bpr_grad_plan_scratch_bytes(int B, int d) { return pda_bpr_step_plan_scratch_bytes(B, d); }
+
+extern "C" int pda_bpr_grad_plan_f32(const float* U, const float* I, const int32_t* users, const int32_t* pos, const int32_t* neg,
+                                     const float* pos_pop, const float* neg_pop, int B, int d, float regs, float reg_div, const void* plan,
+                                     float* scratch, float* gU, int32_t* tagU, float* gI, int32_t* tagI, int step_tag, float* loss_acc,
+                                     void* stream) {
+    if (!U || !I || !users || !pos || !neg || !plan || !scratch || !gU || !gI || B <= 0 || B > (1 << 24) || reg_div <= 0.f) return PDA_ERR_ARG;
+    if ((pos_pop == nullptr) != (neg_pop == nullptr) || (tagU == nullptr) != (tagI == nullptr)) return PDA_ERR_ARG;
+    if (d != 32 && d != 64 && d != 128 && d != 256) return PDA_ERR_UNSUPPORTED;
+    const PlanView pv = plan_view(const_cast<void*>(plan), B);
+    // (U / I are only read: the gradient launches never write through PlanStepArgs::U / I)
+    const GradStepArgs a{{const_cast<float*>(U), const_cast<float*>(I), U, I, nullptr, nullptr, users, pos, neg, pos_pop, neg_pop, pv.hdr, pv.seg_item,
+                          pv.seg_start, pv.entries, pv.flags, scratch, loss_acc, B, 1.0f / (float)B, regs / reg_div, 0.f, 1, B > kPlanMaxB ? 1 : 0},
+                         gU, gI, tagU, tagI, step_tag};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (d) {
+        case 32: return launch_grad_plan<32>(a, s);
+        case 64: return launch_grad_plan<64>(a, s);
+        case 128: return launch_grad_plan<128>(a, s);
+        default: return launch_grad_plan<256>(a, s);
+    }
 }
 
 extern "C" int pda_bpr_step_plan_bf16(uint16_t* U_bf16, uint16_t* I_bf16, float* U_master, float* I_master, const int32_t* users,

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdlib>
 #include "pda_common.h"
+#include "pda_hip_det.h"
 #include "pda_sample.h"
 
 namespace {
@@ -617,12 +618,19 @@ __global__ void __launch_bounds__(256) adam_dense_sweep3_kernel(float* __restric
 // working set: NT = false reads and writes x, m, v with plain accesses, so tables that fit the 256 MiB Infinity Cache (C1 / C2: 54 MB)
 // are swept out of it instead of out of HBM; NT = true is adam_dense_sweep3_kernel's streaming policy for the big tables.  Same
 // arithmetic as adam_dense_sweep2_kernel / 3, operation for operation: bit-identical tables.
-template <bool NT, int UN>
+// Guard = const int* (pda_adam_step_plan_f32: the sweep behind the planned gradient): a batch its plan rejects (*rejected != 0: a user occurs twice)
+// leaves tables and moments as they are -- decided on the device, uniformly over the grid, no host synchronisation.  The instances without the
+// extra argument are the kernels of pda_adam_step_f32 / pda_adam_dense_sweep4_f32, argument block and instructions unchanged.
+__device__ __forceinline__ bool sweep_rejected() { return false; }
+__device__ __forceinline__ bool sweep_rejected(const int* rejected) { return *rejected != 0; }
+template <bool NT, int UN, typename... Guard>
 __global__ void __launch_bounds__(256) adam_dense_sweep4_kernel(float* __restrict__ var_a, float* __restrict__ m_a, float* __restrict__ v_a,
                                                                 float* __restrict__ g_a, size_t n4_a, const int32_t* __restrict__ t_a,
                                                                 float* __restrict__ var_b, float* __restrict__ m_b, float* __restrict__ v_b,
                                                                 float* __restrict__ g_b, size_t n4_b, const int32_t* __restrict__ t_b,
-                                                                int sh, int tag, unsigned blocks_a, float lr_t, float b1, float b2, float eps) {
+                                                                int sh, int tag, unsigned blocks_a, float lr_t, float b1, float b2, float eps,
+                                                                Guard... rejected) {
+    if (sweep_rejected(rejected...)) return;
     const bool first = blockIdx.x < blocks_a;
     float* var = first ? var_a : var_b;
     float* m = first ? m_a : m_b;
@@ -1166,7 +1174,7 @@ extern "C" int pda_adam_dense_sweep3_f32(float* var_a, float* m_a, float* v_a, f
 
 static int launch_sweep4(float* var_a, float* m_a, float* v_a, float* g_a, size_t rows_a, const int32_t* tag_a, float* var_b, float* m_b, float* v_b,
                          float* g_b, size_t rows_b, const int32_t* tag_b, int d, int tag, float lr_t, float beta1, float beta2, float eps, int cache_policy,
-                         hipStream_t s) {
+                         hipStream_t s, const int* rejected = nullptr) {
     int sh = 0;
     while ((4 << sh) < d) ++sh;
     const size_t n4a = rows_a * (size_t)(d / 4), n4b = rows_b * (size_t)(d / 4);
@@ -1181,10 +1189,13 @@ static int launch_sweep4(float* var_a, float* m_a, float* v_a, float* g_a, size_
     ba = ba < 1 ? 1 : (ba > total - 1 ? total - 1 : ba);
     const size_t wa = (n4a + 255) / 256, wb = (n4b + 255) / 256;
     const unsigned blocks_a = (unsigned)(wa < ba ? wa : ba), blocks_b = (unsigned)(wb < total - ba ? wb : total - ba);
-#define PDA_SWEEP4(NTV, UNV)                                                                                                                          \
-    hipLaunchKernelGGL((adam_dense_sweep4_kernel<NTV, UNV>), dim3(blocks_a + blocks_b), dim3(256), 0, s, var_a, m_a, v_a, g_a, n4a, tag_a, var_b, m_b, v_b, \
-                       g_b, n4b, tag_b, sh, tag, blocks_a, lr_t, beta1, beta2, eps)
-    if (nt) PDA_SWEEP4(true, 2);
+#define PDA_SWEEP4(NTV, UNV, ...)                                                                                                                     \
+    hipLaunchKernelGGL((adam_dense_sweep4_kernel<NTV, UNV __VA_OPT__(, const int*)>), dim3(blocks_a + blocks_b), dim3(256), 0, s, var_a, m_a, v_a, g_a, n4a, \
+                       tag_a, var_b, m_b, v_b, g_b, n4b, tag_b, sh, tag, blocks_a, lr_t, beta1, beta2, eps __VA_OPT__(, ) __VA_ARGS__)
+    if (rejected) {
+        if (nt) PDA_SWEEP4(true, 2, rejected);
+        else PDA_SWEEP4(false, 2, rejected);
+    } else if (nt) PDA_SWEEP4(true, 2);
     else PDA_SWEEP4(false, 2);
 #undef PDA_SWEEP4
     PDA_CHECK_LAUNCH();
@@ -1228,6 +1239,23 @@ extern "C" int pda_adam_step_f32(float* U, float* mU, float* vU, float* gU, int3
     }
     if (rc != PDA_OK) return rc;
     return launch_sweep4(U, mU, vU, gU, n_users, tagU, I, mI, vI, gI, n_items, tagI, d, step_tag, lr_t, beta1, beta2, eps, cache_policy, s);
+}
+
+// The same step, bit-reproducible (include/pda_hip_det.h): the planned gradient of pda_bpr_plan.hip (two launches, sums in plan order, no float
+// atomics), then the sweep above, which is order-free.  Three launches.
+extern "C" int pda_adam_step_plan_f32(float* U, float* mU, float* vU, float* gU, int32_t* tagU, size_t n_users, float* I, float* mI, float* vI,
+                                      float* gI, int32_t* tagI, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* neg,
+                                      const float* pos_pop, const float* neg_pop, int B, int d, float regs, float reg_div, int step_tag, float lr_t,
+                                      float beta1, float beta2, float eps, int cache_policy, const void* plan, float* scratch, float* loss_acc,
+                                      void* stream) {
+    if (!U || !I || !mU || !vU || !tagU || !mI || !vI || !tagI || n_users == 0 || n_items == 0 || step_tag <= 0) return PDA_ERR_ARG;
+    if (cache_policy < PDA_ADAM_CACHE_AUTO || cache_policy > PDA_ADAM_CACHE_STREAM) return PDA_ERR_ARG;
+    const int rc = pda_bpr_grad_plan_f32(U, I, users, pos, neg, pos_pop, neg_pop, B, d, regs, reg_div, plan, scratch, gU, tagU, gI, tagI, step_tag,
+                                         loss_acc, stream);
+    if (rc != PDA_OK) return rc;
+    // (plan header, word 1: "a user occurs twice" -- the layout of pda_triplet_plan)
+    return launch_sweep4(U, mU, vU, gU, n_users, tagU, I, mI, vI, gI, n_items, tagI, d, step_tag, lr_t, beta1, beta2, eps, cache_policy,
+                         reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int*>(plan) + 1);
 }
 
 extern "C" int pda_adam_rows_f32(float* var, float* m, float* v, float* g, const int32_t* rows, int n_rows, int d,

@@ -687,7 +687,10 @@ class ItemShardedBPR:
 
     def __init__(self, U: torch.Tensor, I_shard: torch.Tensor, item_offset: int, *, regs: float, lr: float, global_batch: int,
                  rank: int = 0, world: int = 1, group=None, step_fn: Optional[Callable] = None, apply_fn: Optional[Callable] = None,
-                 optimizer: str = "sgd", sweep_fn: Optional[Callable] = None):
+                 optimizer: str = "sgd", sweep_fn: Optional[Callable] = None, deterministic: bool = False):
+        if deterministic:
+            raise NotImplementedError("--deterministic runs on one GPU: the item-parallel step sums its gradients with float atomics and "
+                                      "exchanges them in arrival order")
         if step_fn is None or apply_fn is None:
             from . import ops
             step_fn = step_fn or ops.bpr_step_shard

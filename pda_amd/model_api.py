@@ -22,6 +22,10 @@ Optimisers (`args.optimizer`):
 Table type (`args.table_dtype`, extension; BASELINE config 5): with "bf16" the forward pass and the evaluation read bf16
 copies of the tables (`score_tables()`), gradients stay fp32 and `weights[...]` are the fp32 masters that take the
 update; the touched rows (sgd / lazy_adam) or the whole tables (adam) are re-rounded after every step.
+
+Determinism (`args.deterministic`, extension; DESIGN.md "Deterministic training"): with 1 every step sums its gradients in the order
+of the batch's plan (ops.adam_step_plan / ops.bpr_grad_plan / ops.bpr_step_plan) instead of with float atomics, so a run is a function
+of its flags and data alone, bit for bit.  Combinations that cannot keep that promise are refused when the model is built.
 """
 from __future__ import annotations
 
@@ -48,12 +52,36 @@ def xavier_uniform_(t: torch.Tensor, gen: torch.Generator):
     return t.uniform_(-lim, lim, generator=gen)
 
 
+DET_EMBED_SIZES = (32, 64, 128, 256)      # the row widths of the planned kernels (pda_bpr_grad_plan_f32, pda_bpr_step_plan_f32)
+
+
+def check_deterministic(args, data_config):
+    """--deterministic 1: refuse, before anything touches the GPU, what has no bit-reproducible path."""
+    opt = getattr(args, "optimizer", "adam")
+    if getattr(args, "train", "normal") == "temp_pop":
+        raise NotImplementedError("--deterministic: --train temp_pop sums the gradients of its four tables with float atomics")
+    if opt == "sgd_fused":
+        raise NotImplementedError("--deterministic: --optimizer sgd_fused updates rows inside the launch that gathers them (hogwild by design)")
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--deterministic runs on one GPU")
+    if getattr(args, "table_dtype", "f32") == "bf16" and opt in ("adam", "lazy_adam"):
+        raise NotImplementedError("--deterministic: --table_dtype bf16 under an Adam optimiser has no planned gradient (fp32 tables, or --optimizer sgd)")
+    if int(args.embed_size) not in DET_EMBED_SIZES:
+        raise NotImplementedError("--deterministic: --embed_size must be one of %s (the planned kernels)" % (DET_EMBED_SIZES,))
+    if int(args.batch_size) > int(data_config["n_users"]):
+        raise NotImplementedError("--deterministic: --batch_size %d > %d users -- the sampler then draws users with replacement and every batch's "
+                                  "plan would be rejected" % (args.batch_size, data_config["n_users"]))
+
+
 class _MFBase:
     with_pop = False
     ADAM_SWEEP_MAX_BYTES = 64 << 20      # C1/C2 (12 .. 18 MB of tables) sweep; config 3 (614 MB) and up replay
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None,
                  neg_items_api=None, pos_pop_api=None, neg_pop_api=None, device=None, seed=2021):
+        self.deterministic = bool(int(getattr(args, "deterministic", 0) or 0))
+        if self.deterministic:
+            check_deterministic(args, data_config)
         self.n_users = data_config["n_users"]
         self.n_items = data_config["n_items"]
         self.decay = args.regs                       # MF/model_api.py:23
@@ -219,6 +247,8 @@ class _MFBase:
             self._loss_i = (self._loss_i + 1) & 15
             self._loss = self._loss_ring[self._loss_i]
             self._loss.zero_()
+        if self.deterministic and plan is None:
+            plan = ops.triplet_plan(users, pos, neg)[0]      # (a batch source without plans: the host sampler, injected batches)
         if self.optimizer == "sgd" and plan is not None:
             if self.tables16 is not None:
                 self._plan_scratch = ops.bpr_step_plan(self.tables16["user_embedding"], self.tables16["item_embedding"], users, pos, neg, pos_pop,
@@ -246,6 +276,8 @@ class _MFBase:
         lr_t = ops.adam_lr_t(self.lr, self._t)
         lazy = self.optimizer == "adam" and self.adam_exact_lazy
         d = U.shape[1]
+        if self.deterministic:
+            return self._train_step_planned(U, I, st, users, pos, neg, pos_pop, neg_pop, plan, lr_t, lazy)
         if self.optimizer == "adam" and not lazy and d in (32, 64, 128, 256):
             # the reference's step in two launches (round 6): gradients + row tags, then the tagged sweep (cache policy by working set)
             if "tagU" not in st:
@@ -263,6 +295,27 @@ class _MFBase:
         elif self.optimizer == "adam":
             self._dense_sweep(U, I, st, users, pos, neg, lr_t)
         else:
+            ops.adam_rows(U, st["mU"], st["vU"], st["gU"], torch.unique(users).int(), lr_t)
+            ops.adam_rows(I, st["mI"], st["vI"], st["gI"], torch.unique(torch.cat([pos, neg])).int(), lr_t)
+        return self._loss
+
+    def _train_step_planned(self, U, I, st, users, pos, neg, pos_pop, neg_pop, plan, lr_t, lazy):
+        """--deterministic 1, the Adam optimisers: the steps of train_step with the planned gradient in place of the atomic one."""
+        sc = getattr(self, "_plan_scratch", None)
+        if self.optimizer == "adam" and not lazy:
+            if "tagU" not in st:
+                st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
+            self._plan_scratch = ops.adam_step_plan(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos,
+                                                    neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size, step=self._t, lr_t=lr_t, plan=plan,
+                                                    scratch=sc, loss_acc=self._loss)
+            return self._loss
+        if lazy:
+            ops.adam_lazy(0, self._lazy_state(), U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
+        self._plan_scratch = ops.bpr_grad_plan(U, I, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size, plan=plan,
+                                               gU=st["gU"], gI=st["gI"], scratch=sc, loss_acc=self._loss)
+        if lazy:
+            ops.adam_lazy(1, self._lazy, U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
+        else:       # lazy_adam
             ops.adam_rows(U, st["mU"], st["vU"], st["gU"], torch.unique(users).int(), lr_t)
             ops.adam_rows(I, st["mI"], st["vI"], st["gI"], torch.unique(torch.cat([pos, neg])).int(), lr_t)
         return self._loss
@@ -361,6 +414,8 @@ class BPRMFTempPop(_MFBase):
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, temp_api=None,
                  raw_api=None, **kw):
+        if int(getattr(args, "deterministic", 0) or 0):
+            check_deterministic(args, data_config)
         if torch.device(kw.get("device") or "cuda").type != "cuda":
             raise NotImplementedError("temp_pop runs on the GPU kernels only (pda_amd has no CPU path)")
         self.temp_num = int(data_config["temp_num"])

@@ -1092,6 +1092,70 @@ def adam_dense_sweep4(var_a, m_a, v_a, g_a, tag_a, var_b, m_b, v_b, g_b, tag_b, 
     mark_modified(var_b)
 
 
+def _grad_plan_args(U, I, users, pos, neg, pos_pop, neg_pop, plan, scratch):
+    """The checks the two planned-gradient entry points share -> (users, pos, neg, pos_pop, neg_pop, plan, scratch, B, d)."""
+    lib = _lib.load()
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    pos_pop = _need(pos_pop, torch.float32, "pos_pop", optional=True)
+    neg_pop = _need(neg_pop, torch.float32, "neg_pop", optional=True)
+    plan = _need(plan, torch.uint8, "plan")
+    B, d = users.numel(), U.shape[1]
+    if pos.numel() != B or neg.numel() != B:
+        raise ValueError("users/pos/neg must have the same length")
+    if plan.numel() != lib.pda_triplet_plan_bytes(B):
+        raise ValueError("plan does not belong to a batch of %d triplets" % B)
+    ns = lib.pda_bpr_grad_plan_scratch_bytes(B, d) // 4
+    if scratch is None or scratch.numel() != ns or scratch.dtype != torch.float32:
+        scratch = torch.empty(ns, dtype=torch.float32, device=U.device)
+    return users, pos, neg, pos_pop, neg_pop, plan, scratch, B, d
+
+
+def bpr_grad_plan(U, I, users, pos, neg, pos_pop=None, neg_pop=None, *, regs: float, reg_div: float, plan: torch.Tensor, gU, gI, tagU=None, tagI=None,
+                  step: int = 0, scratch: Optional[torch.Tensor] = None, loss_acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_bpr_grad_plan_f32: the summed gradients of a batch with DISTINCT users into gU / gI, bit-reproducible -- two launches, sums in the
+    order of plan = triplet_plan(users, pos, neg)[j], no float atomics.  A drop-in for bpr_step(mode=UPD_DENSE_GRAD); with tagU / tagI the
+    touched rows get the tag `step` (adam_dense_sweep4).  A rejected batch (a user occurs twice): loss_acc := NaN, nothing else is written.
+    Returns the scratch buffer for reuse."""
+    lib = _lib.load()
+    for t in (U, I, gU, gI):
+        _need(t, torch.float32, "tables / gradient tables")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shape of the tables")
+    if (tagU is None) != (tagI is None):
+        raise ValueError("tagU and tagI come together")
+    if tagU is not None:
+        tagU, tagI = _need(tagU, torch.int32, "tagU"), _need(tagI, torch.int32, "tagI")
+        if tagU.numel() != U.shape[0] or tagI.numel() != I.shape[0]:
+            raise ValueError("tagU / tagI hold one int32 per table row")
+    users, pos, neg, pos_pop, neg_pop, plan, scratch, B, d = _grad_plan_args(U, I, users, pos, neg, pos_pop, neg_pop, plan, scratch)
+    loss_acc = _need(loss_acc, torch.float32, "loss_acc", optional=True)
+    check(lib.pda_bpr_grad_plan_f32(ptr(U), ptr(I), ptr(users), ptr(pos), ptr(neg), ptr(pos_pop), ptr(neg_pop), B, d, float(regs), float(reg_div),
+                                    ptr(plan), ptr(scratch), ptr(gU), ptr(tagU), ptr(gI), ptr(tagI), int(step), ptr(loss_acc), stream_ptr()),
+          "pda_bpr_grad_plan_f32")
+    return scratch
+
+
+def adam_step_plan(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, neg, pos_pop=None, neg_pop=None, *, regs: float, reg_div: float, step: int,
+                   lr_t: float, plan: torch.Tensor, scratch: Optional[torch.Tensor] = None, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS,
+                   cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_adam_step_plan_f32: adam_step, bit-reproducible -- bpr_grad_plan followed by the tagged sweep (three launches).  The batch's users
+    must be distinct (a batch whose plan says otherwise is rejected: loss_acc := NaN, nothing else moves).  Returns the scratch buffer."""
+    lib = _lib.load()
+    for t in (U, mU, vU, gU, I, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    tagU, tagI = _need(tagU, torch.int32, "tagU"), _need(tagI, torch.int32, "tagI")
+    if tagU.numel() != U.shape[0] or tagI.numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    users, pos, neg, pos_pop, neg_pop, plan, scratch, B, d = _grad_plan_args(U, I, users, pos, neg, pos_pop, neg_pop, plan, scratch)
+    loss_acc = _need(loss_acc, torch.float32, "loss_acc", optional=True)
+    check(lib.pda_adam_step_plan_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI), I.shape[0],
+                                     ptr(users), ptr(pos), ptr(neg), ptr(pos_pop), ptr(neg_pop), B, d, float(regs), float(reg_div), int(step),
+                                     float(lr_t), beta1, beta2, eps, int(cache_policy), ptr(plan), ptr(scratch), ptr(loss_acc), stream_ptr()),
+          "pda_adam_step_plan_f32")
+    mark_modified(U, I)
+    return scratch
+
+
 def adam_dense_sweep(var, m, v, g, lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS):
     lib = _lib.load()
     for t, n in ((var, "var"), (m, "m"), (v, "v"), (g, "g")):
@@ -1193,6 +1257,27 @@ def metrics_sums(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Tensor]
         sums = torch.zeros((4, Ks.numel()), dtype=torch.float64, device=topk.device)
     check(lib.pda_metrics(ptr(topk), topk.shape[0], topk.shape[1], ptr(tgt_indptr), ptr(tgt_indices), ptr(Ks),
                           Ks.numel(), ptr(sums), stream_ptr()), "pda_metrics")
+    return sums
+
+
+_METRICS_WS = {}
+
+
+def metrics_sums_ordered(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_metrics_ordered: metrics_sums with the waves' partial sums added in a fixed order (no float atomics): the same bits run after run."""
+    lib = _lib.load()
+    topk = _need(topk, torch.int32, "topk")
+    tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
+    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    Ks = _need(Ks, torch.int32, "Ks")
+    if sums is None:
+        sums = torch.zeros((4, Ks.numel()), dtype=torch.float64, device=topk.device)
+    nb = lib.pda_metrics_ordered_workspace_bytes(topk.shape[0], Ks.numel())
+    ws = _METRICS_WS.get(topk.device)
+    if ws is None or ws.numel() * 8 < nb:
+        ws = _METRICS_WS[topk.device] = torch.empty(max(1, nb // 8), dtype=torch.float64, device=topk.device)
+    check(lib.pda_metrics_ordered(ptr(topk), topk.shape[0], topk.shape[1], ptr(tgt_indptr), ptr(tgt_indices), ptr(Ks), Ks.numel(), ptr(sums),
+                                  ptr(ws), stream_ptr()), "pda_metrics_ordered")
     return sums
 
 

@@ -1,7 +1,7 @@
 """Command-line surface of the reference trainer (MF/parse.py:3-117), kept flag-for-flag so that the commands
 in the reference README (README.md:41,69,93) run unchanged against `python -m pda_amd.train_new_api`.
 
-Flags the reference marks "not used" are accepted and ignored (they still have to parse).  Three flags are
+Flags the reference marks "not used" are accepted and ignored (they still have to parse).  A few flags are
 additions of this implementation and default to the reference's behaviour; they are listed last.
 """
 from __future__ import annotations
@@ -71,6 +71,7 @@ _EXTENSION_FLAGS = [
     ("adam_sweep", str, "auto", "how --optimizer adam applies the reference's dense decay: sweep = one pass over both tables per step | replay = the same arithmetic without the sweep (idle rows replay their decay when next needed; bit-identical after the sync) | replay_fast = that catch-up to 1e-6 instead of bit for bit (~4x less arithmetic; explicit opt-in) | auto = sweep up to 64 MB of tables, the bit-identical replay above"),
     ("sampler", str, "device", "device = HIP counter-based sampler | host = the reference's Python generators"),
     ("table_dtype", str, "f32", "f32 | bf16 (BASELINE config 5): bf16 embedding tables for the forward pass and the evaluation, fp32 masters take the updates"),
+    ("deterministic", int, 0, "1: the run is a function of its flags and data alone, bit for bit -- gradients summed in the order of the batch's plan and metrics in wave order instead of with float atomics (adam, lazy_adam, sgd on one GPU, fp32 tables under Adam; not temp_pop)"),
     ("eval_block", int, 262144, "users per score+top-K launch (the reference always uses 2048, MF/train_new_api.py:703); large blocks balance the early-terminating sweep: 92 M users/s at 65536, 109 M at 262144 (C3)"),
 ]
 

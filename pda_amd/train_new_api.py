@@ -89,8 +89,10 @@ class DatasetApi_Model:
         self.generator_sampler = generator_sampler
         self._iter = None
         self.batch_plan = None        # pda_triplet_plan of the batch next_batch() returned last (--optimizer sgd, device sampler)
-        if getattr(args, "optimizer", "adam") == "sgd" and getattr(generator_sampler, "distinct_users", False) and hasattr(generator_sampler, "with_plan"):
-            generator_sampler.with_plan = True       # the exact SGD step without atomics wants the batch's plan (ops.bpr_step_plan)
+        wants_plan = getattr(args, "optimizer", "adam") == "sgd" or bool(int(getattr(args, "deterministic", 0) or 0))
+        if wants_plan and getattr(generator_sampler, "distinct_users", False) and hasattr(generator_sampler, "with_plan"):
+            # the exact SGD step without atomics wants the batch's plan (ops.bpr_step_plan), and so does every planned step of --deterministic 1
+            generator_sampler.with_plan = True
         self.sess = None
         self.testing_model_type, self.testing_popularity = "o", None
         if args.train in ("s_condition", "condition"):
@@ -349,7 +351,9 @@ class evaluation:
             idx, _ = model.recommend_device(ub, None, rec_type, pop, self._hist, eval_pos=i, eval_users=self.users_dev)
             tp = self._tp_host[i:i + ub.numel() + 1]
             tptr = torch.from_numpy(tp - tp[0]).to(self.device)
-            ops.metrics_sums(idx, tptr, self.tgt_indices[int(tp[0]):int(tp[-1])], ks, sums)
+            # --deterministic 1: the ordered reduction -- recall decides the early stop and the best checkpoint with `>=`
+            reduce = ops.metrics_sums_ordered if int(getattr(args, "deterministic", 0) or 0) else ops.metrics_sums
+            reduce(idx, tptr, self.tgt_indices[int(tp[0]):int(tp[-1])], ks, sums)
         s = (sums / float(self.tot_user)).cpu().numpy()
         return {"precision": s[0], "recall": s[1], "ndcg": s[2], "hit_ratio": s[3]}
 

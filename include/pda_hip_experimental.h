@@ -77,6 +77,16 @@ int pda_score_topk4_phase_bf16(const uint16_t* U, const uint16_t* I_shard, const
                                const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int K, int head,
                                int early_stop, int n_splits, int phase, int warm_tiles, const float* seed, uint64_t* out_keys,
                                void* workspace, void* stream);
+/* The user block as the huge geometry's sweep reads it -- bf16 MFMA operands of whole 1 024-user (d = 256: 512-user) workgroups and the
+ * rows' padded norms.  A phase-2 sweep builds the image itself; in a one-call dense sweep the warm-up kernel writes the same bytes into
+ * the workspace while it holds the rows.  Tests compare the two:
+ *   pda_score_topk4_phase_image_offsets   offs[0 .. 2] = byte offsets, in the workspace of pda_score_topk4_*, of the image, the norms and
+ *            the K-th values of the warm-up's rows; offs[3] = rows of the padded image (2 d bytes and one float each)
+ *   pda_score_topk4_phase_user_image      the image and the norms of a block as a call of its own (ufrag: offs[3] x 2 d bytes, unorm:
+ *            offs[3] floats; bf16 != 0: U is a bf16 table) */
+int pda_score_topk4_phase_image_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs);
+int pda_score_topk4_phase_user_image(const void* U, int bf16, const int32_t* users, int n_users_blk, int d, void* ufrag, float* unorm,
+                                     void* stream);
 
 /* ---- train step variants -------------------------------------------------------------------------------------------------------------- */
 /* ---- The exact mini-batch SGD step without atomics (round 3; pda_bpr_plan.hip): plan + two launches -------------------------

@@ -532,6 +532,83 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(MergeArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// R = 1: nothing to merge -- the list is sorted already (zeros behind its keys), the result is its keys unpacked.  A streaming
+// kernel: a thread owns four consecutive keys of the flat [n_users_blk * K] array (two 16-byte loads; 16-byte stores of the
+// four ids and of the four values, two of the keys), no LDS.  A row that ends in a 0 key holds fewer than K unmasked items:
+// the thread that owns its last key fills the ids behind the keys as topk_merge_kernel does (train items, lowest id first,
+// then -1); the owners of such a row's other empty slots leave the ids to it.
+// ------------------------------------------------------------------------------------------------
+constexpr int kUnpackKeys = 4;      // keys per thread
+
+__device__ __forceinline__ void unpack1_fill_row(const MergeArgs& a, size_t u) {
+    const int K = a.K;
+    const uint64_t* row = a.in_keys + u * K;
+    int nreal = 0;
+    for (int p = 0; p < K; ++p) nreal += row[p] != 0ull ? 1 : 0;
+    int32_t* orow = a.out_idx + u * K;
+    for (int p = 0; p < K; ++p)
+        if (row[p] == 0ull) orow[p] = -1;
+    const int64_t hr = a.hist_row_mode == PDA_HIST_BY_USER_ID ? (int64_t)a.users[u] : (int64_t)u;
+    int fill = nreal, prev = -1;
+    for (int64_t p = a.hist_indptr[hr]; p < a.hist_indptr[hr + 1] && fill < K; ++p) {
+        const int it = a.hist_indices[p];
+        if (it != prev) orow[fill++] = it;
+        prev = it;
+    }
+}
+
+__global__ void __launch_bounds__(256) topk_unpack1_kernel(MergeArgs a, size_t total) {
+    typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i0 = g * kUnpackKeys;
+    if (i0 >= total) return;
+    const bool fill_on = a.out_idx != nullptr && a.hist_indptr != nullptr;
+    if (i0 + kUnpackKeys <= total) {
+        const u64x2 k01 = *reinterpret_cast<const u64x2*>(a.in_keys + i0), k23 = *reinterpret_cast<const u64x2*>(a.in_keys + i0 + 2);
+        const uint64_t k[kUnpackKeys] = {k01[0], k01[1], k23[0], k23[1]};
+        if (a.out_keys) {
+            *reinterpret_cast<u64x2*>(a.out_keys + i0) = k01;
+            *reinterpret_cast<u64x2*>(a.out_keys + i0 + 2) = k23;
+        }
+        if (a.out_idx == nullptr) return;
+        i32x4 id;
+        f32x4 v;
+#pragma unroll
+        for (int q = 0; q < kUnpackKeys; ++q) {
+            id[q] = k[q] ? pda_key_item(k[q]) : -1;
+            v[q] = k[q] ? pda_key_val(k[q]) : -INFINITY;
+        }
+        if (a.out_val) *reinterpret_cast<f32x4*>(a.out_val + i0) = v;
+        const bool empty = k[0] == 0ull || k[1] == 0ull || k[2] == 0ull || k[3] == 0ull;
+        if (!(fill_on && empty)) {
+            *reinterpret_cast<i32x4*>(a.out_idx + i0) = id;
+            return;
+        }
+        // (rare) empty slots of a row that may be filled: the ids of the real keys here, the others by the owner of the row's last key
+        const size_t u0 = i0 / (size_t)a.K;
+        int p = (int)(i0 - u0 * (size_t)a.K);
+        size_t u = u0;
+#pragma unroll
+        for (int q = 0; q < kUnpackKeys; ++q) {
+            if (k[q] != 0ull) a.out_idx[i0 + q] = id[q];
+            else if (p == a.K - 1) unpack1_fill_row(a, u);
+            if (++p == a.K) { p = 0; ++u; }
+        }
+        return;
+    }
+    // the last, partial group of the array
+    for (size_t i = i0; i < total; ++i) {
+        const uint64_t k = a.in_keys[i];
+        if (a.out_keys) a.out_keys[i] = k;
+        if (a.out_idx == nullptr) continue;
+        if (a.out_val) a.out_val[i] = k ? pda_key_val(k) : -INFINITY;
+        if (k != 0ull || !fill_on) a.out_idx[i] = k ? pda_key_item(k) : -1;
+        else if ((i + 1) % (size_t)a.K == 0) unpack1_fill_row(a, i / (size_t)a.K);
+    }
+}
+
 }  // namespace
 
 int pda_topk::launch_score_bias(const ScoreArgs& a, int d, hipStream_t s) {
@@ -625,6 +702,17 @@ extern "C" int pda_topk_merge(const uint64_t* in_keys, int R, int n_users_blk, i
     if (!in_keys || R < 1 || n_users_blk <= 0 || K < 1 || K > PDA_MAX_K) return PDA_ERR_ARG;
     if (!out_keys && !out_idx) return PDA_ERR_ARG;
     if (hist_indptr && (!hist_indices || (hist_row_mode == PDA_HIST_BY_USER_ID && !users))) return PDA_ERR_ARG;
+#ifndef PDA_MERGE_R1_GENERAL        // (A/B build: R = 1 through the general kernel -- tools/build_variant.sh merge1 -DPDA_MERGE_R1_GENERAL)
+    // one list per user: an unpack (topk_unpack1_kernel); its 16-byte accesses want 16-byte aligned arrays -- anything else takes the general kernel
+    if (R == 1 && ((reinterpret_cast<uintptr_t>(in_keys) | reinterpret_cast<uintptr_t>(out_keys) | reinterpret_cast<uintptr_t>(out_idx) |
+                    reinterpret_cast<uintptr_t>(out_val)) & 15u) == 0) {
+        MergeArgs a{in_keys, out_keys, out_idx, out_val, users, hist_indptr, hist_indices, hist_row_mode, 1, n_users_blk, K};
+        const size_t total = (size_t)n_users_blk * K, threads = (total + kUnpackKeys - 1) / kUnpackKeys;
+        hipLaunchKernelGGL(topk_unpack1_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, total);
+        PDA_CHECK_LAUNCH();
+        return PDA_OK;
+    }
+#endif
     const size_t smem = 4 * (((size_t)R * K + PDA_MAX_K) * sizeof(uint64_t) + (((size_t)R * 4 + 7) & ~(size_t)7));
     if (smem > 160 * 1024) return PDA_ERR_UNSUPPORTED;
     static int attr_set = 0;

@@ -116,6 +116,15 @@ struct Args4 {
     // these are the maxima of the very popularities being ranked.  NULL: the sweep tests every half-tile.
     const float* tailA;
     const float* tailB;
+    // the dense call of the huge geometry (warm-up and sweep5_kernel in ONE call): passes over the same bytes that the result does not need
+    //   ufrag_out / unorm_out   warm4_kernel holds every user row in registers anyway: it writes the sweep's user image and padded norms
+    //                           (uprep5_kernel's bytes, pda_v4_shared.h) and launch_sweep5 launches no uprep5_kernel.  NULL: uprep5_kernel.
+    //   kth_ws                  [n_splits][n_users_blk] with warm_final: the K-th value of every row (-inf: fewer than K keys) INSTEAD of a
+    //                           hand-over row -- the warm-up's sorted rows go to out_keys only, the sweep copies a row into its list slots
+    //                           the first time it appends to it (handover is NULL then)
+    unsigned char* ufrag_out;
+    float* unorm_out;
+    float* kth_ws;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -516,6 +525,46 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) warm4_kernel(Arg
         if (row_ok) v = pda_load4<BF>(g.U, (size_t)uid * D + 4 * h + 8 * c);
         areg[c] = v;
     }
+    if constexpr (HEAD == PDA_HEAD_POP) {
+        // the huge geometry's user image and padded norms, bit for bit what uprep5_kernel (pda_v4_shared.h) makes of the same rows: fragment
+        // (16-user block rb >> 4, k-step c >> 2) holds chunk c of user rb at 16-byte lane (rb & 15) + 16 (c & 3); this lane has half h of every
+        // chunk of its row: 8 bytes.  split8's round-to-nearest-even; the norm in uprep5's summation order (its thread c sums
+        // x_k^2 + y_k^2 over k -- x on this lane, y on lane ^ 32, or the other way round: the sum commutes --, then the xor butterfly over c).
+        if (g.ufrag_out != nullptr && split == 0) {
+            constexpr int NK5 = D / 32;
+            unsigned char* fb = g.ufrag_out + ((size_t)(row_blk >> 4) * (NK5 * 64) + (size_t)(row_blk & 15)) * 16 + 8 * h;
+            float ssc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const f32x4 v = areg[c];
+                uint2 w;
+                w.x = bf16_rne(v[0]) | (bf16_rne(v[1]) << 16);
+                w.y = bf16_rne(v[2]) | (bf16_rne(v[3]) << 16);
+                *reinterpret_cast<uint2*>(fb + ((c >> 2) * 64 + 16 * (c & 3)) * 16) = w;
+                float ss = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float sq = v[k] * v[k];
+                    ss += sq + __shfl_xor(sq, 32, 64);
+                }
+                ssc[c] = ss;
+            }
+#pragma unroll
+            for (int o = NC / 2; o > 0; o >>= 1)
+#pragma unroll
+                for (int c = 0; c < o; ++c) ssc[c] += ssc[c + o];
+            if (h == 0) g.unorm_out[row_blk] = sqrtf(ssc[0]) * 1.0009765625f * 1.0001f;
+            // rows of the sweep's padding (whole 1 024- / 512-user workgroups) behind the last 128-user tile: zeros, norm 0
+            const int utiles_w = (g.n_users_blk + kUserTile - 1) / kUserTile;
+            if (utile == utiles_w - 1) {
+                constexpr int UT5 = D == 256 ? 512 : kUT5;
+                const size_t r0 = (size_t)utiles_w * kUserTile, r1 = ((size_t)g.n_users_blk + UT5 - 1) / UT5 * UT5;
+                const u32x4 z = {0u, 0u, 0u, 0u};
+                for (size_t q = r0 * (2 * D) + (size_t)tid * 16; q < r1 * (2 * D); q += (size_t)kThreads * 16) *reinterpret_cast<u32x4*>(g.ufrag_out + q) = z;
+                for (size_t r = r0 + tid; r < r1; r += kThreads) g.unorm_out[r] = 0.f;
+            }
+        }
+    }
     if (g.pred_ws != nullptr) {          // the row's padded norm, as the sweep's votes use it (stop_predict4_kernel)
         float ss = 0.f;
 #pragma unroll
@@ -597,7 +646,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) warm4_kernel(Arg
     // unsorted hand-over through out_keys: exactly K survivors (K slots per row) -- a bisection down to the K-th value itself,
     // ~20 rounds of ballots over the 256 scores of a row, 0.25 of the warm-up's 0.6 ms at 262 144 users.  Through the workspace
     // (g.handover: CAP slots per row) any threshold with K .. CAP survivors will do: a handful of rounds.
-    const int cap_t = (g.warm_sorted || g.handover != nullptr) ? CAP : K;
+    const int cap_t = (g.warm_sorted || g.handover != nullptr || g.warm_final) ? CAP : K;
     auto emit_row = [&](const int r, const uint32_t t, const int c_t) __attribute__((always_inline)) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
         const int lrow = wave * 32 + row;
@@ -718,6 +767,7 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) warm4_kernel(Arg
             for (int o = 32; o >= 1; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
             if (lane == 0 && rb < g.n_users_blk) g.seed_out[rb] = c >= K ? pda_unordf(mn) : -INFINITY;
         }
+        if (g.kth_ws != nullptr) continue;          // (warm_final without a hand-over copy: the wave's rows leave together below)
         if (g.handover != nullptr) {
             if (rb < g.n_users_blk && lane < CAP) g.handover[((size_t)split * g.n_users_blk + rb) * CAP + lane] = lane < c ? buf[lane] : 0ull;
             // (warm_final: the row is sorted and holds at most K keys -- it is the final answer unless the sweep appends to it)
@@ -725,6 +775,26 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) warm4_kernel(Arg
         } else if (rb < g.n_users_blk && lane < K) {
             const uint64_t k = lane < c ? buf[lane] : 0ull;
             g.out_keys[((size_t)split * g.n_users_blk + rb) * K + lane] = k;
+        }
+    }
+    if (g.kth_ws != nullptr) {
+        // warm_final: every row is sorted and holds at most K keys -- the final answer unless the sweep appends to it.  The wave's 32 rows are
+        // ONE run of out_keys (32 K keys): written as such out of the LDS lists, 512 bytes per store; and the K-th value of every row (-inf:
+        // fewer than K keys), all the sweep's prologue needs of a row
+        pda_wave_sync();
+        const int rb0 = utile * kUserTile + wave * 32, nv = max(0, min(32, g.n_users_blk - rb0));
+        if (lane < nv) {
+            const uint64_t kl = my_lists[(size_t)lane * CAP + (K - 1)];
+            g.kth_ws[(size_t)split * g.n_users_blk + rb0 + lane] = cntl[wave * 32 + lane] >= K ? pda_unordf((uint32_t)(kl >> 32)) : -INFINITY;
+        }
+        uint64_t* ob = g.out_keys + ((size_t)split * g.n_users_blk + rb0) * K;
+        const int q64 = 64 / K, r64 = 64 % K;
+        int rr = lane / K, p = lane % K;
+        for (int i = lane; i < nv * K; i += 64) {
+            ob[i] = p < cntl[wave * 32 + rr] ? my_lists[(size_t)rr * CAP + p] : 0ull;
+            rr += q64;
+            p += r64;
+            if (p >= K) { p -= K; ++rr; }
         }
     }
     if (g.pred_ws != nullptr && lane < 32) {
@@ -1983,7 +2053,7 @@ static bool lists_in_hbm4(int) { return true; }       // (every d may run with i
 // the workspace of the pda_score_topk4_* calls: [counters of pda_score_topk_workspace_bytes | list slots of every workgroup when the
 // lists live in HBM | Bloom filters, 128 B per user | warm-position train-item masks, 32 B per user and split | regrouping: 1024 bins, bin and sweep row of every user]
 struct Ws4 {
-    size_t lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, total;
+    size_t lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, kth, total;
 };
 static Ws4 ws4_layout(int n_users_blk, int d, int n_splits) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2009,6 +2079,8 @@ static Ws4 ws4_layout(int n_users_blk, int d, int n_splits) {
     }
     w.seed = w.total;                                   // the shared warm-up's seed: one float per user
     w.total = w.seed + al((size_t)n_users_blk * 4);
+    w.kth = w.total;                                    // the dense call of the huge geometry: the K-th value of every warm-up row (Args4::kth_ws)
+    w.total = w.kth + al((size_t)n_splits * (size_t)n_users_blk * 4);
     return w;
 }
 extern "C" size_t pda_score_topk4_workspace_bytes(int n_users_blk, int n_items_local, int d, int n_splits) {
@@ -2083,6 +2155,19 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     g.warm_final = (geometry >= 4 && phase == 3 && g.handover != nullptr && g.prep_hdr_pop && !early_stop) ? 1 : 0;
     g.lists_empty = from_empty ? 1 : 0;
     g.n_users_dev = n_users_dev;
+    // the dense call of the huge geometry (launch4_sweep's conditions for sweep5_kernel, behind a warm-up of this call):
+#ifndef PDA_V5_HANDOVER             // (A/B build: the warm-up's rows through the hand-over AND out_keys -- tools/build_variant.sh handover -DPDA_V5_HANDOVER)
+    if (g.warm_final && geometry == 4) {            // no hand-over copy: sorted rows to out_keys, K-th values to the workspace
+        g.handover = nullptr;
+        g.kth_ws = reinterpret_cast<float*>(wsb + W.kth);
+    }
+#endif
+#ifndef PDA_V5_UPREP                // (A/B build: uprep5_kernel in every call -- tools/build_variant.sh uprep -DPDA_V5_UPREP)
+    if (geometry == 4 && phase == 3 && g.prep_hdr_pop && !early_stop && n_users_dev == nullptr && (L.n_tiles + n_splits - 1) / n_splits > warm_tiles) {
+        g.ufrag_out = wsb + W.ufrag;                // warm4_kernel writes the sweep's user image: launch_sweep5 launches no uprep5_kernel
+        g.unorm_out = reinterpret_cast<float*>(wsb + W.unorm);
+    }
+#endif
     if (g.prep_hdr_pop) {                // the suffix bounds of the popularities being ranked: the huge geometry's decided half-tile
         g.tailA = reinterpret_cast<const float*>(pb + L.sufA);
         g.tailB = reinterpret_cast<const float*>(pb + L.sufB);
@@ -2394,4 +2479,35 @@ extern "C" int pda_score_topk4_bf16(const uint16_t* U, const uint16_t* I_shard, 
                                     uint64_t* out_keys, void* workspace, void* stream) {
     return run_score4(U, I_shard, true, prep, pop_shard, users, n_users_blk, item_offset, n_items_local, d, hist_indptr, hist_indices,
                       hist_row_mode, K, head, early_stop, n_splits, out_keys, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+// What a phase-2 sweep of the huge geometry makes of a user block by itself (uprep5_kernel), as a call of its own, and where the one-call path
+// keeps the same bytes in its workspace -- the dense call's warm-up writes them instead (Args4::ufrag_out), and tests compare the two.
+//   offs[0 .. 3] = byte offsets of (user image, padded norms, K-th values of the warm-up's rows), rows of the padded image
+extern "C" int pda_score_topk4_phase_image_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs) {
+    if (n_users_blk <= 0 || n_items_local <= 0 || (d != 64 && d != 128 && d != 256) || !offs) return PDA_ERR_ARG;
+    if (n_splits <= 0) n_splits = pda_score_topk4_auto_splits(n_users_blk, n_items_local, d);
+    const Ws4 W = ws4_layout(n_users_blk, d, n_splits);
+    const size_t ut = d == 256 ? 512 : kUT5;
+    offs[0] = W.ufrag;
+    offs[1] = W.unorm;
+    offs[2] = W.kth;
+    offs[3] = ((size_t)n_users_blk + ut - 1) / ut * ut;
+    return PDA_OK;
+}
+extern "C" int pda_score_topk4_phase_user_image(const void* U, int bf16, const int32_t* users, int n_users_blk, int d, void* ufrag, float* unorm,
+                                                void* stream) {
+    if (!U || !users || !ufrag || !unorm || n_users_blk <= 0) return PDA_ERR_ARG;
+    if (d != 64 && d != 128 && d != 256) return PDA_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t ut = d == 256 ? 512 : kUT5, n_pad = ((size_t)n_users_blk + ut - 1) / ut * ut;
+#define PDA_UIMG_(DD, BFV, UPWV)                                                                                                                \
+    hipLaunchKernelGGL((uprep5_kernel<DD, BFV, true, UPWV>), dim3((unsigned)((n_pad * (DD / 8) + 255) / 256)), dim3(256), 0, s, U, users, n_users_blk, \
+                       (int)n_pad, reinterpret_cast<unsigned char*>(ufrag), unorm)
+    if (d == 64) { if (bf16) PDA_UIMG_(64, true, 256); else PDA_UIMG_(64, false, 256); }
+    else if (d == 128) { if (bf16) PDA_UIMG_(128, true, 256); else PDA_UIMG_(128, false, 256); }
+    else { if (bf16) PDA_UIMG_(256, true, 128); else PDA_UIMG_(256, false, 128); }
+#undef PDA_UIMG_
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
 }

@@ -100,6 +100,25 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             taul[rr] = utile * UT + rr < g.n_users_blk ? -INFINITY : INFINITY;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    } else if (warm_final && g.kth_ws != nullptr) {
+        // sorted rows of at most K keys in out_keys (warm4_kernel) and their K-th values, read as one run of floats: a LANE per row -- the value
+        // says everything (-inf: fewer than K keys, or K keys down to -inf; count them).  A row reaches the list slots when it is appended to.
+        for (int rr = tid; rr < UT; rr += 256) {
+            const int rb = utile * UT + rr;
+            int c = 0;
+            float tau = INFINITY;
+            if (rb < g.n_users_blk) {
+                tau = g.kth_ws[(size_t)split * g.n_users_blk + rb];
+                c = K;
+                if (tau == -INFINITY) {
+                    const uint64_t* row = g.out_keys + ((size_t)split * g.n_users_blk + rb) * K;
+                    for (c = 0; c < K && row[c] != 0ull; ++c) {}
+                }
+            }
+            cntl[rr] = c;
+            taul[rr] = tau;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     } else if (warm_final) {
         // sorted lists of at most K keys (warm4_kernel): a LANE per row -- its K-th key says everything (0: fewer than K keys; count them)
         for (int rr = tid; rr < UT; rr += 256) {
@@ -177,6 +196,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
         const unsigned t0 = (unsigned)(split + wt * g.n_splits);
         const size_t img = (size_t)g.rows5, meta = (size_t)g.meta5;
         const bool hist_on = g.hist_indptr != nullptr;
+        const bool lazy_rows = warm_final && g.kth_ws != nullptr;
 
         // the lowered threshold of the lane's user of block u: strictly below the exact K-th value (ties must pass) and below the fp32
         // roundings between the bound and the rescored head; +-1e30 stand for +-inf
@@ -291,7 +311,22 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
                     if (lo < he && g.hist_indices[lo] == item) p = false;
                 }
                 const uint64_t key = pda_pack_key(tt, (uint32_t)item);
-                if (p) atomicOr(&touched[(row0 + row) >> 5], 1u << ((row0 + row) & 31));
+                bool first = false;                                 // this lane's append is the first to its row
+                if (p) first = (atomicOr(&touched[(row0 + row) >> 5], 1u << ((row0 + row) & 31)) & (1u << ((row0 + row) & 31))) == 0u;
+                if (lazy_rows) {
+                    // the warm-up's row still sits in out_keys only: into the row's list slots before the first append (rows belong to one wave;
+                    // of several lanes on one untouched row the atomic names one)
+                    uint64_t need = __ballot(first);
+                    if (need != 0ull) {
+                        while (need != 0ull) {
+                            const int lr = row0 + __builtin_amdgcn_readlane(row, __builtin_ctzll(need));
+                            need &= need - 1ull;
+                            const int c_r = cntl[lr];
+                            if (lane < c_r) lists[(size_t)lr * CAPL + lane] = g.out_keys[((size_t)split * g.n_users_blk + (size_t)(utile * UT + lr)) * K + lane];
+                        }
+                        list_sync<true>();
+                    }
+                }
                 append_keys<CAPL, true>(p, row0 + row, tt, key, lists, cntl, taul, row0, UPW, K, lane, s_uns);
             }
             n_cand += ring_n;
@@ -538,9 +573,11 @@ int launch_sweep5(const Args4& g, hipStream_t stream) {
         attr_set = 1;
     }
     const int utiles = (g.n_users_blk + UT - 1) / UT, n_pad = utiles * UT;
-    hipLaunchKernelGGL((uprep5_kernel<D, BF, S16, UPW>), dim3((unsigned)(((size_t)n_pad * (D / 8) + 255) / 256)), dim3(256), 0, stream, g.U, g.users, g.n_users_blk, n_pad,
-                       const_cast<unsigned char*>(g.ufrag), const_cast<float*>(g.unorm));
-    PDA_CHECK_LAUNCH();
+    if (g.ufrag_out == nullptr) {        // (else: the warm-up of this call has written the user image and the norms -- warm4_kernel)
+        hipLaunchKernelGGL((uprep5_kernel<D, BF, S16, UPW>), dim3((unsigned)(((size_t)n_pad * (D / 8) + 255) / 256)), dim3(256), 0, stream, g.U, g.users, g.n_users_blk, n_pad,
+                           const_cast<unsigned char*>(g.ufrag), const_cast<float*>(g.unorm));
+        PDA_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL((sweep5_kernel<D, BF, S16, UPW>), dim3((unsigned)(utiles * g.n_splits)), dim3(256), lds, stream, g);
     PDA_CHECK_LAUNCH();
     return PDA_OK;

@@ -641,6 +641,8 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
             stats["huge_entries"] = ws[20:24].view(torch.int32)  # huge geometry: entries of its asm loop, summed over the waves (1 per wave + 1 per flagged half-tile)
             stats["huge_free_halftiles"] = ws[28:32].view(torch.int32)  # huge geometry: 32-item half-tiles run without threshold tests (behind the decided half-tile), summed over the workgroups
             stats["error"] = ws[0:4].view(torch.int32)           # 0, or which bounded wait of the sweep ran out (1 .. 4: hand-over words; 5, 6: huge geometry)
+            stats["workspace"] = ws                               # (tests read the huge geometry's user image out of it: huge_image_offsets)
+            stats["n_splits"] = n_splits
         return out
     if impl == "v2" and prune:
         prep, order = item_prep_ordered(I_shard, pop_shard if head == HEAD_POP else None)
@@ -753,6 +755,31 @@ def kernel_identity(word) -> dict:
         return {"generation": 0}
     return {"generation": w >> 28, "geometry": GEOMETRY_NAMES.get((w >> 8) & 15, "?") if (w >> 28) == 4 else None,
             ("early_stop" if (w >> 28) == 4 else "visiting_order"): bool((w >> 12) & 1), "head": (w >> 13) & 1, "bf16": bool((w >> 14) & 1), "d": (w & 15) * 64}
+
+
+def huge_image_offsets(nu: int, nloc: int, d: int, n_splits: int):
+    """pda_score_topk4_phase_image_offsets -> (byte offsets of the user image, the padded norms and the warm-up rows' K-th values in the
+    workspace of a pda_score_topk4_* call, rows of the padded image)."""
+    offs = (C.c_size_t * 4)()
+    check(_lib.load().pda_score_topk4_phase_image_offsets(nu, nloc, d, n_splits, C.cast(offs, C.c_void_p)), "pda_score_topk4_phase_image_offsets")
+    return int(offs[0]), int(offs[1]), int(offs[2]), int(offs[3])
+
+
+def huge_user_image(U: torch.Tensor, users: torch.Tensor):
+    """pda_score_topk4_phase_user_image: the block as a phase-2 sweep of the huge geometry prepares it by itself
+    -> (image uint8 [n_pad * 2 d], padded norms float32 [n_pad])."""
+    lib = _lib.load()
+    bf = U.dtype == torch.bfloat16
+    U = _need(U, torch.bfloat16 if bf else torch.float32, "U")
+    users = _need(users, torch.int32, "users")
+    d, nu = U.shape[1], users.numel()
+    ut = 512 if d == 256 else 1024
+    n_pad = -(-nu // ut) * ut
+    ufrag = torch.empty(n_pad * 2 * d, dtype=torch.uint8, device=U.device)
+    unorm = torch.empty(n_pad, dtype=torch.float32, device=U.device)
+    check(lib.pda_score_topk4_phase_user_image(ptr(U), 1 if bf else 0, ptr(users), nu, d, ptr(ufrag), ptr(unorm), stream_ptr()),
+          "pda_score_topk4_phase_user_image")
+    return ufrag, unorm
 
 
 def topk_merge(keys: torch.Tensor, users=None, hist: Optional[HistoryCSR] = None, want="idx_val"):

@@ -457,6 +457,10 @@ int pda_metrics(const int32_t* topk, int n_rows, int k_cols, const int64_t* tgt_
  *   train CSR indexed by user id, indices sorted ascending; train_slots i32 parallel to indices or NULL
  *   negatives are drawn from [neg_lo, neg_hi) (the whole catalogue, or a rank's item shard)
  *   pop_matrix f32 [n_items, n_slots] or NULL.   Counter-based RNG: (seed, step, row) -> draws.
+ * Rejection cap: a row gives up after 4096 rejected negatives and returns the last one drawn, which is then a TRAIN
+ * item of that user inside [neg_lo, neg_hi) -- the case of a user who owns every item of the range, where the
+ * reference loops for ever.  With one free item among m the cap is reached with probability (1 - 1/m)^4096.
+ * The permutation has 16 rounds for n_pool <= 256 and 4 above (the batch stream of a pool > 256 is unchanged).
  * ------------------------------------------------------------------------------------------------ */
 int pda_sample_triplets(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B,
                         const int64_t* train_indptr, const int32_t* train_indices, const int32_t* train_slots,

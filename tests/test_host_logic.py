@@ -48,6 +48,27 @@ def test_written_dataset_round_trips_through_both_loaders(toy):
         assert sorted(zip(row.tolist(), sl[ip[u]:ip[u + 1]].tolist())) == pairs
 
 
+def test_train_csr_sorts_an_unsorted_file_and_moves_the_slots_with_the_items(tmp_path):
+    """The sampler's binary search needs ascending rows, and a positive's popularity is read at ITS slot: a train file whose
+    lines interleave the users, list the items out of order and repeat an item under two slots (user 3 has no line at all)."""
+    lines = [(1, 7, 2), (0, 9, 0), (1, 3, 1), (0, 2, 3), (1, 7, 0), (4, 5, 1), (0, 4, 2), (1, 0, 3), (4, 1, 0), (0, 2, 1)]
+    os.makedirs(tmp_path / "mess")
+    with open(tmp_path / "mess" / "train_with_time.txt", "w") as f:
+        for u, i, t in lines:
+            f.write("%d %d %d 5\n" % (u, i, t))
+    a = parse.parse_args(["--data_path", str(tmp_path) + "/", "--dataset", "mess", "--batch_size", "4", "--train", "s_condition"])
+    d = load_data.Data2(a)
+    assert d.train_user_list[1] == [7, 3, 7, 0] and d.train_user_list_time[1] == [2, 1, 0, 3]      # file order, like the reference
+    ip, ix, sl = (t.numpy() for t in d.train_csr("cpu"))
+    assert ip.dtype == np.int64 and ix.dtype == np.int32 and sl.dtype == np.int32
+    assert ip.tolist() == [0, 4, 8, 8, 8, 10]                                                    # users 2 and 3: empty rows
+    assert ix.tolist() == [2, 2, 4, 9, 0, 3, 7, 7, 1, 5]
+    assert sl.tolist() == [3, 1, 2, 0, 3, 1, 2, 0, 0, 1]                                         # equal items keep their file order
+    for u in range(5):
+        assert np.all(np.diff(ix[ip[u]:ip[u + 1]]) >= 0)
+    assert sorted(zip(ix.tolist(), sl.tolist(), np.repeat(np.arange(5), np.diff(ip)).tolist())) == sorted((i, t, u) for u, i, t in lines)
+
+
 def test_host_generator_follows_the_sampler_protocol(toy):
     a = parse.parse_args(["--data_path", toy, "--dataset", "toy", "--batch_size", "32", "--train", "s_condition"])
     d = load_data.Data2(a)

@@ -1,4 +1,5 @@
-"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h and pda_hip_det.h).
+"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h and
+pda_hip_deep.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -162,6 +163,16 @@ DET_SIGNATURES = {
     "pda_metrics_ordered": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_deep.h (deep lists: exact top-K up to 1 024, `--topk_max`)
+DEEP_MAX_K = 1024
+DEEP_SIGNATURES = {
+    "pda_deep_topk_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pda_deep_topk_f32": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pda_deep_topk_bf16": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pda_metrics_deep_workspace_bytes": (_sz, [_i, _i]),
+    "pda_metrics_deep": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -180,7 +191,7 @@ def load():
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
-            list(DET_SIGNATURES.items()):
+            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -159,6 +159,9 @@ def main(argv=None):
     from . import train_new_api as t
     t.configure(argv)
     args, data = t.args, t.data
+    if t.check_topk_max(args) > ops.TOPK_K_V4:
+        raise NotImplementedError("--topk_max %d: BPR-PC ranks at most %d items per user (its sweep keeps K + 8 candidates on chip and there is "
+                                  "no PC head on the deep path)" % (args.topk_max, ops.PC_MAX_K))
     random.seed(2020)
     np.random.seed(2020)
     torch.manual_seed(2021)

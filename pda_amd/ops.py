@@ -1736,3 +1736,130 @@ def recommend_topk_pc(U, I, users, pop, scale, alpha, beta, K=50, hist: Optional
         stats["kernel_id"] = wsa[16:20].view(torch.int32)
         stats["pc_fallback_rows"] = int(wsa[20:24].view(torch.int32).item())
     return idx, val
+
+
+# ---- deep lists (include/pda_hip_deep.h) ------------------------------------------------------------------------------------------------
+DEEP_MAX_K = _lib.DEEP_MAX_K
+DEEP_GENERATION = 8                      # generation tag of the deep path in its identity word
+DEEP_WORKSPACE_BUDGET = 1 << 30          # bytes of workspace a recommend_topk_deep call may hold at a time: the users are chunked to stay within it
+_DEEP_WS = {}                            # device -> the workspace of the last call (kept: a 1 GiB allocation per evaluation block is not free)
+
+
+def deep_workspace_bytes(n_users_blk: int, n_items_local: int, d: int, K: int) -> int:
+    return int(_lib.load().pda_deep_topk_workspace_bytes(n_users_blk, n_items_local, d, K))
+
+
+def deep_kernel_identity(word) -> dict:
+    """Decodes the identity word of a deep call (stats["kernel_id"] of recommend_topk_deep): generation 8 = the deep path."""
+    w = int(word) & 0xFFFFFFFF
+    return {"generation": w >> 28, "head": (w >> 13) & 1, "bf16": bool((w >> 14) & 1), "d": (w & 15) * 64 or 32}
+
+
+def deep_chunk_users(n_users: int, n_items_local: int, d: int, K: int, budget: Optional[int] = None) -> int:
+    """Users per pda_deep_topk_* call so that its workspace stays within `budget` bytes (whole 128-user tiles; at least one tile)."""
+    budget = DEEP_WORKSPACE_BUDGET if budget is None else int(budget)
+    if deep_workspace_bytes(n_users, n_items_local, d, K) <= budget:
+        return n_users
+    lo, hi = 1, -(-n_users // 128)        # tiles: the size is non-decreasing in the users
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if deep_workspace_bytes(mid * 128, n_items_local, d, K) <= budget:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo * 128
+
+
+def recommend_topk_deep(U, I_shard, users, K, head=HEAD_RAW, pop_shard=None, hist: Optional[HistoryCSR] = None, item_offset=0,
+                        stats: Optional[dict] = None, want="idx_val", workspace_budget: Optional[int] = None):
+    """pda_deep_topk_f32 / _bf16: exact score + mask + top-K for 1 <= K <= 1 024 without the rating matrix -> (idx int32 [Bu, K], val float32
+    [Bu, K]), or packed keys int64 [Bu, K] with want="keys".  The users are chunked so that the workspace stays within DEEP_WORKSPACE_BUDGET
+    (or workspace_budget) bytes; a history by block row is re-based per chunk.  stats["kernel_id"]: deep_kernel_identity()."""
+    lib = _lib.load()
+    bf = U is not None and U.dtype == torch.bfloat16
+    tdt = torch.bfloat16 if bf else torch.float32
+    U, I_shard = _need(U, tdt, "U"), _need(I_shard, tdt, "I_shard")
+    users = _need(users, torch.int32, "users")
+    pop_shard = _need(pop_shard, torch.float32, "pop_shard", optional=True)
+    nu, nloc, d = users.numel(), I_shard.shape[0], I_shard.shape[1]
+    K = int(K)
+    if U.shape[1] != d:
+        raise ValueError("U and I_shard must share the embed dim")
+    if d not in (32, 64, 128, 256):
+        raise ValueError(f"deep lists support embed sizes 32, 64, 128 and 256, not {d}")
+    if not 1 <= K <= DEEP_MAX_K:
+        raise ValueError(f"deep lists need 1 <= K <= {DEEP_MAX_K}, got {K}")
+    if K > nloc:
+        raise ValueError(f"K = {K} exceeds the item shard ({nloc} items)")
+    if head not in (HEAD_RAW, HEAD_POP):
+        raise ValueError("deep lists rank by the raw head or the popularity head")
+    if head == HEAD_POP:
+        if pop_shard is None or pop_shard.numel() != nloc:
+            raise ValueError("pop_shard must hold one value per local item row")
+        _check_pop(pop_shard)
+    if nu == 0:
+        raise ValueError("empty user block")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    dev = U.device
+    out_keys = out_idx = out_val = None
+    if want == "keys":
+        out_keys = torch.empty((nu, K), dtype=torch.int64, device=dev)
+    else:
+        out_idx = torch.empty((nu, K), dtype=torch.int32, device=dev)
+        out_val = torch.empty((nu, K), dtype=torch.float32, device=dev)
+    chunk = deep_chunk_users(nu, nloc, d, K, workspace_budget)
+    nbytes = deep_workspace_bytes(min(chunk, nu), nloc, d, K)
+    ws = _DEEP_WS.get(dev)
+    if ws is None or ws.numel() < nbytes:
+        ws = None
+        _DEEP_WS.pop(dev, None)            # (released before the larger one is taken)
+        ws = _DEEP_WS[dev] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws[:32].zero_()
+    fn = lib.pda_deep_topk_bf16 if bf else lib.pda_deep_topk_f32
+    for lo in range(0, nu, chunk):
+        hi = min(nu, lo + chunk)
+        ip = None
+        if hist is not None:     # rows by user id: the whole CSR; by block row: the chunk's rows (indptr keeps its absolute offsets)
+            ip = hist.indptr if hist.mode == HIST_BY_USER_ID else hist.indptr[lo:hi + 1]
+        check(fn(ptr(U), ptr(I_shard), ptr(pop_shard), ptr(users[lo:hi]), hi - lo, int(item_offset), nloc, d, ptr(ip),
+                 ptr(hist.indices) if hist else None, hist.mode if hist else 0, K, int(head),
+                 ptr(out_keys[lo:hi]) if out_keys is not None else None, ptr(out_idx[lo:hi]) if out_idx is not None else None,
+                 ptr(out_val[lo:hi]) if out_val is not None else None, ptr(ws), ws.numel(), stream_ptr()),
+              "pda_deep_topk_bf16" if bf else "pda_deep_topk_f32")
+    if stats is not None:
+        stats["kernel_id"] = ws[16:20].view(torch.int32).clone()
+        stats["workspace_bytes"] = nbytes
+        stats["chunk_users"] = chunk
+    return out_keys if want == "keys" else (out_idx, out_val)
+
+
+def _metrics_deep(topk, tgt_indptr, tgt_indices, Ks, sums, ordered: bool):
+    lib = _lib.load()
+    topk = _need(topk, torch.int32, "topk")
+    tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
+    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    Ks = _need(Ks, torch.int32, "Ks")
+    if not 1 <= topk.shape[1] <= DEEP_MAX_K:
+        raise ValueError(f"deep metrics take lists of 1 .. {DEEP_MAX_K} columns, got {topk.shape[1]}")
+    if sums is None:
+        sums = torch.zeros((4, Ks.numel()), dtype=torch.float64, device=topk.device)
+    ws = None
+    if ordered:
+        nb = lib.pda_metrics_deep_workspace_bytes(topk.shape[0], Ks.numel())
+        ws = _METRICS_WS.get(topk.device)
+        if ws is None or ws.numel() * 8 < nb:
+            ws = _METRICS_WS[topk.device] = torch.empty(max(1, nb // 8), dtype=torch.float64, device=topk.device)
+    check(lib.pda_metrics_deep(ptr(topk), topk.shape[0], topk.shape[1], ptr(tgt_indptr), ptr(tgt_indices), ptr(Ks), Ks.numel(), ptr(sums),
+                               ptr(ws), stream_ptr()), "pda_metrics_deep")
+    return sums
+
+
+def metrics_sums_deep(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_metrics_deep: metrics_sums on lists of up to 1 024 columns (float atomics)."""
+    return _metrics_deep(topk, tgt_indptr, tgt_indices, Ks, sums, ordered=False)
+
+
+def metrics_sums_deep_ordered(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_metrics_deep with a workspace: the ordered reduction of metrics_sums_ordered (the same bits run after run)."""
+    return _metrics_deep(topk, tgt_indptr, tgt_indices, Ks, sums, ordered=True)

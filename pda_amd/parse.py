@@ -73,6 +73,8 @@ _EXTENSION_FLAGS = [
     ("table_dtype", str, "f32", "f32 | bf16 (BASELINE config 5): bf16 embedding tables for the forward pass and the evaluation, fp32 masters take the updates"),
     ("deterministic", int, 0, "1: the run is a function of its flags and data alone, bit for bit -- gradients summed in the order of the batch's plan and metrics in wave order instead of with float atomics (adam, lazy_adam, sgd on one GPU, fp32 tables under Adam; not temp_pop)"),
     ("eval_block", int, 262144, "users per score+top-K launch (the reference always uses 2048, MF/train_new_api.py:703); large blocks balance the early-terminating sweep: 92 M users/s at 65536, 109 M at 262144 (C3)"),
+    ("topk_max", int, 50, "columns of every ranking (the reference's graph constant, MF/train_new_api.py:594: 50); 1 .. 1024.  Above 54 the lists come from the deep path (include/pda_hip_deep.h): --train normal | s_condition on one GPU"),
+    ("export_out", str, "", "python -m pda_amd.export_topk: the .npz file that receives users, idx and val"),
 ]
 
 

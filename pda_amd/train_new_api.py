@@ -82,8 +82,26 @@ def reference_block_first(eval_pos: int, n: int, device=None, block: int = 2048)
     return torch.div(posn, block, rounding_mode="floor") * block
 
 
+def check_topk_max(args, topk_shard=None) -> int:
+    """--topk_max (an extension; 50 = the reference's graph constant): the columns of every ranking.  Above ops.TOPK_K_V4 the lists come from
+    the deep path (ops.recommend_topk_deep), which has the raw and the popularity head on one GPU: everything else is refused here."""
+    k = getattr(args, "topk_max", None)
+    k = 50 if k is None else int(k)
+    if not 1 <= k <= ops.DEEP_MAX_K:
+        raise ValueError("--topk_max must lie in 1 .. %d, got %d" % (ops.DEEP_MAX_K, k))
+    if k > ops.TOPK_K_V4:
+        if getattr(args, "train", "normal") == "temp_pop":
+            raise NotImplementedError("--topk_max %d: lists deeper than %d have no bias head (--train temp_pop ranks by s + alpha beta; the deep path "
+                                      "ranks by the raw and the popularity head only)" % (k, ops.TOPK_K_V4))
+        if topk_shard is not None:
+            raise NotImplementedError("--topk_max %d: lists deeper than %d are not merged across item shards (pda_topk_merge takes at most %d columns): "
+                                      "evaluate on one GPU" % (k, ops.TOPK_K_V4, ops._lib.MAX_K))
+    return k
+
+
 class DatasetApi_Model:
     def __init__(self, args, data_config, test_batch, generator_sampler, device=None, topk_shard=None):
+        topk_max = check_topk_max(args, topk_shard)
         self.args = args
         self.device = torch.device(device if device is not None else "cuda")
         self.generator_sampler = generator_sampler
@@ -114,10 +132,10 @@ class DatasetApi_Model:
         self.Recommender.users_distinct = bool(getattr(generator_sampler, "distinct_users", False))
         self.n_items = data_config["n_items"]
         self._shard = topk_shard            # optional pda_amd.dist.ItemShardedTopK (multi-GPU evaluation)
-        self.Create_Recommendation()
+        self.Create_Recommendation(topk_max)
 
     def Create_Recommendation(self, topk_max=50):
-        self.topk_max = topk_max            # "top-K hard-capped at 50" (:594)
+        self.topk_max = topk_max            # "top-K hard-capped at 50" (:594); --topk_max
 
     # ---- training side ------------------------------------------------------------------------------
     def switch_to_training_or_reinitsampler(self, sess=None):
@@ -236,6 +254,8 @@ class DatasetApi_Model:
         if self._shard is not None and _sel is None:
             self._shard.set_popularity(pop_t)
             return self._shard.topk(users, K, head, hist)
+        if K > ops.TOPK_K_V4:               # deep lists (--topk_max): the exact sweep with its lists in the workspace
+            return ops.recommend_topk_deep(self.Recommender.score_tables()[0], I, users, K, head, pop_t, hist)
         return ops.recommend_topk(self.Recommender.score_tables()[0], I, users, K, head, pop_t, hist)
 
     def testing(self, sess, batch_users, items, model_type, pos_pop=None):
@@ -352,7 +372,11 @@ class evaluation:
             tp = self._tp_host[i:i + ub.numel() + 1]
             tptr = torch.from_numpy(tp - tp[0]).to(self.device)
             # --deterministic 1: the ordered reduction -- recall decides the early stop and the best checkpoint with `>=`
-            reduce = ops.metrics_sums_ordered if int(getattr(args, "deterministic", 0) or 0) else ops.metrics_sums
+            det = int(getattr(args, "deterministic", 0) or 0)
+            if idx.shape[1] > ops._lib.MAX_K:   # (--topk_max: pda_metrics keeps a 64-bit hit mask)
+                reduce = ops.metrics_sums_deep_ordered if det else ops.metrics_sums_deep
+            else:
+                reduce = ops.metrics_sums_ordered if det else ops.metrics_sums
             reduce(idx, tptr, self.tgt_indices[int(tp[0]):int(tp[-1])], ks, sums)
         s = (sums / float(self.tot_user)).cpu().numpy()
         return {"precision": s[0], "recall": s[1], "ndcg": s[2], "hit_ratio": s[3]}
@@ -407,6 +431,7 @@ def main(argv=None):
     print("*** Current working path ***")
     print(os.getcwd())
     configure(argv)
+    check_topk_max(args)                   # (refusals before anything is built)
     random.seed(2020)                      # :934-936
     np.random.seed(2020)
     torch.manual_seed(2021)

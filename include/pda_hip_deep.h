@@ -15,6 +15,17 @@
  *   d in {32, 64, 128, 256}, else PDA_ERR_UNSUPPORTED;  1 <= K <= min(PDA_DEEP_MAX_K, n_items_local), else PDA_ERR_ARG;
  *   a workspace smaller than pda_deep_topk_workspace_bytes says: PDA_ERR_WORKSPACE.  The workspace is 16-byte aligned.
  *   Behind the call: workspace + 16 the identity word  8 << 28 | bf16 << 14 | head << 13 | d / 64  (generation 8 = the deep path).
+ *
+ * Item shards ("Deep lists on item shards"): every shard runs pda_deep_topk_* on its rows with min(K, n_items_local) columns and
+ * out_keys alone, the lists are exchanged, and pda_deep_merge merges them -- pda_topk_merge's contract for 1 <= K <= PDA_DEEP_MAX_K:
+ *   in       u64 [R, n_users_blk, K]; every list best first, 0 = an empty slot, zeros only behind a list's last key; the non-zero keys of a
+ *            row are distinct across its lists (a precondition: the shards are disjoint)
+ *   out      the K largest keys of the row's union, descending, as out_keys and / or out_idx + out_val; a slot that stays empty holds key 0
+ *            and value -inf.  With out_idx, empty slots take the user's WHOLE history row (hist_indptr != NULL; PDA_HIST_BY_USER_ID needs
+ *            `users`), lowest id first, duplicates once, then -1 -- what a one-GPU pda_deep_topk_* call writes; without a history -1.
+ *   errors   R < 1, K outside 1 .. PDA_DEEP_MAX_K, n_users_blk < 1, in_keys NULL, out_keys and out_idx both NULL: PDA_ERR_ARG;
+ *            R * K > PDA_DEEP_MERGE_MAX_KEYS (64 KB of keys in a CU's 160 KB of LDS): PDA_ERR_UNSUPPORTED -- merge groups of lists to keys first
+ *            (the order is total: merging in groups is exact).  No workspace; integers only: the same bits whatever the launch geometry.
  */
 #ifndef PDA_HIP_DEEP_H
 #define PDA_HIP_DEEP_H
@@ -48,6 +59,11 @@ int pda_deep_topk_bf16(const uint16_t* U, const uint16_t* I_shard, const float* 
 size_t pda_metrics_deep_workspace_bytes(int n_rows, int n_ks);
 int pda_metrics_deep(const int32_t* topk, int n_rows, int k_cols, const int64_t* tgt_indptr, const int32_t* tgt_indices, const int32_t* Ks,
                      int n_ks, double* sums, void* workspace, void* stream);
+
+/* Merge of R sorted lists of K keys per user (the lists of R item shards) into one: see "Item shards" above. */
+#define PDA_DEEP_MERGE_MAX_KEYS 8192
+int pda_deep_merge(const uint64_t* in_keys, int R, int n_users_blk, int K, uint64_t* out_keys, int32_t* out_idx, float* out_val,
+                   const int32_t* users, const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, void* stream);
 
 #ifdef __cplusplus
 }

@@ -165,12 +165,14 @@ DET_SIGNATURES = {
 
 # name -> (restype, argtypes); exactly the declarations of include/pda_hip_deep.h (deep lists: exact top-K up to 1 024, `--topk_max`)
 DEEP_MAX_K = 1024
+DEEP_MERGE_MAX_KEYS = 8192
 DEEP_SIGNATURES = {
     "pda_deep_topk_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pda_deep_topk_f32": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pda_deep_topk_bf16": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pda_metrics_deep_workspace_bytes": (_sz, [_i, _i]),
     "pda_metrics_deep": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "pda_deep_merge": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 _lib = None

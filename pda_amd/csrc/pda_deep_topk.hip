@@ -15,6 +15,7 @@
 //                <= cap: the retry cannot fail).  Items are visited in natural order, so a row accepts about K ln(n / K) candidates in all.
 //   last pass  = deep_final_kernel, one workgroup per row: gathers the row's buffers of every split, sorts them best first, writes K keys /
 //                ids / values and completes a short row with its listed items.
+//   shards     = deep_merge_kernel (pda_deep_merge): the sorted lists of R item shards -> one list per user, by ranks, without a sort.
 #include "pda_topk_common.h"
 #include "pda_hip_deep.h"
 
@@ -502,6 +503,240 @@ int deep_topk(const void* U, const void* I_shard, const float* pop_shard, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Merge of R sorted lists of K <= 1 024 keys per row (pda_deep_merge): the item shards' lists of a user -> the user's list.  One workgroup
+// per row, the row's R * K keys in LDS.  The lists are sorted, so nothing is sorted here:
+//   floor     the K-th key of the union is at least (a) the largest K-th key of any list and (b) the smallest ceil(K / R)-th key of the lists
+//             (every list holds that many keys at or above it: R ceil(K / R) >= K of them).  Equal shards put (b) near the answer.
+//   cut       per list, how many of its keys reach the floor (one binary search): only those can rank, and only those need to be searched.
+//   rank      the survivors are dealt to the threads evenly (a prefix sum of the cuts); a survivor's place in the result is the number of
+//             keys above it = the sum of its lower bounds in the lists' survivors (its own list gives its own position: the keys of a row are
+//             distinct).  Four lists are searched at a time, so that four LDS reads are in flight per step.
+// The keys are integers and every result slot is written by the one key whose rank it is: the result does not depend on the geometry.
+// ------------------------------------------------------------------------------------------------
+struct DeepMergeArgs {
+    const uint64_t* in_keys;
+    uint64_t* out_keys;
+    int32_t* out_idx;
+    float* out_val;
+    const int32_t* users;
+    const int64_t* hist_indptr;
+    const int32_t* hist_indices;
+    int hist_row_mode, R, n_users_blk, K;
+    int vec;   // every array starts on a 16-byte boundary: 16-byte loads and stores
+};
+
+constexpr int kMergeThreads = 256;
+constexpr int kMergeLoads = 8;     // 16-byte loads a thread has in flight while it stages a row
+
+// LDS of a row: keys u64 [R K] | merged u64 [K] | floors u64 [2] | ids i32 [K] | cut i32 [R] | prefix i32 [R + 1] | partial sums i32 [256]
+inline size_t deep_merge_smem(int R, int K) {
+    return ((size_t)R * K + K + 2) * sizeof(uint64_t) + ((size_t)K + 2 * (size_t)R + 1 + kMergeThreads) * sizeof(int);
+}
+
+__global__ void __launch_bounds__(kMergeThreads) deep_merge_kernel(DeepMergeArgs a) {
+    typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, R = a.R, K = a.K, n = R * K;
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
+    uint64_t* outl = keys + n;
+    unsigned long long* floors = reinterpret_cast<unsigned long long*>(outl + K);
+    int* ids = reinterpret_cast<int*>(floors + 2);
+    int* cut = ids + K;
+    int* pre = cut + R;
+    int* part = pre + R + 1;
+    const size_t u = blockIdx.x;
+
+    // ---- the row's lists -> LDS.  A list starts on an 8-byte boundary: 16-byte chunks counted from the 16-byte boundary at or below it.
+    // kMergeLoads chunks per thread are loaded before the first is written: 64 KB in flight per CU at two workgroups (measured against a
+    // chunk at a time: 4.0 - 4.1 instead of 4.4 ms at R = 8, K = 1 000 and 65 536 rows) ----
+    const int P = (K + 2) >> 1;   // chunks that cover a list wherever it starts
+    const int W = R * P;
+    for (int w0 = tid; w0 < W; w0 += kMergeThreads * kMergeLoads) {
+        u64x2 v[kMergeLoads];
+        int at[kMergeLoads];      // LDS index of the chunk's first key; -1: that key is not the list's
+        bool second[kMergeLoads];
+#pragma unroll
+        for (int q = 0; q < kMergeLoads; ++q) {
+            const int w = w0 + q * kMergeThreads;
+            const bool in = w < W;
+            const int r = in ? w / P : 0, c = in ? w - r * P : 0;
+            const size_t e0 = ((size_t)r * a.n_users_blk + u) * K;
+            const uint64_t* g = a.in_keys + e0;
+            const int p0 = 2 * c - (int)(e0 & 1);
+            const bool k0 = in && p0 >= 0 && p0 < K, k1 = in && p0 + 1 < K;
+            if (a.vec && k0 && k1) {
+                v[q] = *reinterpret_cast<const u64x2*>(g + p0);
+            } else {
+                v[q][0] = k0 ? g[p0] : 0ull;
+                v[q][1] = k1 ? g[p0 + 1] : 0ull;
+            }
+            at[q] = k0 ? r * K + p0 : -1;
+            second[q] = k1;
+            if (!k0 && k1) at[q] = -(r * K + p0 + 1) - 2;   // (only the chunk's second key is the list's: its index, folded below -1)
+        }
+#pragma unroll
+        for (int q = 0; q < kMergeLoads; ++q) {
+            if (at[q] >= 0) {
+                keys[at[q]] = v[q][0];
+                if (second[q]) keys[at[q] + 1] = v[q][1];
+            } else if (at[q] < -1) {
+                keys[-(at[q] + 2)] = v[q][1];
+            }
+        }
+    }
+    for (int i = tid; i < K; i += kMergeThreads) outl[i] = 0ull;
+    if (tid == 0) {
+        floors[0] = 0ull;
+        floors[1] = ~0ull;
+    }
+    __syncthreads();
+
+    // ---- the floor ----
+    const int t = (K + R - 1) / R;
+    for (int r = tid; r < R; r += kMergeThreads) {
+        atomicMax(&floors[0], (unsigned long long)keys[r * K + K - 1]);   // (LDS, integers)
+        atomicMin(&floors[1], (unsigned long long)keys[r * K + t - 1]);
+    }
+    __syncthreads();
+    uint64_t fl = floors[0] > floors[1] ? floors[0] : floors[1];
+    fl = fl ? fl : 1ull;          // an empty slot never ranks
+
+    // ---- cuts and their prefix sums: thread q owns the lists [q chunk, (q + 1) chunk) ----
+    const int chunk = (R + kMergeThreads - 1) / kMergeThreads;
+    const int r_lo = min(tid * chunk, R), r_hi = min(r_lo + chunk, R);
+    int mine = 0;
+    for (int r = r_lo; r < r_hi; ++r) {
+        const uint64_t* l = keys + r * K;
+        int lo = 0, hi = K;       // first position whose key is below the floor
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (l[mid] >= fl) lo = mid + 1; else hi = mid;
+        }
+        cut[r] = lo;
+        mine += lo;
+    }
+    part[tid] = mine;
+    __syncthreads();
+    if (r_lo < r_hi) {
+        int base = 0;
+        for (int q = 0; q < tid; ++q) base += part[q];
+        for (int r = r_lo; r < r_hi; ++r) {
+            pre[r] = base;
+            base += cut[r];
+        }
+        if (r_hi == R) pre[R] = base;
+    }
+    __syncthreads();
+
+    // ---- every survivor's rank ----
+    const int S = pre[R];
+    for (int s = tid; s < S; s += kMergeThreads) {
+        int lo = 0, hi = R - 1;   // the survivor's list: the last one that starts at or before s
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (pre[mid] <= s) lo = mid; else hi = mid - 1;
+        }
+        const uint64_t key = keys[lo * K + (s - pre[lo])];
+        int rank = 0, r2 = 0;
+        for (; r2 + 4 <= R; r2 += 4) {
+            const uint64_t *b0 = keys + r2 * K, *b1 = b0 + K, *b2 = b1 + K, *b3 = b2 + K;
+            int l0 = 0, l1 = 0, l2 = 0, l3 = 0, h0 = cut[r2], h1 = cut[r2 + 1], h2 = cut[r2 + 2], h3 = cut[r2 + 3];
+            while ((l0 < h0) | (l1 < h1) | (l2 < h2) | (l3 < h3)) {
+                // (a finished search reads the slot at its bound again -- at most b[K], still this row's LDS -- and ignores it)
+                const int m0 = (l0 + h0) >> 1, m1 = (l1 + h1) >> 1, m2 = (l2 + h2) >> 1, m3 = (l3 + h3) >> 1;
+                const uint64_t k0 = b0[m0], k1 = b1[m1], k2 = b2[m2], k3 = b3[m3];
+                if (l0 < h0) { if (k0 > key) l0 = m0 + 1; else h0 = m0; }
+                if (l1 < h1) { if (k1 > key) l1 = m1 + 1; else h1 = m1; }
+                if (l2 < h2) { if (k2 > key) l2 = m2 + 1; else h2 = m2; }
+                if (l3 < h3) { if (k3 > key) l3 = m3 + 1; else h3 = m3; }
+            }
+            rank += l0 + l1 + l2 + l3;
+        }
+        for (; r2 < R; ++r2) {
+            const uint64_t* b = keys + r2 * K;
+            int l0 = 0, h0 = cut[r2];
+            while (l0 < h0) {
+                const int m0 = (l0 + h0) >> 1;
+                if (b[m0] > key) l0 = m0 + 1; else h0 = m0;
+            }
+            rank += l0;
+        }
+        if (rank < K) outl[rank] = key;
+    }
+    __syncthreads();
+
+    // ---- how many slots are filled (the ranks 0 .. nreal - 1 are all taken), the ids, a short row's listed items ----
+    int nreal = 0;
+    {
+        int hi = K;
+        while (nreal < hi) {
+            const int mid = (nreal + hi) >> 1;
+            if (outl[mid] != 0ull) nreal = mid + 1; else hi = mid;
+        }
+    }
+    if (a.out_idx) {
+        for (int i = tid; i < K; i += kMergeThreads) {
+            const uint64_t k = outl[i];
+            ids[i] = k ? pda_key_item(k) : -1;
+        }
+        if (nreal < K && a.hist_indptr) {   // (the same in every thread)
+            __syncthreads();
+            if (tid == 0) {
+                const int64_t hr = a.hist_row_mode == PDA_HIST_BY_USER_ID ? (int64_t)a.users[u] : (int64_t)u;
+                int at = nreal, prev = -1;
+                for (int64_t p = a.hist_indptr[hr]; p < a.hist_indptr[hr + 1] && at < K; ++p) {
+                    const int it = a.hist_indices[p];
+                    if (it != prev) ids[at++] = it;
+                    prev = it;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- out: 16-byte stores counted from the 16-byte boundary at or below the row's start, single words at the row's ends ----
+    const size_t o0 = u * (size_t)K;
+    if (a.out_keys) {
+        uint64_t* g = a.out_keys + o0;
+        const int a0 = (int)(o0 & 1);
+        for (int c = tid; c < (a0 + K + 1) >> 1; c += kMergeThreads) {
+            const int p0 = 2 * c - a0;
+            if (a.vec && p0 >= 0 && p0 + 1 < K) {
+                const u64x2 v = {outl[p0], outl[p0 + 1]};
+                *reinterpret_cast<u64x2*>(g + p0) = v;
+            } else {
+                if (p0 >= 0) g[p0] = outl[p0];
+                if (p0 + 1 < K) g[p0 + 1] = outl[p0 + 1];
+            }
+        }
+    }
+    if (a.out_idx || a.out_val) {
+        const int a0 = (int)(o0 & 3);
+        for (int c = tid; c < (a0 + K + 3) >> 2; c += kMergeThreads) {
+            const int p0 = 4 * c - a0;
+            if (a.vec && p0 >= 0 && p0 + 3 < K) {
+                if (a.out_idx) {
+                    const i32x4 v = {ids[p0], ids[p0 + 1], ids[p0 + 2], ids[p0 + 3]};
+                    *reinterpret_cast<i32x4*>(a.out_idx + o0 + p0) = v;
+                }
+                if (a.out_val) {
+                    f32x4 v;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = p0 + q < nreal ? pda_key_val(outl[p0 + q]) : -INFINITY;
+                    *reinterpret_cast<f32x4*>(a.out_val + o0 + p0) = v;
+                }
+            } else {
+                for (int p = max(p0, 0); p < min(p0 + 4, K); ++p) {
+                    if (a.out_idx) a.out_idx[o0 + p] = ids[p];
+                    if (a.out_val) a.out_val[o0 + p] = p < nreal ? pda_key_val(outl[p]) : -INFINITY;
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Metrics on deep lists: one thread per user row, the row walked once per K (no 64-bit hit mask).  Same sums and the same two reductions
 // as pda_metrics / pda_metrics_ordered (pda_aux.hip).
 // ------------------------------------------------------------------------------------------------
@@ -608,6 +843,31 @@ extern "C" int pda_deep_topk_bf16(const uint16_t* U, const uint16_t* I_shard, co
                                   size_t workspace_bytes, void* stream) {
     return deep_topk<true>(U, I_shard, pop_shard, users, n_users_blk, item_offset, n_items_local, d, hist_indptr, hist_indices, hist_row_mode,
                            K, head, out_keys, out_idx, out_val, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pda_deep_merge(const uint64_t* in_keys, int R, int n_users_blk, int K, uint64_t* out_keys, int32_t* out_idx, float* out_val,
+                              const int32_t* users, const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, void* stream) {
+    if (!in_keys || R < 1 || n_users_blk <= 0 || K < 1 || K > PDA_DEEP_MAX_K) return PDA_ERR_ARG;
+    if (!out_keys && !out_idx) return PDA_ERR_ARG;
+    if (hist_indptr && !hist_indices) return PDA_ERR_ARG;
+    if (hist_indptr && hist_row_mode != PDA_HIST_BY_BLOCK_ROW && hist_row_mode != PDA_HIST_BY_USER_ID) return PDA_ERR_ARG;
+    if (hist_indptr && hist_row_mode == PDA_HIST_BY_USER_ID && !users) return PDA_ERR_ARG;
+    if ((long long)R * K > PDA_DEEP_MERGE_MAX_KEYS) return PDA_ERR_UNSUPPORTED;
+    const size_t smem = deep_merge_smem(R, K);
+    if (smem > 160 * 1024) return PDA_ERR_UNSUPPORTED;   // (not reached: 132 KB at R = 8 192, K = 1)
+    static int attr_set = 0;
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&deep_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+            hipSuccess)
+            return PDA_ERR_LAUNCH;
+        attr_set = 1;
+    }
+    const int vec = ((reinterpret_cast<uintptr_t>(in_keys) | reinterpret_cast<uintptr_t>(out_keys) | reinterpret_cast<uintptr_t>(out_idx) |
+                      reinterpret_cast<uintptr_t>(out_val)) & 15u) == 0;
+    DeepMergeArgs a{in_keys, out_keys, out_idx, out_val, users, hist_indptr, hist_indices, hist_row_mode, R, n_users_blk, K, vec};
+    hipLaunchKernelGGL(deep_merge_kernel, dim3((unsigned)n_users_blk), dim3(kMergeThreads), smem, reinterpret_cast<hipStream_t>(stream), a);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
 }
 
 extern "C" size_t pda_metrics_deep_workspace_bytes(int n_rows, int n_ks) {

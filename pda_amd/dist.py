@@ -2,7 +2,8 @@
 
 One process per GPU.  Rank r owns the item rows [lo_r, hi_r) (+ their popularity); the user table and the
 history CSR are replicated.  Per user block every rank produces its partial top-K (packed keys), then ONE RCCL
-collective over xGMI and a merge with pda_topk_merge:
+collective over xGMI and a merge with pda_topk_merge (lists deeper than 54: pda_deep_topk_* per shard, the exchange in user chunks
+of deep_exchange_chunk with one collective each, pda_deep_merge -- no seeds, no hot items):
     topk           all-gather (Bu*K*8 bytes per rank out, R times that in): every rank ends up with the full [Bu, K]
     topk_sharded   all-to-all (R times less traffic, R-1 links in parallel on the full mesh): rank r merges and keeps the
                    lists of ITS slice of the users -- what bench.py times for N > 1 (at R = 8 the all-gather would move
@@ -115,7 +116,26 @@ def _ops_score_fn():
     return ops.score_topk_keys
 
 
+def _ops_merge_fn():
+    from . import ops
+    return ops.topk_merge
+
+
+def deep_exchange_chunk(n_users: int, K: int, world: int) -> int:
+    """Users of a block per collective of a deep exchange (K > ops.TOPK_K_V4): the gathered [world, chunk, K] int64 stays within
+    ops.DEEP_WORKSPACE_BUDGET.  A whole number of users per rank (at least one), at most the block rounded up to one.  A function of
+    (n_users, K, world) ONLY -- never of the local shard or of the chunks of the scoring call: every rank issues the same collectives
+    in the same order."""
+    from . import ops
+    per_rank = max(1, ops.DEEP_WORKSPACE_BUDGET // (world * world * K * 8))
+    return min(per_rank, max(1, -(-n_users // world))) * world
+
+
 class ItemShardedTopK:
+    # lists deeper than ops.TOPK_K_V4 (up to ops.DEEP_MAX_K) are merged across the shards: ops.deep_shard_keys per rank, the lists exchanged
+    # in user chunks (deep_exchange_chunk), ops.deep_merge -- what train_new_api.check_topk_max asks a shard object for
+    deep_lists = True
+
     def __init__(self, U: torch.Tensor, I_shard: torch.Tensor, item_offset: int, pop_shard: Optional[torch.Tensor] = None,
                  rank: int = 0, world: int = 1, group=None, score_fn: Optional[Callable] = None,
                  merge_fn: Optional[Callable] = None):
@@ -196,8 +216,22 @@ class ItemShardedTopK:
         self.n_collectives += 1
         dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
 
+    @staticmethod
+    def _deep(K) -> bool:
+        from . import ops
+        return K > ops.TOPK_K_V4
+
+    def _merge(self, K):
+        """The merge of [R, Bu, K] lists: the caller's own function at any K, else pda_topk_merge / pda_deep_merge by K."""
+        if self._deep(K) and self.merge_fn is _ops_merge_fn():
+            from . import ops
+            return ops.deep_merge
+        return self.merge_fn
+
     def _seed_applies(self, K, head) -> bool:
         from . import ops
+        if self._deep(K):                   # deep lists: every shard ships its K keys per user, no seed exchange
+            return False
         return self.world > 1 and self.seeded and ops.seed_exchange_applies(self.I_shard.shape[1], K, head, self.prune)
 
     def _validate_once(self, head):
@@ -232,7 +266,24 @@ class ItemShardedTopK:
         if n_thr > 0:
             self._seed_sum(torch.zeros((n_thr, nu), dtype=torch.int32, device=dev))
 
+    def _deep_local_keys(self, users, K, head, hist):
+        """local_keys for K > ops.TOPK_K_V4: this shard's sorted list per user, zeros behind its keys ([Bu, K]; one rank: [1, Bu, K])."""
+        if self.score_fn is _ops_score_fn():
+            from . import ops
+            if self.world > 1:
+                self._validate_once(head)   # (a rank that raised alone would leave the others waiting in the exchange)
+            keys = ops.deep_shard_keys(self.U, self.I_shard, users, K, head, self.pop_shard if head else None, hist, self.item_offset)
+            return keys[None] if self.world == 1 else keys
+        if self.I_shard.shape[0] == 0:
+            return torch.zeros((users.numel(), K) if self.world > 1 else (1, users.numel(), K), dtype=torch.int64, device=users.device)
+        keys = self.score_fn(self.U, self.I_shard, users, K, head, self.pop_shard if head else None, hist, self.item_offset, 0)
+        if self.world == 1:
+            return keys
+        return keys[0] if keys.shape[0] == 1 else self.merge_fn(keys, users, hist, want="keys")
+
     def local_keys(self, users, K, head, hist):
+        if self._deep(K):
+            return self._deep_local_keys(users, K, head, hist)
         seeded = self._seed_applies(K, head)
         if seeded:
             self._validate_once(head)
@@ -259,9 +310,11 @@ class ItemShardedTopK:
     def topk(self, users, K=50, head=0, hist=None):
         keys = self.local_keys(users, K, head, hist)
         if self.world > 1:
+            if self._deep(K):
+                return self._finish_deep(keys, users, hist, False)
             self.n_collectives += 1
             keys = _all_gather_keys(keys, self.world, self.group)     # [R, Bu, K] -- the one collective
-        return self.merge_fn(keys, users, hist, want="idx_val")
+        return self._merge(K)(keys, users, hist, want="idx_val")
 
     def user_slice(self, n_users: int) -> Tuple[int, int]:
         """Rows of a user block whose final lists THIS rank produces in sharded mode."""
@@ -271,6 +324,8 @@ class ItemShardedTopK:
     def _finish(self, keys, users, hist, sharded: bool):
         """The exchange + final merge of one block.  sharded: all-to-all, this rank merges its slice of the users and
         returns (idx, val) for those rows only; else all-gather and every rank merges everything."""
+        if self._deep(keys.shape[1]):
+            return self._finish_deep(keys, users, hist, sharded)
         self.n_collectives += 1
         if sharded and users.numel() % self.world == 0 and (hist is None or getattr(hist, "mode", 1) == 1):
             lo, hi = self.user_slice(users.numel())
@@ -284,12 +339,48 @@ class ItemShardedTopK:
             return tuple(t[lo:lo + per] for t in res)
         return res
 
+    @staticmethod
+    def _hist_rows(hist, a, b):
+        """The history of the block rows [a, b): a CSR by block row keeps its absolute offsets, one by user id is the whole CSR."""
+        if hist is None or isinstance(hist, tuple) or getattr(hist, "mode", 1) == 1:
+            return hist
+        return type(hist)(hist.indptr[a:b + 1].contiguous(), hist.indices, by_user=False)
+
+    def _finish_deep(self, keys, users, hist, sharded: bool):
+        """_finish for K > ops.TOPK_K_V4: the users go through the exchange in chunks of deep_exchange_chunk -- ONE collective and one
+        merge per chunk, so that the gathered lists stay within ops.DEEP_WORKSPACE_BUDGET (262 144 users x 1 000 keys x 8 ranks are
+        16.8 GB at once).  The chunks are the same on every rank."""
+        nu, K = users.numel(), keys.shape[1]
+        merge, chunk, outs = self._merge(K), deep_exchange_chunk(users.numel(), keys.shape[1], self.world), []
+        a2a = sharded and nu % self.world == 0 and (hist is None or getattr(hist, "mode", 1) == 1)
+        if a2a:                               # all-to-all: chunk / R rows of every rank's user slice at a time
+            per, step = nu // self.world, chunk // self.world
+            lo, _ = self.user_slice(nu)
+            by_owner = keys.view(self.world, per, K)
+            for a in range(0, per, step):
+                b = min(per, a + step)
+                self.n_collectives += 1
+                allk = _exchange_user_slices(by_owner[:, a:b].reshape(-1, K), self.world, self.group)
+                outs.append(merge(allk, users[lo + a:lo + b].contiguous(), hist, want="idx_val"))
+        else:
+            for a in range(0, nu, chunk):
+                b = min(nu, a + chunk)
+                self.n_collectives += 1
+                allk = _all_gather_keys(keys[a:b], self.world, self.group)
+                outs.append(merge(allk, users[a:b].contiguous(), self._hist_rows(hist, a, b), want="idx_val"))
+        res = outs[0] if len(outs) == 1 else tuple(torch.cat(t) for t in zip(*outs))
+        if sharded and not a2a:               # block not divisible by the world size: slice the full result
+            per = -(-nu // self.world)
+            lo = min(self.rank * per, nu)
+            return tuple(t[lo:lo + per] for t in res)
+        return res
+
     def topk_sharded(self, users, K=50, head=0, hist=None):
         """(idx, val) of this rank's user slice (`user_slice`): the multi-GPU path with R times less traffic; the union
         over ranks is what `topk` returns on every rank."""
         keys = self.local_keys(users, K, head, hist)
         if self.world == 1:
-            return self.merge_fn(keys, users, hist, want="idx_val")
+            return self._merge(K)(keys, users, hist, want="idx_val")
         return self._finish(keys, users, hist, True)
 
     # -- replicated hot items: item shards without a warm-up per rank (round 4) -------------------------------------------------
@@ -303,6 +394,8 @@ class ItemShardedTopK:
     # K-th value of any K items, so it is a hot pair or a cold pair at or above the seed.  Dense sweeps and early-terminating ones (the
     # product default for this head: the cold sweep then stops where a one-GPU sweep would -- its seed is that sweep's warm-up value).
     def _hot_applies(self, K, head, hist, users, sharded) -> bool:
+        if self._deep(K):                   # deep lists: the hot pass, its K-th values and the sweep from a seed stop at K = 54
+            return False
         if not (self.hot_items and self.world >= 2 and sharded and head == 1 and self.prune in ("order", True, None)):
             return False
         if self.world < self.hot_min_shards and users.numel() < self.hot_min_users_two_shards:

@@ -1834,6 +1834,67 @@ def recommend_topk_deep(U, I_shard, users, K, head=HEAD_RAW, pop_shard=None, his
     return out_keys if want == "keys" else (out_idx, out_val)
 
 
+DEEP_MERGE_MAX_KEYS = _lib.DEEP_MERGE_MAX_KEYS      # keys of a row that one pda_deep_merge launch holds in LDS (R * K)
+
+
+def deep_merge(keys: torch.Tensor, users=None, hist: Optional[HistoryCSR] = None, want="idx_val"):
+    """pda_deep_merge: topk_merge for lists of 1 .. 1 024 columns.  keys int64 [R, Bu, K], every list best first, zeros behind its keys, the
+    keys of a row distinct across its lists.  want: 'keys' -> int64 [Bu, K]; 'idx_val' -> (int32, float32), a short row completed from the
+    user's history row.  More than DEEP_MERGE_MAX_KEYS keys per row are folded: groups of at most 8192 // K lists are merged to keys until
+    one launch is left (the order is total: the fold is exact)."""
+    lib = _lib.load()
+    keys = _need(keys, torch.int64, "keys")
+    if keys.dim() != 3:
+        raise ValueError("keys must be [R, Bu, K]")
+    R, nu, K = keys.shape
+    if not 1 <= K <= DEEP_MAX_K:
+        raise ValueError(f"deep lists need 1 <= K <= {DEEP_MAX_K}, got {K}")
+    if R < 1 or nu < 1:
+        raise ValueError("deep_merge needs at least one list and one user")
+    dev = keys.device
+    if users is not None:
+        users = _need(users, torch.int32, "users")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+
+    def launch(src, out_keys, out_idx, out_val, h):
+        check(lib.pda_deep_merge(ptr(src), src.shape[0], nu, K, ptr(out_keys), ptr(out_idx), ptr(out_val), ptr(users),
+                                 ptr(h.indptr) if h else None, ptr(h.indices) if h else None, h.mode if h else 0, stream_ptr()),
+              "pda_deep_merge")
+
+    group = max(2, DEEP_MERGE_MAX_KEYS // K)           # lists per launch (K > 4 096 does not occur: two lists always fit)
+    while keys.shape[0] > group:
+        n_groups = -(-keys.shape[0] // group)
+        folded = torch.empty((n_groups, nu, K), dtype=torch.int64, device=dev)
+        for g in range(n_groups):
+            launch(keys[g * group:(g + 1) * group], folded[g], None, None, None)
+        keys = folded
+    if want == "keys":
+        out = torch.empty((nu, K), dtype=torch.int64, device=dev)
+        launch(keys, out, None, None, None)
+        return out
+    out_idx = torch.empty((nu, K), dtype=torch.int32, device=dev)
+    out_val = torch.empty((nu, K), dtype=torch.float32, device=dev)
+    launch(keys, None, out_idx, out_val, hist)
+    return out_idx, out_val
+
+
+def deep_shard_keys(U, I_shard, users, K, head=HEAD_RAW, pop_shard=None, hist: Optional[HistoryCSR] = None, item_offset=0) -> torch.Tensor:
+    """One item shard's share of a deep ranking: packed keys int64 [Bu, K] of the shard's best min(K, n_items_local) unlisted items per user
+    (recommend_topk_deep, want="keys"), zeros behind them -- one list of deep_merge.  An empty shard returns all zeros."""
+    users = _need(users, torch.int32, "users")
+    K = int(K)
+    if not 1 <= K <= DEEP_MAX_K:
+        raise ValueError(f"deep lists need 1 <= K <= {DEEP_MAX_K}, got {K}")
+    nloc = I_shard.shape[0]
+    if nloc >= K:
+        return recommend_topk_deep(U, I_shard, users, K, head, pop_shard, hist, item_offset, want="keys")
+    out = torch.zeros((users.numel(), K), dtype=torch.int64, device=users.device)
+    if nloc > 0:
+        out[:, :nloc] = recommend_topk_deep(U, I_shard, users, nloc, head, pop_shard, hist, item_offset, want="keys")
+    return out
+
+
 def _metrics_deep(topk, tgt_indptr, tgt_indices, Ks, sums, ordered: bool):
     lib = _lib.load()
     topk = _need(topk, torch.int32, "topk")

@@ -84,7 +84,8 @@ def reference_block_first(eval_pos: int, n: int, device=None, block: int = 2048)
 
 def check_topk_max(args, topk_shard=None) -> int:
     """--topk_max (an extension; 50 = the reference's graph constant): the columns of every ranking.  Above ops.TOPK_K_V4 the lists come from
-    the deep path (ops.recommend_topk_deep), which has the raw and the popularity head on one GPU: everything else is refused here."""
+    the deep path (ops.recommend_topk_deep; across item shards ops.deep_shard_keys + ops.deep_merge, for a shard object whose `deep_lists`
+    is true), which has the raw and the popularity head: everything else is refused here."""
     k = getattr(args, "topk_max", None)
     k = 50 if k is None else int(k)
     if not 1 <= k <= ops.DEEP_MAX_K:
@@ -93,9 +94,10 @@ def check_topk_max(args, topk_shard=None) -> int:
         if getattr(args, "train", "normal") == "temp_pop":
             raise NotImplementedError("--topk_max %d: lists deeper than %d have no bias head (--train temp_pop ranks by s + alpha beta; the deep path "
                                       "ranks by the raw and the popularity head only)" % (k, ops.TOPK_K_V4))
-        if topk_shard is not None:
-            raise NotImplementedError("--topk_max %d: lists deeper than %d are not merged across item shards (pda_topk_merge takes at most %d columns): "
-                                      "evaluate on one GPU" % (k, ops.TOPK_K_V4, ops._lib.MAX_K))
+        if topk_shard is not None and getattr(topk_shard, "deep_lists", False) is not True:
+            raise NotImplementedError("--topk_max %d: lists deeper than %d are merged across item shards by pda_amd.dist.ItemShardedTopK only "
+                                      "(pda_topk_merge takes at most %d columns; this shard object has no deep_lists): evaluate on one GPU"
+                                      % (k, ops.TOPK_K_V4, ops._lib.MAX_K))
     return k
 
 

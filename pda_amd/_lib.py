@@ -1,5 +1,5 @@
-"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h and
-pda_hip_deep.h).
+"""ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
+pda_hip_deep.h and pda_hip_xquad.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -175,6 +175,14 @@ DEEP_SIGNATURES = {
     "pda_deep_merge": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_xquad.h (xQuAD re-ranking of candidate lists, `python -m pda_amd.xquad`)
+XQUAD_MAX_K = 64
+XQUAD_MAX_N = 1024
+XQUAD_BINARY, XQUAD_SMOOTH = 0, 1
+XQUAD_SIGNATURES = {
+    "pda_xquad_rerank": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -193,7 +201,7 @@ def load():
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
-            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()):
+            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1924,3 +1924,55 @@ def metrics_sums_deep(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Te
 def metrics_sums_deep_ordered(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pda_metrics_deep with a workspace: the ordered reduction of metrics_sums_ordered (the same bits run after run)."""
     return _metrics_deep(topk, tgt_indptr, tgt_indices, Ks, sums, ordered=True)
+
+
+# ---- xQuAD (include/pda_hip_xquad.h) ----------------------------------------------------------------------------------------------------
+XQUAD_MAX_K = _lib.XQUAD_MAX_K
+XQUAD_MAX_N = _lib.XQUAD_MAX_N
+XQUAD_VARIANTS = {"binary": _lib.XQUAD_BINARY, "smooth": _lib.XQUAD_SMOOTH}
+
+
+def xquad_rerank(cand_idx, cand_val, item_is_head, lam, K=50, variant="smooth", users=None, hist: Optional[HistoryCSR] = None):
+    """pda_xquad_rerank: xQuAD's greedy selection of K out of each row's N candidates -> (idx int32 [Bu, K], val float32 [Bu, K] = x at the pick).
+    cand_idx int32 [Bu, N], cand_val float32 [Bu, N]: what every recommend_* call returns (best first; -1 / -inf behind a short row).
+    item_is_head uint8 [n_items]: non-zero = short head.  hist: the users' profiles (by user id: `users` int32 [Bu] is needed; by block row:
+    row r of the CSR is row r of the candidates); None = no profile, which leaves the candidates' order."""
+    lib = _lib.load()
+    cand_idx = _need(cand_idx, torch.int32, "cand_idx")
+    cand_val = _need(cand_val, torch.float32, "cand_val")
+    item_is_head = _need(item_is_head, torch.uint8, "item_is_head")
+    users = _need(users, torch.int32, "users", optional=True)
+    if cand_idx.dim() != 2 or cand_idx.shape != cand_val.shape:
+        raise ValueError("cand_idx and cand_val must be [Bu, N], the same shape")
+    if item_is_head.dim() != 1 or item_is_head.numel() < 1:
+        raise ValueError("item_is_head holds one byte per item of the catalogue")
+    if cand_val.device != cand_idx.device or item_is_head.device != cand_idx.device:
+        raise ValueError("cand_idx, cand_val and item_is_head must live on one device")
+    nu, N = cand_idx.shape
+    K = int(K)
+    if nu < 1:
+        raise ValueError("empty user block")
+    if not 1 <= N <= XQUAD_MAX_N:
+        raise ValueError(f"xQuAD takes 1 .. {XQUAD_MAX_N} candidates per user, got {N}")
+    if not 1 <= K <= min(XQUAD_MAX_K, N):
+        raise ValueError(f"xQuAD needs 1 <= K <= min({XQUAD_MAX_K}, N = {N}), got {K}")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda must lie in [0, 1], got {lam}")
+    if variant not in XQUAD_VARIANTS:
+        raise ValueError(f"variant must be 'smooth' or 'binary', not {variant!r}")
+    if users is not None and users.numel() != nu:
+        raise ValueError("users holds one id per candidate row")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    if hist is not None:
+        if hist.mode == HIST_BY_USER_ID and users is None:
+            raise ValueError("a history by user id needs `users`")
+        if hist.mode == HIST_BY_BLOCK_ROW and hist.indptr.numel() < nu + 1:
+            raise ValueError("a history by block row holds one row per candidate row")
+    idx = torch.empty((nu, K), dtype=torch.int32, device=cand_idx.device)
+    val = torch.empty((nu, K), dtype=torch.float32, device=cand_idx.device)
+    check(lib.pda_xquad_rerank(ptr(cand_idx), ptr(cand_val), nu, N, ptr(item_is_head), item_is_head.numel(), ptr(users),
+                               ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
+                               lam, XQUAD_VARIANTS[variant], K, ptr(idx), ptr(val), stream_ptr()), "pda_xquad_rerank")
+    return idx, val

@@ -75,6 +75,10 @@ _EXTENSION_FLAGS = [
     ("eval_block", int, 262144, "users per score+top-K launch (the reference always uses 2048, MF/train_new_api.py:703); large blocks balance the early-terminating sweep: 92 M users/s at 65536, 109 M at 262144 (C3)"),
     ("topk_max", int, 50, "columns of every ranking (the reference's graph constant, MF/train_new_api.py:594: 50); 1 .. 1024.  Above 54 the lists come from the deep path (include/pda_hip_deep.h): --train normal | s_condition on one GPU"),
     ("export_out", str, "", "python -m pda_amd.export_topk: the .npz file that receives users, idx and val"),
+    ("xq_lambda", float, 0.5, "xQuAD (python -m pda_amd.xquad): weight lambda of the diversification term, 0 .. 1 (0 leaves the BPRMF ranking)"),
+    ("xq_candidates", int, 1000, "xQuAD: candidates per user the re-ranking selects from, max(Ks) .. 1024 (above 54 they come from the deep path)"),
+    ("xq_head_share", float, 0.8, "xQuAD: the short head is the most popular items that hold this share of the train interactions, strictly inside 0 .. 1"),
+    ("xq_variant", str, "smooth", "xQuAD: smooth | binary"),
 ]
 
 

@@ -32,6 +32,7 @@
 #include "pda_common.h"
 #include "pda_hip_det.h"
 #include "pda_plan_common.h"
+#include "pda_train_common.h"
 
 namespace {
 
@@ -253,21 +254,10 @@ constexpr bool kGrad = false;
 template <>
 constexpr bool kGrad<GradStepArgs> = true;
 
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-__device__ __forceinline__ void atomic_add4(float* p, f32x4 v) {
-    unsafeAtomicAdd(p + 0, v[0]);
-    unsafeAtomicAdd(p + 1, v[1]);
-    unsafeAtomicAdd(p + 2, v[2]);
-    unsafeAtomicAdd(p + 3, v[3]);
-}
-__device__ __forceinline__ uint32_t rne16(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
 __device__ __forceinline__ void store_bf16x4(uint16_t* p, f32x4 v) {
     uint2 o;
-    o.x = rne16(v[0]) | (rne16(v[1]) << 16);
-    o.y = rne16(v[2]) | (rne16(v[3]) << 16);
+    o.x = bf16_rne(v[0]) | (bf16_rne(v[1]) << 16);
+    o.y = bf16_rne(v[2]) | (bf16_rne(v[3]) << 16);
     *reinterpret_cast<uint2*>(p) = o;
 }
 
@@ -282,7 +272,6 @@ __global__ void __launch_bounds__(512) plan_triplets_kernel(Args a) {
     const int tid = threadIdx.x, g = tid / L, e = tid % L;
     const int t = (int)blockIdx.x * TPB + g;
     const bool active = t < a.B;
-    const bool with_pop = a.pos_pop != nullptr;
     const bool rejected = a.hdr[1] != 0;             // a user occurs twice: nothing is written, the loss becomes NaN
     float maxi = 0.f, sq = 0.f;
     int p = -1;
@@ -303,35 +292,10 @@ __global__ void __launch_bounds__(512) plan_triplets_kernel(Args a) {
                 nm = *reinterpret_cast<const f32x4*>(a.I + (size_t)n * D + 4 * e);
             }
         }
-        float ps = dot4(ue, pe), ns = dot4(ue, ne);
-        sq = dot4(ue, ue) + dot4(pe, pe) + dot4(ne, ne);
-#pragma unroll
-        for (int o = L / 2; o > 0; o >>= 1) {
-            ps += __shfl_xor(ps, o, 64);
-            ns += __shfl_xor(ns, o, 64);
-        }
-        float ap = 1.f, an = 1.f, psw = ps, nsw = ns;
-        if (with_pop) {
-            const float qp = a.pos_pop[t], qn = a.neg_pop[t];
-            const float ep = ps > 0.f ? 1.f : expf(ps);   // d(elu+1)/dx  [TF-ext EluGrad]
-            const float en = ns > 0.f ? 1.f : expf(ns);
-            psw = (ps > 0.f ? ps + 1.f : ep) * qp;        // (elu(ps)+1)*pos_pop   MF/model_api.py:107,109
-            nsw = (ns > 0.f ? ns + 1.f : en) * qn;        // :108,110
-            ap = qp * ep;
-            an = qn * en;
-        }
-        const float x = psw - nsw;
-        const float sg = 1.f / (1.f + expf(-x));
-        if (e == 0) maxi = logf(sg + 1e-10f);             // :112 / :702
-        const float gg = -a.inv_B * sg * (1.f - sg) / (sg + 1e-10f);
-        const float gp = gg * ap, gn = gg * an, c = a.reg_c, nlr = -a.lr;
+        float gp, gn;
         f32x4 due, dpe, dne;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            due[k] = gp * pe[k] - gn * ne[k] + c * ue[k];
-            dpe[k] = gp * ue[k] + c * pe[k];
-            dne[k] = -gn * ue[k] + c * ne[k];
-        }
+        bpr_triplet<D>(ue, pe, ne, a.pos_pop, a.neg_pop, t, a.inv_B, a.reg_c, e, maxi, sq, gp, gn, due, dpe, dne);
+        const float nlr = -a.lr;
         if constexpr (GRAD) {
             // the user row's gradient: users are distinct inside the batch, one plain store; no table row is written
             *reinterpret_cast<f32x4*>(a.gU + (size_t)u * D + 4 * e) = due;
@@ -378,26 +342,10 @@ __global__ void __launch_bounds__(512) plan_triplets_kernel(Args a) {
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        maxi += __shfl_xor(maxi, o, 64);
-        sq += __shfl_xor(sq, o, 64);
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) {
-        red[0][wave] = maxi;
-        red[1][wave] = sq;
-    }
-    __syncthreads();
+    block_loss_reduce(maxi, sq, red);
     if (tid == 0 && (a.loss_acc || a.exact)) {
-        float sm = 0.f, ss = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {
-            sm += red[0][w];
-            ss += red[1][w];
-        }
-        float mf = -sm * a.inv_B;                   // -mean(maxi)          :114 / :704
-        float rg = a.reg_c * 0.5f * ss;             // regs * l2 / batch    :117-120
+        float mf, rg;
+        block_loss_terms(red, a.inv_B, a.reg_c, mf, rg);
         if (rejected) mf = rg = __int_as_float(0x7FC00000);
         if (a.exact && blockIdx.x == 0 && a.strided) {          // (launch B's arrival counters of the very long segments)
             int* xc = reinterpret_cast<int*>(a.scratch + scratch_floats_base(a.B, D));

@@ -14,6 +14,7 @@
 #include "pda_common.h"
 #include "pda_hip_det.h"
 #include "pda_sample.h"
+#include "pda_train_common.h"
 
 namespace {
 
@@ -47,28 +48,13 @@ struct StepArgs {
     int tag = 0;
 };
 
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
-__device__ __forceinline__ void atomic_add4(float* p, f32x4 v) {
-    unsafeAtomicAdd(p + 0, v[0]);
-    unsafeAtomicAdd(p + 1, v[1]);
-    unsafeAtomicAdd(p + 2, v[2]);
-    unsafeAtomicAdd(p + 3, v[3]);
-}
-
 // 512 threads = 512/(D/4) triplets per block.  Positive items are popularity-skewed (the whole point of PDA): with Zipf
 // data one batch holds the hottest item ~170 times, and 170 x 64 float atomics on the same two cache lines serialise in
 // L2 (measured 25 us per 2048-triplet step).  The positives' contributions therefore go through LDS first: runs of
 // equal `pos` inside the block are summed by their first triplet and leave as ONE atomic per element.  Any batch order
 // is correct; a batch sorted by `pos` (pda_sort_triplets_by_pos, done by the device sampler) makes the runs long.
 // COH (pda_bpr_train_steps_f32): the batch and the table rows were written by OTHER workgroups of this launch -- by the sampler
-// and by the previous step's atomics, both at device scope -- and are read with device-scope loads (they miss the caches that
-// are not coherent across the XCDs), so that a grid barrier needs no cache invalidation.
-template <bool COH, typename T>
-__device__ __forceinline__ T in_load(const T* p) {
-    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
+// and by the previous step's atomics, both at device scope -- and are read with device-scope loads (in_load, pda_train_common.h).
 template <bool COH, bool BF>
 __device__ __forceinline__ f32x4 row_load4(const void* base, size_t idx) {
     if constexpr (COH && !BF) {
@@ -93,7 +79,6 @@ __device__ __forceinline__ void bpr_step_body(const StepArgs& a, const int bid) 
     const int tid = threadIdx.x, g = tid / L, e = tid % L;
     const int t = bid * TPB + g;
     const bool active = t < a.B;
-    const bool with_pop = a.pos_pop != nullptr;
     const bool scatter = a.mode == PDA_UPD_SGD_FUSED || a.mode == PDA_UPD_DENSE_GRAD || a.mode == PDA_UPD_SGD_ITEMS ||
                          a.mode == PDA_UPD_DENSE_ITEMS;
 
@@ -109,35 +94,9 @@ __device__ __forceinline__ void bpr_step_body(const StepArgs& a, const int bid) 
         const f32x4 ue = row_load4<COH, BF>(a.Ufwd, (size_t)u * D + 4 * e);
         const f32x4 pe = row_load4<COH, BF>(a.Ifwd, (size_t)p * D + 4 * e);
         const f32x4 ne = row_load4<COH, BF>(a.Ifwd, (size_t)n * D + 4 * e);
-        float ps = dot4(ue, pe), ns = dot4(ue, ne);
-        sq = dot4(ue, ue) + dot4(pe, pe) + dot4(ne, ne);
-#pragma unroll
-        for (int o = L / 2; o > 0; o >>= 1) {
-            ps += __shfl_xor(ps, o, 64);
-            ns += __shfl_xor(ns, o, 64);
-        }
-        float ap = 1.f, an = 1.f, psw = ps, nsw = ns;
-        if (with_pop) {
-            const float qp = in_load<COH>(&a.pos_pop[t]), qn = in_load<COH>(&a.neg_pop[t]);
-            const float ep = ps > 0.f ? 1.f : expf(ps);   // d(elu+1)/dx  [TF-ext EluGrad]
-            const float en = ns > 0.f ? 1.f : expf(ns);
-            psw = (ps > 0.f ? ps + 1.f : ep) * qp;        // (elu(ps)+1)*pos_pop   MF/model_api.py:107,109
-            nsw = (ns > 0.f ? ns + 1.f : en) * qn;        // :108,110
-            ap = qp * ep;
-            an = qn * en;
-        }
-        const float x = psw - nsw;
-        const float sg = 1.f / (1.f + expf(-x));
-        if (e == 0) maxi = logf(sg + 1e-10f);             // :112 / :702
-        const float gg = -a.inv_B * sg * (1.f - sg) / (sg + 1e-10f);
-        const float gp = gg * ap, gn = gg * an, c = a.reg_c;
+        float gp, gn;
         f32x4 due, dpe, dne;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            due[k] = gp * pe[k] - gn * ne[k] + c * ue[k];
-            dpe[k] = gp * ue[k] + c * pe[k];
-            dne[k] = -gn * ue[k] + c * ne[k];
-        }
+        bpr_triplet<D, COH>(ue, pe, ne, a.pos_pop, a.neg_pop, t, a.inv_B, a.reg_c, e, maxi, sq, gp, gn, due, dpe, dne);
         const f32x4 dpe_raw = dpe;
         if (a.mode == PDA_UPD_SGD_FUSED) {
             const float nlr = -a.lr;
@@ -198,31 +157,8 @@ __device__ __forceinline__ void bpr_step_body(const StepArgs& a, const int bid) 
         for (int k = g + 1; k < TPB && s_pos[k] == p; ++k) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
         atomic_add4(ptarget, sum);
     }
-    // block reduction of sum(log(.)) and sum of squares -> (loss, mf, reg)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        maxi += __shfl_xor(maxi, o, 64);
-        sq += __shfl_xor(sq, o, 64);
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) {
-        red[0][wave] = maxi;
-        red[1][wave] = sq;
-    }
-    __syncthreads();
-    if (tid == 0 && a.loss_acc) {
-        float sm = 0.f, ss = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {
-            sm += red[0][w];
-            ss += red[1][w];
-        }
-        const float mf = -sm * a.inv_B;             // -mean(maxi)          :114 / :704
-        const float rg = a.reg_c * 0.5f * ss;       // regs * l2 / batch    :117-120
-        unsafeAtomicAdd(a.loss_acc + 0, mf + rg);
-        unsafeAtomicAdd(a.loss_acc + 1, mf);
-        unsafeAtomicAdd(a.loss_acc + 2, rg);
-    }
+    block_loss_reduce(maxi, sq, red);
+    if (tid == 0 && a.loss_acc) block_loss_add(red, a.inv_B, a.reg_c, a.loss_acc);
 }
 
 template <int D, bool BF>
@@ -482,12 +418,8 @@ __global__ void __launch_bounds__(256) adam_dense_sweep_kernel(float* __restrict
         f32x4 xx = reinterpret_cast<f32x4*>(var)[i];
         bool touched = false;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            touched |= gg[k] != 0.f;
-            mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-            vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-            xx[k] = xx[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
-        }
+        for (int k = 0; k < 4; ++k) touched |= gg[k] != 0.f;
+        adam_elem(xx, mm, vv, gg, lr_t, b1, b2, eps);
         reinterpret_cast<f32x4*>(m)[i] = mm;
         reinterpret_cast<f32x4*>(v)[i] = vv;
         reinterpret_cast<f32x4*>(var)[i] = xx;
@@ -495,19 +427,15 @@ __global__ void __launch_bounds__(256) adam_dense_sweep_kernel(float* __restrict
     }
 }
 
-// Both tables of the model in one launch (the same arithmetic element by element): workgroups [0, blocks_a) sweep the first
-// table, the rest the second -- one launch and one tail less per training step.
+// Both tables of the model in one launch (sweep_table, pda_train_common.h) -- one launch and one tail less per training step.
 __global__ void __launch_bounds__(256) adam_dense_sweep2_kernel(float* __restrict__ var_a, float* __restrict__ m_a, float* __restrict__ v_a,
                                                                 float* __restrict__ g_a, size_t n4_a, float* __restrict__ var_b,
                                                                 float* __restrict__ m_b, float* __restrict__ v_b, float* __restrict__ g_b,
                                                                 size_t n4_b, unsigned blocks_a, float lr_t, float b1, float b2, float eps) {
     const bool first = blockIdx.x < blocks_a;
-    float* var = first ? var_a : var_b;
-    float* m = first ? m_a : m_b;
-    float* v = first ? v_a : v_b;
-    float* g = first ? g_a : g_b;
-    const size_t n4 = first ? n4_a : n4_b;
-    const size_t blk = first ? blockIdx.x : blockIdx.x - blocks_a, nblk = first ? blocks_a : gridDim.x - blocks_a;
+    const SweepTable tab = sweep_table(first, var_a, m_a, v_a, g_a, n4_a, var_b, m_b, v_b, g_b, n4_b);
+    float *const var = tab.var, *const m = tab.m, *const v = tab.v, *const g = tab.g;
+    const size_t n4 = tab.n4, blk = first ? blockIdx.x : blockIdx.x - blocks_a, nblk = first ? blocks_a : gridDim.x - blocks_a;
     const size_t stride = nblk * blockDim.x;
     for (size_t i = blk * blockDim.x + threadIdx.x; i < n4; i += stride) {
         f32x4 gg = reinterpret_cast<f32x4*>(g)[i];
@@ -516,12 +444,8 @@ __global__ void __launch_bounds__(256) adam_dense_sweep2_kernel(float* __restric
         f32x4 xx = reinterpret_cast<f32x4*>(var)[i];
         bool touched = false;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            touched |= gg[k] != 0.f;
-            mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-            vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-            xx[k] = xx[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
-        }
+        for (int k = 0; k < 4; ++k) touched |= gg[k] != 0.f;
+        adam_elem(xx, mm, vv, gg, lr_t, b1, b2, eps);
         reinterpret_cast<f32x4*>(m)[i] = mm;
         reinterpret_cast<f32x4*>(v)[i] = vv;
         reinterpret_cast<f32x4*>(var)[i] = xx;
@@ -532,8 +456,8 @@ __global__ void __launch_bounds__(256) adam_dense_sweep2_kernel(float* __restric
 
 // ---- the dense-decay sweep as SIX streams (round 5): a step's gradient is zero on all but the batch's rows, so the dense gradient tables need not
 // be read at all -- one bit per row says "touched by this step" (adam_mark_rows_kernel: the batch's users / positives / negatives), the sweep
-// reads and clears g only where it is set (and its bits behind itself).  Same arithmetic as adam_dense_sweep2_kernel, operation for operation
-// (an untouched row computes with g = 0): bit-identical tables.  4.3 -> 3.7 GB per step on config 3's tables.
+// reads and clears g only where it is set (and its bits behind itself).  An untouched row computes adam_elem with g = 0: the tables of
+// adam_dense_sweep2_kernel, bit for bit.  4.3 -> 3.7 GB per step on config 3's tables.
 __global__ void __launch_bounds__(256) adam_mark_rows_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ pos, const int32_t* __restrict__ neg,
                                                              int B, uint32_t* __restrict__ touched_u, uint32_t* __restrict__ touched_i) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -549,14 +473,11 @@ __global__ void __launch_bounds__(256) adam_dense_sweep3_kernel(float* __restric
                                                                 float* __restrict__ g_b, size_t n4_b, int sh_b, const uint32_t* __restrict__ t_b,
                                                                 unsigned blocks_a, float lr_t, float b1, float b2, float eps) {
     const bool first = blockIdx.x < blocks_a;
-    float* var = first ? var_a : var_b;
-    float* m = first ? m_a : m_b;
-    float* v = first ? v_a : v_b;
-    float* g = first ? g_a : g_b;
+    const SweepTable tab = sweep_table(first, var_a, m_a, v_a, g_a, n4_a, var_b, m_b, v_b, g_b, n4_b);
+    float *const var = tab.var, *const m = tab.m, *const v = tab.v, *const g = tab.g;
     const uint32_t* tb = first ? t_a : t_b;
     const int sh = first ? sh_a : sh_b;                       // log2 of the row's 16-byte chunks
-    const size_t n4 = first ? n4_a : n4_b;
-    const size_t blk = first ? blockIdx.x : blockIdx.x - blocks_a, nblk = first ? blocks_a : gridDim.x - blocks_a;
+    const size_t n4 = tab.n4, blk = first ? blockIdx.x : blockIdx.x - blocks_a, nblk = first ? blocks_a : gridDim.x - blocks_a;
     const size_t stride = nblk * blockDim.x;
     auto ld = [&](float* p, size_t i) __attribute__((always_inline)) -> f32x4 {
 #ifdef PDA_ADAM_PLAIN_STREAMS
@@ -599,12 +520,7 @@ __global__ void __launch_bounds__(256) adam_dense_sweep3_kernel(float* __restric
         for (int q = 0; q < UN; ++q) {
             const size_t i = i0 + q * stride;
             if (i >= n4) break;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                mm[q][k] = b1 * mm[q][k] + (1.f - b1) * gg[q][k];
-                vv[q][k] = b2 * vv[q][k] + (1.f - b2) * gg[q][k] * gg[q][k];
-                xx[q][k] = xx[q][k] - lr_t * mm[q][k] / (sqrtf(vv[q][k]) + eps);
-            }
+            adam_elem(xx[q], mm[q], vv[q], gg[q], lr_t, b1, b2, eps);
             st(m, i, mm[q]);
             st(v, i, vv[q]);
             st(var, i, xx[q]);
@@ -616,8 +532,7 @@ __global__ void __launch_bounds__(256) adam_dense_sweep3_kernel(float* __restric
 // ---- round 6: the sweep keyed by per-row step TAGS instead of bitmaps (tag[row] == step  <=>  the step's batch touched the row; written by
 // the step kernel itself, never cleared: no mark launch, no memsets -- five launches per reference step become two), and the cache policy by
 // working set: NT = false reads and writes x, m, v with plain accesses, so tables that fit the 256 MiB Infinity Cache (C1 / C2: 54 MB)
-// are swept out of it instead of out of HBM; NT = true is adam_dense_sweep3_kernel's streaming policy for the big tables.  Same
-// arithmetic as adam_dense_sweep2_kernel / 3, operation for operation: bit-identical tables.
+// are swept out of it instead of out of HBM; NT = true is adam_dense_sweep3_kernel's streaming policy for the big tables.
 // Guard = const int* (pda_adam_step_plan_f32: the sweep behind the planned gradient): a batch its plan rejects (*rejected != 0: a user occurs twice)
 // leaves tables and moments as they are -- decided on the device, uniformly over the grid, no host synchronisation.  The instances without the
 // extra argument are the kernels of pda_adam_step_f32 / pda_adam_dense_sweep4_f32, argument block and instructions unchanged.
@@ -632,13 +547,10 @@ __global__ void __launch_bounds__(256) adam_dense_sweep4_kernel(float* __restric
                                                                 Guard... rejected) {
     if (sweep_rejected(rejected...)) return;
     const bool first = blockIdx.x < blocks_a;
-    float* var = first ? var_a : var_b;
-    float* m = first ? m_a : m_b;
-    float* v = first ? v_a : v_b;
-    float* g = first ? g_a : g_b;
+    const SweepTable tab = sweep_table(first, var_a, m_a, v_a, g_a, n4_a, var_b, m_b, v_b, g_b, n4_b);
+    float *const var = tab.var, *const m = tab.m, *const v = tab.v, *const g = tab.g;
     const int32_t* tg = first ? t_a : t_b;
-    const size_t n4 = first ? n4_a : n4_b;
-    const size_t blk = first ? blockIdx.x : blockIdx.x - blocks_a, nblk = first ? blocks_a : gridDim.x - blocks_a;
+    const size_t n4 = tab.n4, blk = first ? blockIdx.x : blockIdx.x - blocks_a, nblk = first ? blocks_a : gridDim.x - blocks_a;
     const size_t stride = nblk * blockDim.x;
     auto ld = [&](float* p, size_t i) __attribute__((always_inline)) -> f32x4 {
         if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
@@ -670,12 +582,7 @@ __global__ void __launch_bounds__(256) adam_dense_sweep4_kernel(float* __restric
         for (int q = 0; q < UN; ++q) {
             const size_t i = i0 + q * stride;
             if (i >= n4) break;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                mm[q][k] = b1 * mm[q][k] + (1.f - b1) * gg[q][k];
-                vv[q][k] = b2 * vv[q][k] + (1.f - b2) * gg[q][k] * gg[q][k];
-                xx[q][k] = xx[q][k] - lr_t * mm[q][k] / (sqrtf(vv[q][k]) + eps);
-            }
+            adam_elem(xx[q], mm[q], vv[q], gg[q], lr_t, b1, b2, eps);
             st(m, i, mm[q]);
             st(v, i, vv[q]);
             st(var, i, xx[q]);
@@ -693,12 +600,7 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float* var, float* m, fl
     const size_t off = (size_t)rows[r] * D + 4 * e;
     f32x4 gg = *reinterpret_cast<f32x4*>(g + off), mm = *reinterpret_cast<f32x4*>(m + off);
     f32x4 vv = *reinterpret_cast<f32x4*>(v + off), xx = *reinterpret_cast<f32x4*>(var + off);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-        vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-        xx[k] = xx[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
-    }
+    adam_elem(xx, mm, vv, gg, lr_t, b1, b2, eps);
     *reinterpret_cast<f32x4*>(m + off) = mm;
     *reinterpret_cast<f32x4*>(v + off) = vv;
     *reinterpret_cast<f32x4*>(var + off) = xx;
@@ -707,8 +609,8 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float* var, float* m, fl
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Exact lazy dense-decay Adam.  A row whose gradient is zero at step k only decays: m <- b1 m, v <- b2 v,
-// x <- x - lr_k m / (sqrt(v) + eps) -- a function of the row and of k alone (the arithmetic of adam_dense_sweep_kernel with
-// g = 0, operation for operation).  So a row may skip its idle steps and replay them in registers when it is next needed:
+// x <- x - lr_k m / (sqrt(v) + eps) -- a function of the row and of k alone (adam_elem with the literal g = 0: what the sweeps
+// compute on such a row).  So a row may skip its idle steps and replay them in registers when it is next needed:
 // last[row] = the step the row is current for, lr_tab[k] = the bias-corrected rate of step k.  Per training step t:
 //   phase 0  every row of the batch is brought to step t - 1 (the forward pass of step t reads it);
 //   (pda_bpr_step_f32, PDA_UPD_DENSE_GRAD: gradients into the dense accumulators)
@@ -743,24 +645,14 @@ __device__ __forceinline__ void adam_replay(f32x4& xx, f32x4& mm, f32x4& vv, int
     int k = from;
     for (; k <= upto; ++k) {
         const float lr_k = lr_tab[k];
+        const f32x4 xo = xx;
+        adam_elem(xx, mm, vv, 0.f, lr_k, b1, b2, eps);
         bool moved = false;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mm[q] = b1 * mm[q] + (1.f - b1) * 0.f;
-            vv[q] = b2 * vv[q] + (1.f - b2) * 0.f * 0.f;
-            const float xn = xx[q] - lr_k * mm[q] / (sqrtf(vv[q]) + eps);
-            moved |= xn != xx[q];
-            xx[q] = xn;
-        }
+        for (int q = 0; q < 4; ++q) moved |= xx[q] != xo[q];
         if (!moved) { ++k; break; }
     }
-    for (; k <= upto; ++k) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mm[q] = b1 * mm[q] + (1.f - b1) * 0.f;
-            vv[q] = b2 * vv[q] + (1.f - b2) * 0.f * 0.f;
-        }
-    }
+    for (; k <= upto; ++k) adam_moments(mm, vv, 0.f, b1, b2);
 }
 
 // The same catch-up to the north_star's tolerance instead of bit for bit (round 3).  What the exact replay pays per element and
@@ -827,12 +719,7 @@ __global__ void __launch_bounds__(256) adam_lazy_kernel(LazyAdamArgs a, FastCons
     if (a.phase == 1) {
         const f32x4 gg = *reinterpret_cast<f32x4*>(g + off);
         const float lr_t = a.lr_tab[a.t];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mm[q] = a.b1 * mm[q] + (1.f - a.b1) * gg[q];
-            vv[q] = a.b2 * vv[q] + (1.f - a.b2) * gg[q] * gg[q];
-            xx[q] = xx[q] - lr_t * mm[q] / (sqrtf(vv[q]) + a.eps);
-        }
+        adam_elem(xx, mm, vv, gg, lr_t, a.b1, a.b2, a.eps);
         *reinterpret_cast<f32x4*>(g + off) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     *reinterpret_cast<f32x4*>(m + off) = mm;
@@ -881,15 +768,11 @@ __global__ void __launch_bounds__(256) refresh_rows_kernel(const float* __restri
     const size_t r = rows ? (size_t)(rows[i / d8] - row_offset) : i / d8;
     const size_t off = r * (8 * (size_t)d8) + 8 * (i % d8);
     const f32x4 a = *reinterpret_cast<const f32x4*>(master + off), b = *reinterpret_cast<const f32x4*>(master + off + 4);
-    auto rne = [](float x) -> uint32_t {
-        const uint32_t u = __float_as_uint(x);
-        return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-    };
     uint4 o;
-    o.x = rne(a[0]) | (rne(a[1]) << 16);
-    o.y = rne(a[2]) | (rne(a[3]) << 16);
-    o.z = rne(b[0]) | (rne(b[1]) << 16);
-    o.w = rne(b[2]) | (rne(b[3]) << 16);
+    o.x = bf16_rne(a[0]) | (bf16_rne(a[1]) << 16);
+    o.y = bf16_rne(a[2]) | (bf16_rne(a[3]) << 16);
+    o.z = bf16_rne(b[0]) | (bf16_rne(b[1]) << 16);
+    o.w = bf16_rne(b[2]) | (bf16_rne(b[3]) << 16);
     *reinterpret_cast<uint4*>(shadow + off) = o;
 }
 

@@ -49,6 +49,12 @@ __device__ __forceinline__ f32x4 pda_load4(const void* base, size_t idx) {
     }
 }
 
+// fp32 -> bf16 bits, round to nearest even (x finite)
+__device__ __forceinline__ uint32_t bf16_rne(float x) {
+    const uint32_t u = __float_as_uint(x);
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
 // Orders LDS traffic between lanes of ONE wave (no instruction: compiler-level only; the LDS
 // pipeline already executes a wave's DS ops in order).
 __device__ __forceinline__ void pda_wave_sync() {

@@ -12,6 +12,7 @@
 #include <cstring>
 #include "pda_common.h"
 #include "pda_topk_common.h"
+#include "pda_train_common.h"
 #include "pda_hip_temp_pop.h"
 
 namespace {
@@ -38,15 +39,6 @@ struct TPStepArgs {
     float inv_B;
     float reg_c;   // regs / reg_div
 };
-
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
-__device__ __forceinline__ void atomic_add4(float* p, f32x4 v) {
-    unsafeAtomicAdd(p + 0, v[0]);
-    unsafeAtomicAdd(p + 1, v[1]);
-    unsafeAtomicAdd(p + 2, v[2]);
-    unsafeAtomicAdd(p + 3, v[3]);
-}
 
 template <int D>
 __global__ void __launch_bounds__(512) temp_pop_step_kernel(TPStepArgs a) {
@@ -76,29 +68,16 @@ __global__ void __launch_bounds__(512) temp_pop_step_kernel(TPStepArgs a) {
         // quirk 1: user_temp_bias_all is [B, 1] and gather_nd reads it at (raw, temp) -- in range only for temp == 0; TF's GPU kernel returns 0
         // out of range and drops the gradient (MF/model_api.py:342-343)
         const float bt = ts == 0 ? a.bu[u] : 0.f;
-        float ps = dot4(ue, pe), ns = dot4(ue, ne);
-        sq = dot4(ue, ue) + dot4(pe, pe) + dot4(ne, ne);
-#pragma unroll
-        for (int o = L / 2; o > 0; o >>= 1) {
-            ps += __shfl_xor(ps, o, 64);
-            ns += __shfl_xor(ns, o, 64);
-        }
+        float ps, ns;
+        triplet_dots<D>(ue, pe, ne, ps, ns);
+        sq = triplet_sq(ue, pe, ne);
         // TF's op order (:355-364): ub = b~ + 1, pb = init + temp, s = ub * pb + preference
         const float ub = bt + 1.0f;
         const float pb = cpT + cpt, nb = cnT + cnt;
         const float sp = ub * pb + ps, sn = ub * nb + ns;
-        const float x = sp - sn;
-        const float sg = 1.f / (1.f + expf(-x));
-        if (e == 0) maxi = logf(sg + 1e-10f);                     // :367
-        const float gg = -a.inv_B * sg * (1.f - sg) / (sg + 1e-10f);
-        const float c = a.reg_c;
+        const float gg = bpr_dloss_dx(sp - sn, a.inv_B, e, maxi);  // :367
         f32x4 due, dpe, dne;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            due[k] = gg * pe[k] - gg * ne[k] + c * ue[k];
-            dpe[k] = gg * ue[k] + c * pe[k];
-            dne[k] = -gg * ue[k] + c * ne[k];
-        }
+        triplet_row_grads(ue, pe, ne, gg, gg, a.reg_c, due, dpe, dne);
         atomic_add4(a.gU + (size_t)u * D + 4 * e, due);
         atomic_add4(a.gI + (size_t)n * D + 4 * e, dne);
         *reinterpret_cast<f32x4*>(s_dpe + g * D + 4 * e) = dpe;
@@ -132,38 +111,11 @@ __global__ void __launch_bounds__(512) temp_pop_step_kernel(TPStepArgs a) {
             if (e == 0) unsafeAtomicAdd(a.gC + (size_t)p * W + a.T, gsum);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        maxi += __shfl_xor(maxi, o, 64);
-        sq += __shfl_xor(sq, o, 64);
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) {
-        red[0][wave] = maxi;
-        red[1][wave] = sq;
-    }
-    __syncthreads();
-    if (tid == 0 && a.loss_acc) {
-        float sm = 0.f, ss = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {
-            sm += red[0][w];
-            ss += red[1][w];
-        }
-        const float mf = -sm * a.inv_B;          // :368
-        const float rg = a.reg_c * 0.5f * ss;    // regs * (l2 of the three embedding rows) / batch_size  :370-373
-        unsafeAtomicAdd(a.loss_acc + 0, mf + rg);
-        unsafeAtomicAdd(a.loss_acc + 1, mf);
-        unsafeAtomicAdd(a.loss_acc + 2, rg);
-    }
+    block_loss_reduce(maxi, sq, red);
+    if (tid == 0 && a.loss_acc) block_loss_add(red, a.inv_B, a.reg_c, a.loss_acc);     // (l2 of the three EMBEDDING rows: the biases take none, :370-373)
 }
 
-// TF-1.14 dense-decay Adam, element for element the arithmetic of adam_dense_sweep_kernel (pda_bpr_step.hip); g is read only on tagged rows.
-__device__ __forceinline__ void adam_elem(float& x, float& m, float& v, float g, float lr_t, float b1, float b2, float eps) {
-    m = b1 * m + (1.f - b1) * g;
-    v = b2 * v + (1.f - b2) * g * g;
-    x = x - lr_t * m / (sqrtf(v) + eps);
-}
+// TF-1.14 dense-decay Adam over the four tables (adam_elem, pda_train_common.h); g is read only on tagged rows.
 
 struct TPSweepArgs {
     float* x[4];
@@ -196,14 +148,7 @@ __global__ void __launch_bounds__(256) temp_pop_sweep_kernel(TPSweepArgs a) {
             f32x4 gg = {0.f, 0.f, 0.f, 0.f};
             if (touched) gg = reinterpret_cast<const f32x4*>(G)[i];
             f32x4 xx = reinterpret_cast<f32x4*>(X)[i], mm = reinterpret_cast<f32x4*>(M)[i], vv = reinterpret_cast<f32x4*>(V)[i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float x1 = xx[k], m1 = mm[k], v1 = vv[k];
-                adam_elem(x1, m1, v1, gg[k], a.lr_t, a.b1, a.b2, a.eps);
-                xx[k] = x1;
-                mm[k] = m1;
-                vv[k] = v1;
-            }
+            adam_elem(xx, mm, vv, gg, a.lr_t, a.b1, a.b2, a.eps);
             reinterpret_cast<f32x4*>(M)[i] = mm;
             reinterpret_cast<f32x4*>(V)[i] = vv;
             reinterpret_cast<f32x4*>(X)[i] = xx;

@@ -59,10 +59,6 @@ struct ScoreArgs2 {
     const float* alpha = nullptr;   // PDA_HEAD_BIAS (temp_pop, natural order only): alpha per block row; beta is behind a.pop
 };
 
-__device__ __forceinline__ uint32_t bf16_rne(float x) {
-    uint32_t u = __float_as_uint(x);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
 // x = t1 + t2 + t3 exactly, every piece a bf16 (truncation split; x finite).  Returned as bf16 bit patterns.
 __device__ __forceinline__ void bf16_split3(float x, uint32_t& t1, uint32_t& t2, uint32_t& t3) {
     const uint32_t b1 = __float_as_uint(x) & 0xFFFF0000u;

@@ -1,0 +1,150 @@
+// The arithmetic every training kernel shares (pda_bpr_step.hip, pda_bpr_plan.hip, pda_temp_pop.hip): the triplet forward / backward of the
+// reference model, the block reduction of the loss, and the TF-1.14 Adam element update.  One definition each: the bit-identity of the sweeps,
+// the lazy replay, --deterministic and the checkpoints (tests/test_gpu_bpr_step.py, test_gpu_deterministic.py, test_gpu_temp_pop.py) holds
+// because every kernel compiles THESE expressions, in this order, under -ffp-contract=off.
+#pragma once
+#include "pda_common.h"
+
+__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
+
+__device__ __forceinline__ void atomic_add4(float* p, f32x4 v) {
+    unsafeAtomicAdd(p + 0, v[0]);
+    unsafeAtomicAdd(p + 1, v[1]);
+    unsafeAtomicAdd(p + 2, v[2]);
+    unsafeAtomicAdd(p + 3, v[3]);
+}
+
+// COH (pda_bpr_train_steps_f32): the value was written by ANOTHER workgroup of this launch at device scope and is read with a device-scope
+// load (it misses the caches that are not coherent across the XCDs), so that a grid barrier needs no cache invalidation.
+template <bool COH, typename T>
+__device__ __forceinline__ T in_load(const T* p) {
+    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *p;
+}
+
+// ---- the triplet: d/4 lanes, each with one float4 of the three gathered rows ------------------------------------------------------------------
+// ps = <u, p>, ns = <u, n>, summed over the D/4 lanes of the group: every lane holds them
+template <int D>
+__device__ __forceinline__ void triplet_dots(f32x4 ue, f32x4 pe, f32x4 ne, float& ps, float& ns) {
+    ps = dot4(ue, pe), ns = dot4(ue, ne);
+#pragma unroll
+    for (int o = D / 8; o > 0; o >>= 1) {
+        ps += __shfl_xor(ps, o, 64);
+        ns += __shfl_xor(ns, o, 64);
+    }
+}
+// this lane's share of |u|^2 + |p|^2 + |n|^2 (the L2 term of the loss)
+__device__ __forceinline__ float triplet_sq(f32x4 ue, f32x4 pe, f32x4 ne) { return dot4(ue, ue) + dot4(pe, pe) + dot4(ne, ne); }
+// x = positive score - negative score  ->  d(mean loss) / dx; lane 0 of the group (e == 0) takes the triplet's log-sigmoid into maxi
+__device__ __forceinline__ float bpr_dloss_dx(float x, float inv_B, int e, float& maxi) {
+    const float sg = 1.f / (1.f + expf(-x));
+    if (e == 0) maxi = logf(sg + 1e-10f);                 // MF/model_api.py:112 / :367 / :702
+    return -inv_B * sg * (1.f - sg) / (sg + 1e-10f);
+}
+// the rows' gradients with the L2 term (c = regs / reg_div): gp = d loss / d(positive score), gn = -d loss / d(negative score)
+__device__ __forceinline__ void triplet_row_grads(f32x4 ue, f32x4 pe, f32x4 ne, float gp, float gn, float c, f32x4& due, f32x4& dpe, f32x4& dne) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        due[k] = gp * pe[k] - gn * ne[k] + c * ue[k];
+        dpe[k] = gp * ue[k] + c * pe[k];
+        dne[k] = -gn * ue[k] + c * ne[k];
+    }
+}
+
+// PD / PDA and plain BPR-MF (MF/model_api.py:102-121 / :695-705): scores (ELU + 1) * pop where pos_pop is given (pos_pop[t], neg_pop[t]: read
+// only then), the raw dots otherwise.
+template <int D, bool COH = false>
+__device__ __forceinline__ void bpr_triplet(f32x4 ue, f32x4 pe, f32x4 ne, const float* pos_pop, const float* neg_pop, int t, float inv_B, float reg_c,
+                                            int e, float& maxi, float& sq, float& gp, float& gn, f32x4& due, f32x4& dpe, f32x4& dne) {
+    float ps, ns;
+    triplet_dots<D>(ue, pe, ne, ps, ns);
+    float ap = 1.f, an = 1.f, psw = ps, nsw = ns;
+    if (pos_pop != nullptr) {
+        const float qp = in_load<COH>(&pos_pop[t]), qn = in_load<COH>(&neg_pop[t]);
+        const float ep = ps > 0.f ? 1.f : expf(ps);   // d(elu+1)/dx  [TF-ext EluGrad]
+        const float en = ns > 0.f ? 1.f : expf(ns);
+        psw = (ps > 0.f ? ps + 1.f : ep) * qp;        // (elu(ps)+1)*pos_pop   MF/model_api.py:107,109
+        nsw = (ns > 0.f ? ns + 1.f : en) * qn;        // :108,110
+        ap = qp * ep;
+        an = qn * en;
+    }
+    const float gg = bpr_dloss_dx(psw - nsw, inv_B, e, maxi);
+    sq = triplet_sq(ue, pe, ne);      // (behind the score chain: nothing waits for it before the block reduction)
+    gp = gg * ap, gn = gg * an;
+    triplet_row_grads(ue, pe, ne, gp, gn, reg_c, due, dpe, dne);
+}
+
+// ---- block reduction of sum(log(.)) and of the squared norms (512 threads = 8 waves; red: a __shared__ float[2][8] of the calling kernel) -----
+__device__ __forceinline__ void block_loss_reduce(float maxi, float sq, float (&red)[2][8]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        maxi += __shfl_xor(maxi, o, 64);
+        sq += __shfl_xor(sq, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = maxi;
+        red[1][wave] = sq;
+    }
+    __syncthreads();
+}
+// (one thread, behind block_loss_reduce) the block's share of the two loss terms
+__device__ __forceinline__ void block_loss_terms(const float (&red)[2][8], float inv_B, float reg_c, float& mf, float& rg) {
+    float sm = 0.f, ss = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        sm += red[0][w];
+        ss += red[1][w];
+    }
+    mf = -sm * inv_B;               // -mean(maxi)          MF/model_api.py:114 / :368 / :704
+    rg = reg_c * 0.5f * ss;         // regs * l2 / batch    :117-120 / :370-373
+}
+// (one thread, behind block_loss_reduce) loss_acc[0..2] += (loss, mf, reg) of this block: three atomics per workgroup
+__device__ __forceinline__ void block_loss_add(const float (&red)[2][8], float inv_B, float reg_c, float* loss_acc) {
+    float mf, rg;
+    block_loss_terms(red, inv_B, reg_c, mf, rg);
+    unsafeAtomicAdd(loss_acc + 0, mf + rg);
+    unsafeAtomicAdd(loss_acc + 1, mf);
+    unsafeAtomicAdd(loss_acc + 2, rg);
+}
+
+// ---- TF-1.14 Adam with dense decay, one element: lr_t is the bias-corrected rate of the step.  A row the step did not touch takes g = 0 (the
+// literal, through these very expressions: that is what makes the sweeps and the exact replay bit-identical) ----------------------------------
+__device__ __forceinline__ void adam_moments(float& m, float& v, float g, float b1, float b2) {
+    m = b1 * m + (1.f - b1) * g;
+    v = b2 * v + (1.f - b2) * g * g;
+}
+__device__ __forceinline__ void adam_elem(float& x, float& m, float& v, float g, float lr_t, float b1, float b2, float eps) {
+    adam_moments(m, v, g, b1, b2);
+    x = x - lr_t * m / (sqrtf(v) + eps);
+}
+// (the four elements of a chunk; a vector element cannot bind to a reference, hence the copies)
+__device__ __forceinline__ void adam_moments(f32x4& mm, f32x4& vv, f32x4 gg, float b1, float b2) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float m = mm[k], v = vv[k];
+        adam_moments(m, v, gg[k], b1, b2);
+        mm[k] = m;
+        vv[k] = v;
+    }
+}
+__device__ __forceinline__ void adam_elem(f32x4& xx, f32x4& mm, f32x4& vv, f32x4 gg, float lr_t, float b1, float b2, float eps) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float x = xx[k], m = mm[k], v = vv[k];
+        adam_elem(x, m, v, gg[k], lr_t, b1, b2, eps);
+        xx[k] = x;
+        mm[k] = m;
+        vv[k] = v;
+    }
+}
+
+// ---- the sweeps over both tables of the model in one launch: workgroups [0, blocks_a) take the first table, the rest the second ---------------
+struct SweepTable {
+    float *var, *m, *v, *g;
+    size_t n4;              // 16-byte chunks of the table
+};
+__device__ __forceinline__ SweepTable sweep_table(bool first, float* var_a, float* m_a, float* v_a, float* g_a, size_t n4_a, float* var_b, float* m_b,
+                                                  float* v_b, float* g_b, size_t n4_b) {
+    return SweepTable{first ? var_a : var_b, first ? m_a : m_b, first ? v_a : v_b, first ? g_a : g_b, first ? n4_a : n4_b};
+}

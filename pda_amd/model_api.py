@@ -10,9 +10,15 @@ so the reference's loop `sess.run([model.Recommender.opt, model.Recommender.loss
 the direct API is `train_step(users, pos, neg[, pos_pop, neg_pop]) -> float32[3] device tensor`.
 
 Optimisers (`args.optimizer`):
-    adam       TF-1.14 AdamOptimizer semantics: m, v decayed and EVERY row updated each step [TF-ext]
-               (= pda_bpr_step_f32(DENSE_GRAD) + pda_adam_dense_sweep_f32 on both tables).  Reference-faithful.
-    lazy_adam  the same update restricted to the rows touched by the batch (declared deviation).
+    adam       TF-1.14 AdamOptimizer semantics: m, v decayed and EVERY row updated each step [TF-ext].  Reference-faithful.  Small tables
+               (up to ADAM_SWEEP_MAX_BYTES): pda_adam_step_f32 -- the step kernel sums the gradients and tags the batch's rows, the tagged
+               sweep updates both tables; two launches (pda_adam_step_plan_f32 under --deterministic: three).  Larger tables, or
+               --adam_sweep replay: the same arithmetic without the sweep, bit for bit -- pda_adam_lazy_f32 phase 0 (the batch's rows
+               replay their idle steps), the gradient, pda_adam_lazy_f32 phase 1.
+    lazy_adam  the same update restricted to the rows touched by the batch (declared deviation): the gradient, then pda_adam_rows_f32
+               on the unique rows of each table.
+               The gradient is pda_bpr_step_f32(DENSE_GRAD), pda_bpr_grad_plan_f32 under --deterministic, pda_bpr_step_bf16 on bf16 tables
+               (_MFBase._adam_step is the one place that spells these steps out).
     sgd        plain mini-batch SGD, exact: gradients of the whole batch against the unchanged tables, then one scatter
                (pda_bpr_step_f32(PDA_UPD_NONE) + pda_sgd_apply_f32; declared deviation from MF/model_api.py:83 = Adam).
     sgd_fused  the north_star's fused in-kernel scatter update, ONE launch per step: asynchronous inside the launch (a row
@@ -174,43 +180,6 @@ class _MFBase:
         t = self.tables16 if self.tables16 is not None else self.weights
         return t["user_embedding"], t["item_embedding"]
 
-    def _train_step_bf16(self, users, pos, neg, pos_pop, neg_pop):
-        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
-        U16, I16 = self.tables16["user_embedding"], self.tables16["item_embedding"]
-        if self.optimizer in ("sgd", "sgd_fused"):      # (bf16 forward reads the shadow tables: no in-launch race either way)
-            ops.bpr_step_bf16(U16, I16, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size, lr=self.lr,
-                              mode=ops.UPD_SGD_FUSED, U_master=U, I_master=I, loss_acc=self._loss)
-            return self._loss
-        st = self._opt_state()
-        self._t += 1
-        lr_t = ops.adam_lr_t(self.lr, self._t)
-        lazy = self.optimizer == "adam" and self.adam_exact_lazy
-        if lazy:
-            lz = self._lazy_state()
-            ops.adam_lazy(0, lz, U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
-            for rows in (users,):
-                ops.refresh_rows_bf16(U, U16, rows)
-            for rows in (pos, neg):
-                ops.refresh_rows_bf16(I, I16, rows)
-        ops.bpr_step_bf16(U16, I16, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size,
-                          mode=ops.UPD_DENSE_GRAD, gU=st["gU"], gI=st["gI"], loss_acc=self._loss)
-        if lazy:
-            ops.adam_lazy(1, lz, U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
-            ops.refresh_rows_bf16(U, U16, users)
-            ops.refresh_rows_bf16(I, I16, pos)
-            ops.refresh_rows_bf16(I, I16, neg)
-        elif self.optimizer == "adam":
-            self._dense_sweep(U, I, st, users, pos, neg, lr_t)
-            ops.refresh_rows_bf16(U, U16)                      # dense decay moves every row
-            ops.refresh_rows_bf16(I, I16)
-        else:
-            ru, ri = torch.unique(users).int(), torch.unique(torch.cat([pos, neg])).int()
-            ops.adam_rows(U, st["mU"], st["vU"], st["gU"], ru, lr_t)
-            ops.adam_rows(I, st["mI"], st["vI"], st["gI"], ri, lr_t)
-            ops.refresh_rows_bf16(U, U16, ru)
-            ops.refresh_rows_bf16(I, I16, ri)
-        return self._loss
-
     # ---- the losses of an announced run of steps (the trainer's epoch, MF/train_new_api.py:1078-1095) -------------
     def start_loss_rows(self, n_steps: int):
         """The next n_steps train_step calls write their (loss, mf, reg) into consecutive rows of one zeroed float32 [n_steps, 3] block (each call
@@ -258,8 +227,10 @@ class _MFBase:
                 self._plan_scratch = ops.bpr_step_plan(U, I, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size,
                                                        lr=self.lr, plan=plan, scratch=getattr(self, "_plan_scratch", None), loss_acc=self._loss)
             return self._loss
-        if self.tables16 is not None:
-            return self._train_step_bf16(users, pos, neg, pos_pop, neg_pop)
+        if self.optimizer in ("sgd", "sgd_fused") and self.tables16 is not None:     # (bf16 forward reads the shadow tables: no in-launch race either way)
+            ops.bpr_step_bf16(self.tables16["user_embedding"], self.tables16["item_embedding"], users, pos, neg, pos_pop, neg_pop, regs=self.decay,
+                              reg_div=self.batch_size, lr=self.lr, mode=ops.UPD_SGD_FUSED, U_master=U, I_master=I, loss_acc=self._loss)
+            return self._loss
         if self.optimizer == "sgd_fused":
             ops.bpr_step(U, I, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size, lr=self.lr,
                          mode=ops.UPD_SGD_FUSED, loss_acc=self._loss, users_distinct=bool(getattr(self, "users_distinct", False)))
@@ -271,66 +242,63 @@ class _MFBase:
             self._sgd_scratch = ops.sgd_step_exact(U, I, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size,
                                                    lr=self.lr, loss_acc=self._loss, scratch=sc)
             return self._loss
+        return self._adam_step(U, I, users, pos, neg, pos_pop, neg_pop, plan)
+
+    def _adam_step(self, U, I, users, pos, neg, pos_pop, neg_pop, plan):
+        """One step of `adam` / `lazy_adam`: [replay: the batch's rows up to step t - 1] -> the batch's gradient summed into gU / gI -> the update
+        [-> bf16 tables: the rows that moved are re-rounded into the shadows].  plan: the batch's plan under --deterministic, unused otherwise.
+        An embed_size the kernels do not have is refused by the first library call (PdaHipError), before any table is written."""
         st = self._opt_state()
         self._t += 1
         lr_t = ops.adam_lr_t(self.lr, self._t)
-        lazy = self.optimizer == "adam" and self.adam_exact_lazy
-        d = U.shape[1]
-        if self.deterministic:
-            return self._train_step_planned(U, I, st, users, pos, neg, pos_pop, neg_pop, plan, lr_t, lazy)
-        if self.optimizer == "adam" and not lazy and d in (32, 64, 128, 256):
-            # the reference's step in two launches (round 6): gradients + row tags, then the tagged sweep (cache policy by working set)
+        state = (U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"])
+        batch = (users, pos, neg, pos_pop, neg_pop)
+        kw = dict(regs=self.decay, reg_div=self.batch_size, loss_acc=self._loss)
+        replay = self.optimizer == "adam" and self.adam_exact_lazy
+        sweep = self.optimizer == "adam" and not replay
+        if sweep and self.tables16 is None:
+            # the reference's step fused (round 6): gradients + row tags, then the tagged sweep (cache policy by working set)
             if "tagU" not in st:
                 st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
-            ops.adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, neg, pos_pop, neg_pop,
-                          regs=self.decay, reg_div=self.batch_size, step=self._t, lr_t=lr_t, loss_acc=self._loss,
-                          users_distinct=bool(getattr(self, "users_distinct", False)))
+            tagged = (U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"])
+            if self.deterministic:
+                self._plan_scratch = ops.adam_step_plan(*tagged, *batch, step=self._t, lr_t=lr_t, plan=plan, scratch=getattr(self, "_plan_scratch", None), **kw)
+            else:
+                ops.adam_step(*tagged, *batch, step=self._t, lr_t=lr_t, users_distinct=bool(getattr(self, "users_distinct", False)), **kw)
             return self._loss
-        if lazy:        # the batch rows up to step t - 1: the forward pass reads them
-            ops.adam_lazy(0, self._lazy_state(), U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
-        ops.bpr_step(U, I, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size,
-                     mode=ops.UPD_DENSE_GRAD, gU=st["gU"], gI=st["gI"], loss_acc=self._loss)
-        if lazy:
-            ops.adam_lazy(1, self._lazy, U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
-        elif self.optimizer == "adam":
-            self._dense_sweep(U, I, st, users, pos, neg, lr_t)
+        if replay:          # the batch rows up to step t - 1: the forward pass reads them
+            ops.adam_lazy(0, self._lazy_state(), *state, users, pos, neg, self._t)
+            self._refresh16((users,), (pos, neg))
+        if self.tables16 is not None:
+            ops.bpr_step_bf16(self.tables16["user_embedding"], self.tables16["item_embedding"], *batch, mode=ops.UPD_DENSE_GRAD, gU=st["gU"], gI=st["gI"], **kw)
+        elif self.deterministic:
+            self._plan_scratch = ops.bpr_grad_plan(U, I, *batch, plan=plan, gU=st["gU"], gI=st["gI"], scratch=getattr(self, "_plan_scratch", None), **kw)
         else:
-            ops.adam_rows(U, st["mU"], st["vU"], st["gU"], torch.unique(users).int(), lr_t)
-            ops.adam_rows(I, st["mI"], st["vI"], st["gI"], torch.unique(torch.cat([pos, neg])).int(), lr_t)
-        return self._loss
-
-    def _train_step_planned(self, U, I, st, users, pos, neg, pos_pop, neg_pop, plan, lr_t, lazy):
-        """--deterministic 1, the Adam optimisers: the steps of train_step with the planned gradient in place of the atomic one."""
-        sc = getattr(self, "_plan_scratch", None)
-        if self.optimizer == "adam" and not lazy:
-            if "tagU" not in st:
-                st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
-            self._plan_scratch = ops.adam_step_plan(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos,
-                                                    neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size, step=self._t, lr_t=lr_t, plan=plan,
-                                                    scratch=sc, loss_acc=self._loss)
-            return self._loss
-        if lazy:
-            ops.adam_lazy(0, self._lazy_state(), U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
-        self._plan_scratch = ops.bpr_grad_plan(U, I, users, pos, neg, pos_pop, neg_pop, regs=self.decay, reg_div=self.batch_size, plan=plan,
-                                               gU=st["gU"], gI=st["gI"], scratch=sc, loss_acc=self._loss)
-        if lazy:
-            ops.adam_lazy(1, self._lazy, U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], users, pos, neg, self._t)
-        else:       # lazy_adam
-            ops.adam_rows(U, st["mU"], st["vU"], st["gU"], torch.unique(users).int(), lr_t)
-            ops.adam_rows(I, st["mI"], st["vI"], st["gI"], torch.unique(torch.cat([pos, neg])).int(), lr_t)
-        return self._loss
-
-    def _dense_sweep(self, U, I, st, users, pos, neg, lr_t):
-        """TF-1.14's dense-decay Adam step on both tables: six streams (the gradient tables are read only on the batch's rows: pda_adam_mark_rows +
-        pda_adam_dense_sweep3_f32) where the row length is a power of two, the seven-stream sweep otherwise.  Bit-identical."""
-        d = U.shape[1]
-        if d >= 4 and (d & (d - 1)) == 0:
+            ops.bpr_step(U, I, *batch, mode=ops.UPD_DENSE_GRAD, gU=st["gU"], gI=st["gI"], **kw)
+        if replay:
+            ops.adam_lazy(1, self._lazy, *state, users, pos, neg, self._t)
+            self._refresh16((users,), (pos, neg))
+        elif sweep:         # TF-1.14's dense-decay Adam on both tables in six streams: the gradient tables are read only on the batch's rows
             if "tU" not in st:
                 st["tU"], st["tI"] = ops.adam_touched_bitmaps(U.shape[0], I.shape[0], U.device)
             ops.adam_mark_rows(users, pos, neg, st["tU"], st["tI"])
             ops.adam_dense_sweep3(U, st["mU"], st["vU"], st["gU"], st["tU"], I, st["mI"], st["vI"], st["gI"], st["tI"], lr_t)
-        else:
-            ops.adam_dense_sweep2(U, st["mU"], st["vU"], st["gU"], I, st["mI"], st["vI"], st["gI"], lr_t)
+            self._refresh16((None,), (None,))                   # dense decay moves every row
+        else:               # lazy_adam
+            ru, ri = torch.unique(users).int(), torch.unique(torch.cat([pos, neg])).int()
+            ops.adam_rows(U, st["mU"], st["vU"], st["gU"], ru, lr_t)
+            ops.adam_rows(I, st["mI"], st["vI"], st["gI"], ri, lr_t)
+            self._refresh16((ru,), (ri,))
+        return self._loss
+
+    def _refresh16(self, user_rows, item_rows):
+        """bf16 tables: re-round the given rows of the masters into the shadow tables (None: the whole table).  Nothing to do for fp32 tables."""
+        if self.tables16 is None:
+            return
+        for rows in user_rows:
+            ops.refresh_rows_bf16(self.weights["user_embedding"], self.tables16["user_embedding"], rows)
+        for rows in item_rows:
+            ops.refresh_rows_bf16(self.weights["item_embedding"], self.tables16["item_embedding"], rows)
 
     # ---- checkpoint (tf.train.Saver stand-in, MF/train_new_api.py:1014,1218-1228) ---------------------
     CKPT_FORMAT = "pda_amd/2"     # torch.save pickle of this dict -- NOT a tf.train.Saver checkpoint (see README)

@@ -180,13 +180,42 @@ def _model(dev, nU, nI, d, B, regs, lr, U, I, extra=()):
     return m
 
 
-def test_three_model_steps_with_the_flag_match_the_oracle(dev):
+@pytest.mark.parametrize("optimizer", ["adam", "lazy_adam"])
+def test_three_model_steps_with_the_flag_match_the_oracle(dev, optimizer):
+    """adam: the three steps against the oracle's.  lazy_adam (the planned gradient + pda_adam_rows_f32 on the batch's rows) is the oracle's Adam
+    step on the rows a batch touches and nothing elsewhere: every step is compared with ONE oracle step from the model's own state before it --
+    the touched rows of tables and moments at test_lazy_adam_rows_matches_dense_on_touched_rows' tolerance, every other row bit for bit."""
     nU, nI, d, B, regs, lr, U, I, batches = _small_case()
-    ref = _three_steps_oracle(U, I, batches, regs, B, lr)
-    m = _model(dev, nU, nI, d, B, regs, lr, U, I)
+    m = _model(dev, nU, nI, d, B, regs, lr, U, I, ("--optimizer", optimizer))
     assert m.deterministic and not m.adam_exact_lazy
-    losses = [m.train_step(*to(dev, *b)).cpu().numpy().copy() for b in batches]      # (no plan given: train_step makes it)
-    _check_against_oracle((m.weights["user_embedding"], m.weights["item_embedding"], m._state), ref[:3], losses, ref[3])
+    if optimizer == "adam":
+        ref = _three_steps_oracle(U, I, batches, regs, B, lr)
+        losses = [m.train_step(*to(dev, *b)).cpu().numpy().copy() for b in batches]      # (no plan given: train_step makes it)
+        _check_against_oracle((m.weights["user_embedding"], m.weights["item_embedding"], m._state), ref[:3], losses, ref[3])
+        return
+
+    def snapshot():
+        st = m._opt_state()
+        return {"U": m.weights["user_embedding"].cpu().numpy().copy(), "I": m.weights["item_embedding"].cpu().numpy().copy(),
+                **{k: st[k].cpu().numpy().copy() for k in ("mU", "vU", "mI", "vI")}}
+
+    for t, b in enumerate(batches, 1):
+        before = snapshot()
+        state = {k: before[k].astype(np.float64) for k in ("mU", "vU", "mI", "vI")}
+        Ur, Ir, state, ref_loss = po.train_step(before["U"].astype(np.float64), before["I"].astype(np.float64), *b, regs, B, lr, "adam", state, t)
+        loss = m.train_step(*to(dev, *b)).cpu().numpy().copy()
+        print("step", t, "loss err", np.abs(loss - np.asarray(ref_loss)).max())
+        np.testing.assert_allclose(loss, ref_loss, atol=TOL, rtol=TOL)
+        after = snapshot()
+        ru, ri = np.unique(b[0]), np.unique(np.concatenate([b[1], b[2]]))
+        for keys, rows, n in ((("U", "mU", "vU"), ru, nU), (("I", "mI", "vI"), ri, nI)):
+            idle = np.setdiff1d(np.arange(n), rows)
+            assert len(rows) > 0 and len(idle) > 0
+            for k, r in zip(keys, (Ur if keys[0] == "U" else Ir, state[keys[1]], state[keys[2]])):
+                print("step", t, k, "err on the touched rows", np.abs(after[k][rows] - r[rows]).max())
+                np.testing.assert_allclose(after[k][rows], r[rows], atol=TOL)
+                np.testing.assert_array_equal(after[k][idle], before[k][idle])
+    assert float(m._state["gU"].abs().max()) == 0.0 and float(m._state["gI"].abs().max()) == 0.0     # accumulators cleared behind the update
 
 
 # ---- 5. bit identity -----------------------------------------------------------------------------------------------------------------

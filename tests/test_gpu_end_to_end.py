@@ -150,16 +150,21 @@ def test_device_sampler_queue_is_the_per_step_sampler(dev, toy, tmp_path, with_p
     assert sum(1 for _ in many()) == d.n_train // d.batch_size + 1
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "bf16-lazy_adam"])
 def test_adam_without_the_sweep_trains_the_same_model(dev, toy, tmp_path, dtype):
     """--adam_sweep replay vs sweep through the drop-in trainer: same seed, same device-sampled batches, two epochs; the tables
     the evaluation reads (after the implicit sync) and the moments in the checkpoint agree to rounding (item rows repeat
-    inside a batch: their atomic gradient sums differ in order between two runs), the recommendations agree."""
+    inside a batch: their atomic gradient sums differ in order between two runs), the recommendations agree.
+    bf16-lazy_adam: --optimizer lazy_adam on bf16 tables (pda_adam_rows_f32 on the masters, the batch's rows re-rounded); --adam_sweep does
+    not reach that optimiser, so its two runs are the same computation up to the order of the atomics.
+    bf16 tables: what the evaluation reads is, element for element, the bf16 rounding of the masters."""
     from pda_amd import train_new_api as t
     from pda_amd.sampler import DeviceSampler
+    dtype, _, optimizer = dtype.partition("-")
+    optimizer = optimizer or "adam"
     res = []
     for mode in ("sweep", "replay"):
-        t.configure(_argv(toy, str(tmp_path) + "/", "s_condition", ("--adam_sweep", mode, "--table_dtype", dtype)))
+        t.configure(_argv(toy, str(tmp_path) + "/", "s_condition", ("--adam_sweep", mode, "--table_dtype", dtype, "--optimizer", optimizer)))
         a, d = t.args, t.data
         pop_all = t.load_popularity(a)
         d.add_expo_popularity(np.power(t.get_popularity_from_load(pop_all), a.pop_exp))
@@ -174,12 +179,18 @@ def test_adam_without_the_sweep_trains_the_same_model(dev, toy, tmp_path, dtype)
                     sess.run([rec.opt_pop_global, rec.loss_pop_global])
             except t.OutOfRangeError:
                 pass
-        if mode == "replay":
+        replay = mode == "replay" and optimizer == "adam"
+        if replay:
             assert int((rec._lazy.lastU < rec._t).sum()) > 0          # rows are behind until something reads the tables
+        else:
+            assert rec._lazy is None
+        if dtype == "bf16":
+            for shadow, master in zip(rec.score_tables(), (rec.weights["user_embedding"], rec.weights["item_embedding"])):
+                assert shadow.dtype == torch.bfloat16 and torch.equal(shadow, master.bfloat16())
         U, I = (x.float().clone() for x in rec.score_tables())
         sd = rec.state_dict()
         res.append((U, I, sd["mU"].clone(), sd["vI"].clone(), sd["adam_t"]))
-        if mode == "replay":
+        if replay:
             assert int(rec._lazy.lastU.min()) == rec._t and int(rec._lazy.lastI.min()) == rec._t
     (U0, I0, m0, v0, t0), (U1, I1, m1, v1, t1) = res
     assert t0 == t1 and t0 > 10

@@ -1,5 +1,5 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
-pda_hip_deep.h and pda_hip_xquad.h).
+pda_hip_deep.h, pda_hip_xquad.h and pda_hip_dice.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -183,6 +183,18 @@ XQUAD_SIGNATURES = {
     "pda_xquad_rerank": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_dice.h (DICE, `--train dice`)
+DICE_DIS_L1, DICE_DIS_L2 = 0, 1
+DICE_SIGNATURES = {
+    "pda_dice_rows_ws_words": (_sz, [_i]),
+    "pda_dice_step_f32": (_i, [_vp, _vp, _sz, _sz] + [_vp] * 4 + [_i, _i, _f, _f, _f, _f] + [_vp] * 4 + [_i, _vp, _vp, _vp]),
+    "pda_dice_dis_f32": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "pda_dice_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 4 + [_i, _i, _f, _f, _i, _f, _f, _f, _i, _f, _f, _f, _f, _i,
+                                    _vp, _vp, _vp]),
+    "pda_dice_sample": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _f, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "pda_dice_sample_dev": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -201,7 +213,7 @@ def load():
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
-            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()):
+            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

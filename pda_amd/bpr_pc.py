@@ -175,7 +175,7 @@ def main(argv=None):
     load_popularity(args)                                                        # the reference reads it first (:1243)
 
     regs_pretain = args.regs
-    if args.model == "mf" and args.train == "normal":                            # :1272-1284
+    if args.model == "mf" and args.train in ("normal", "dice"):                  # :1272-1284 (a DICE checkpoint ranks by the raw head too)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
         print("normal MF... ")
         args.regs = args.fregs
@@ -185,7 +185,7 @@ def main(argv=None):
     args.wd = regs_pretain                                                       # :1300
     path = checkpoint_dir(args) + "best_ckpt.ckpt"
     if not os.path.exists(path):
-        raise FileNotFoundError("BPR-PC restores a --train normal checkpoint, and there is none at %s (train with the same flags first)" % path)
+        raise FileNotFoundError("BPR-PC restores a --train %s checkpoint, and there is none at %s (train with the same flags first)" % (args.train, path))
     model = t.DatasetApi_Model(args, config, test_batch_size, (lambda: host_generator(data, False)), device)
     model.set_sess(None)
 

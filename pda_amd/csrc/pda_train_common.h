@@ -33,6 +33,21 @@ __device__ __forceinline__ void triplet_dots(f32x4 ue, f32x4 pe, f32x4 ne, float
         ns += __shfl_xor(ns, o, 64);
     }
 }
+// DICE (pda_dice.hip): a row of W floats is two embeddings of W/2, the lower half of the W/4 lanes holds the first (interest), the upper half
+// (upper == true) the second (conformity).  x_lo / x_hi = <u, p> - <u, n> over each half: the ladder above stopped one rung early, then one
+// exchange across the halves.  Every lane of the group holds both, bit for bit the same.
+template <int W>
+__device__ __forceinline__ void triplet_half_dots(f32x4 ue, f32x4 pe, f32x4 ne, bool upper, float& x_lo, float& x_hi) {
+    float ps = dot4(ue, pe), ns = dot4(ue, ne);
+#pragma unroll
+    for (int o = W / 16; o > 0; o >>= 1) {
+        ps += __shfl_xor(ps, o, 64);
+        ns += __shfl_xor(ns, o, 64);
+    }
+    const float mine = ps - ns, other = __shfl_xor(mine, W / 8, 64);
+    x_lo = upper ? other : mine;
+    x_hi = upper ? mine : other;
+}
 // this lane's share of |u|^2 + |p|^2 + |n|^2 (the L2 term of the loss)
 __device__ __forceinline__ float triplet_sq(f32x4 ue, f32x4 pe, f32x4 ne) { return dot4(ue, ue) + dot4(pe, pe) + dot4(ne, ne); }
 // x = positive score - negative score  ->  d(mean loss) / dx; lane 0 of the group (e == 0) takes the triplet's log-sigmoid into maxi

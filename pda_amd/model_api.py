@@ -3,6 +3,7 @@
     ConditionalBPRMF   PD / PDA            MF/model_api.py:14-185
     BPRMFTempPop       BPRMF(t)-pop        MF/model_api.py:300-416   (temporal popularity bias; Adam sweep only)
     BPRMF              plain BPR-MF        MF/model_api.py:419-757   (only :419-471, :521-536, :695-706 are live)
+    DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
 trainer passes to `sess.run`.  Here they are light handle objects understood by `pda_amd.train_new_api.Session`,
@@ -482,3 +483,153 @@ class BPRMFTempPop(_MFBase):
             for names, tabs in zip(self.CKPT_MOMENTS, (st.m, st.v)):
                 for n, t in zip(names, tabs):
                     t.copy_(sd[n])
+
+
+DICE_EMBED_SIZES = ops.DICE_EMBED_SIZES   # --embed_size of a DICE model: the width of EACH of its two embeddings (rows of 64 / 128 / 256 floats)
+
+
+def check_dice(args):
+    """--train dice: refuse, before anything is built, what DICE has no kernel for.  Every message names its flag."""
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train dice sums its gradients with float atomics (no planned gradient)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train dice runs fp32 tables only" % args.table_dtype)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train dice runs the reference's dense-decay Adam only (--optimizer adam)" % args.optimizer)
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("--adam_sweep %s: --train dice runs the dense Adam sweep only (auto | sweep)" % getattr(args, "adam_sweep", "auto"))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train dice trains on one GPU" % args.gpus)
+    if getattr(args, "dice_dis_loss", "l1") not in ("l1", "l2"):
+        raise NotImplementedError("--dice_dis_loss %s: l1 | l2 (dcor is not implemented)" % args.dice_dis_loss)
+    if int(args.embed_size) not in DICE_EMBED_SIZES:
+        raise ValueError("--train dice: --embed_size is the width of each of the two embeddings and must be one of %s, got %s"
+                         % (DICE_EMBED_SIZES, args.embed_size))
+    for flag in ("dice_int_weight", "dice_con_weight", "dice_dis_pen", "dice_margin"):
+        if not float(getattr(args, flag, 0.0)) >= 0.0:
+            raise ValueError("--%s must be >= 0" % flag)
+    for flag in ("dice_margin_decay", "dice_loss_decay"):
+        if not 0.0 < float(getattr(args, flag, 0.9)) <= 1.0:
+            raise ValueError("--%s must lie in (0, 1]" % flag)
+
+
+class DICE(_MFBase):
+    """DICE (Zheng et al., WWW'21).  Fetchables: opt, loss, mf_loss, reg_loss, batch_ratings.
+
+    weights: user_embedding [n_users, 2d], item_embedding [n_items, 2d]; columns [0, d) are the interest embedding, [d, 2d) the conformity
+    embedding, d = --embed_size.  Each [n, d] half is Xavier-uniform like a [n, d] table of the other models, drawn in the order user interest,
+    user conformity, item interest, item conformity.  The click score s_int + s_con is the dot of two rows: score_tables() hands the 2d-wide
+    tables to every evaluation path as they are.  A step is pda_dice_adam_step_f32; the loss weights follow DICE's schedule (start_epoch)."""
+    with_pop = False
+    LOSS_TERMS = 6           # a step's loss row: loss, mf_loss, reg_loss, L_int, L_con, L_dis
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_dice(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.w_int = float(getattr(args, "dice_int_weight", 0.1))
+        self.w_con = float(getattr(args, "dice_con_weight", 0.1))
+        self.dis_pen = float(getattr(args, "dice_dis_pen", 0.01))
+        self.dis_loss = getattr(args, "dice_dis_loss", "l1")
+        self.loss_decay = float(getattr(args, "dice_loss_decay", 0.9))
+        self.margin = float(getattr(args, "dice_margin", 40.0))       # the sampler's current margin, kept for the checkpoint (start_epoch)
+        self._dice = None
+        self._loss_ring = torch.zeros((16, self.LOSS_TERMS), dtype=torch.float32, device=self.device)
+        self._loss = self._loss_ring[0]
+        self.epoch_terms = None                                       # float64 [6]: the sums of the last finished epoch's loss rows
+        self.opt, self.loss = Fetch(self, "opt"), Fetch(self, "loss")
+        self.mf_loss, self.reg_loss = Fetch(self, "mf_loss"), Fetch(self, "reg_loss")
+        self.batch_ratings = Fetch(self, "batch_ratings")
+
+    def init_weights(self, gen):
+        d = self.emb_dim
+
+        def table(n):
+            a = xavier_uniform_(torch.empty(n, d, device=self.device), gen)
+            b = xavier_uniform_(torch.empty(n, d, device=self.device), gen)
+            return torch.cat([a, b], dim=1).contiguous()
+        return {"user_embedding": table(self.n_users), "item_embedding": table(self.n_items)}
+
+    def _dice_state(self):
+        if self._dice is None:
+            self._dice = ops.DiceState(self.weights["user_embedding"], self.weights["item_embedding"])
+        return self._dice
+
+    def start_epoch(self, epoch: int, margin=None):
+        """DICE's schedule: at the start of every epoch after the first, w_int and w_con are multiplied by --dice_loss_decay.  margin: the
+        sampler's margin for this epoch (the sampler owns that half of the schedule); recorded for the checkpoint."""
+        if epoch > 0:
+            self.w_int *= self.loss_decay
+            self.w_con *= self.loss_decay
+        if margin is not None:
+            self.margin = float(margin)
+
+    def start_loss_rows(self, n_steps: int):
+        self._loss_rows = torch.zeros((max(1, int(n_steps)), self.LOSS_TERMS), dtype=torch.float32, device=self.device)
+        self._loss_row_i = 0
+
+    def finish_loss_rows(self) -> torch.Tensor:
+        """The trainer's (loss, mf_loss, reg_loss) sums; all six terms of the epoch stay in epoch_terms."""
+        rows, n = self._loss_rows, self._loss_row_i
+        self._loss_rows = None
+        self.epoch_terms = rows[:n].double().sum(0)
+        return self.epoch_terms[:3]
+
+    def train_step(self, users, pos, neg, mask=None, plan=None) -> torch.Tensor:
+        """One DICE step.  mask: 1 where the negative is the more popular item (PNSM), uint8 (bool and integer tensors are converted).
+        Returns the float32 [6] device tensor (loss, mf_loss, reg_loss, L_int, L_con, L_dis) of this step: mf_loss is everything except
+        reg_loss, so loss = mf_loss + reg_loss as for the other models."""
+        if mask is None:
+            raise ValueError("dice needs the mask of every triplet (1: the negative is the more popular item)")
+        if mask.dtype != torch.uint8:
+            mask = mask.to(torch.uint8)
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._dice_state()
+        self._t += 1
+        ops.dice_adam_step(self.weights["user_embedding"], self.weights["item_embedding"], users, pos, neg, mask.contiguous(), st,
+                           w_int=self.w_int, w_con=self.w_con, dis_pen=self.dis_pen, dis_loss=self.dis_loss, regs=self.decay,
+                           reg_div=self.batch_size, step=self._t, lr_t=ops.adam_lr_t(self.lr, self._t), loss_acc=self._loss)
+        return self._loss
+
+    def state_dict(self):
+        sd = {"format": self.CKPT_FORMAT, "model": "dice", "embed_size": self.emb_dim, "n_users": self.n_users, "n_items": self.n_items,
+              "optimizer": self.optimizer, "table_dtype": self.table_dtype, "user_embedding": self.weights["user_embedding"],
+              "item_embedding": self.weights["item_embedding"], "adam_t": self._t, "dice_margin": self.margin, "dice_int_weight": self.w_int,
+              "dice_con_weight": self.w_con}
+        if self._dice is not None:
+            sd.update({k: getattr(self._dice, k) for k in ("mU", "vU", "mI", "vI")})
+        return sd
+
+    def load_state_dict(self, sd):
+        if not isinstance(sd, dict) or "user_embedding" not in sd:
+            raise ValueError("not a pda_amd checkpoint (a tf.train.Saver checkpoint of the reference cannot be loaded)")
+        if sd.get("format") != self.CKPT_FORMAT:
+            raise ValueError("checkpoint format %r, DICE reads %s" % (sd.get("format"), self.CKPT_FORMAT))
+        if sd.get("model", "mf") != "dice":
+            raise ValueError("checkpoint of a %s model cannot be loaded into DICE" % sd.get("model", "mf"))
+        for key, mine in (("embed_size", self.emb_dim), ("n_users", self.n_users), ("n_items", self.n_items)):
+            if int(sd[key]) != int(mine):
+                raise ValueError("checkpoint %s = %s, model has %s" % (key, sd[key], mine))
+        for k in ("user_embedding", "item_embedding"):
+            if tuple(sd[k].shape) != tuple(self.weights[k].shape):
+                raise ValueError("checkpoint table %s does not have the model's shape" % k)
+        for k in ("user_embedding", "item_embedding"):
+            self.weights[k].copy_(sd[k])
+        self._t = int(sd.get("adam_t", 0))
+        self.margin = float(sd.get("dice_margin", self.margin))
+        self.w_int = float(sd.get("dice_int_weight", self.w_int))
+        self.w_con = float(sd.get("dice_con_weight", self.w_con))
+        # a fresh state: the row tags of the steps run so far must not meet the step numbers that follow adam_t (a row whose tag equals
+        # the step's is not listed, and would miss its L_dis gradient); the gradient tables are zero between steps anyway
+        self._dice = None
+        if "mU" in sd:
+            st = self._dice_state()
+            for k in ("mU", "vU", "mI", "vI"):
+                getattr(st, k).copy_(sd[k])

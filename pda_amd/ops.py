@@ -1976,3 +1976,147 @@ def xquad_rerank(cand_idx, cand_val, item_is_head, lam, K=50, variant="smooth", 
                                ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
                                lam, XQUAD_VARIANTS[variant], K, ptr(idx), ptr(val), stream_ptr()), "pda_xquad_rerank")
     return idx, val
+
+
+# ---- DICE (include/pda_hip_dice.h) ------------------------------------------------------------------------------------------------------
+DICE_EMBED_SIZES = (32, 64, 128)          # d, the width of ONE embedding: the tables' rows are 2 d wide
+DICE_DIS_KINDS = {"l1": _lib.DICE_DIS_L1, "l2": _lib.DICE_DIS_L2}
+DICE_LOSS_TERMS = 6                       # loss_acc: loss, mf_loss, reg_loss, L_int, L_con, L_dis
+
+
+def dice_rows_ws(B: int, device) -> torch.Tensor:
+    """The row-list workspace of one batch size (pda_dice_rows_ws_words): int32, private to one stream."""
+    return torch.zeros(int(_lib.load().pda_dice_rows_ws_words(int(B))), dtype=torch.int32, device=device)
+
+
+class DiceState:
+    """Adam state of the two concatenated DICE tables: m, v, the dense gradient accumulators, the per-row step tags and the row lists."""
+
+    def __init__(self, U, I):
+        z = torch.zeros_like
+        self.mU, self.vU, self.gU, self.mI, self.vI, self.gI = z(U), z(U), z(U), z(I), z(I), z(I)
+        self.tagU, self.tagI = adam_row_tags(U.shape[0], I.shape[0], U.device)
+        self.rows_ws = None
+
+    def ws(self, B: int) -> torch.Tensor:
+        if self.rows_ws is None or self.rows_ws.numel() < 4 + 3 * B:
+            self.rows_ws = dice_rows_ws(B, self.gU.device)
+        return self.rows_ws
+
+
+def _dice_check(U, I, users, pos, neg, mask, check_ids: bool):
+    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
+    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1] or U.shape[1] % 2:
+        raise ValueError("DICE tables: U [n_users, 2d] and I [n_items, 2d] (interest columns, then conformity columns)")
+    d = U.shape[1] // 2
+    if d not in DICE_EMBED_SIZES:
+        raise ValueError(f"DICE: the embedding width d must be one of {DICE_EMBED_SIZES} (rows of 2d floats), got {d}")
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    mask = _need(mask, torch.uint8, "mask")
+    B = users.numel()
+    if B < 1 or pos.numel() != B or neg.numel() != B or mask.numel() != B:
+        raise ValueError("users/pos/neg/mask must have the same, non-zero length")
+    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
+        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
+        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
+            raise ValueError("DICE batch: a user or item id lies outside the tables")
+    return d, B
+
+
+def dice_grads(U, I, users, pos, neg, mask, st: DiceState, *, w_int: float, w_con: float, dis_pen: float, dis_loss: str = "l1", regs: float,
+               reg_div: float, step: int, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_dice_step_f32 + pda_dice_dis_f32: the batch's whole gradient summed into st.gU / st.gI (rows tagged `step`), no update.
+    loss_acc float32 [6] += (loss, mf_loss, reg_loss, L_int, L_con, L_dis)."""
+    d, B = _dice_check(U, I, users, pos, neg, mask, check_ids)
+    if dis_loss not in DICE_DIS_KINDS:
+        raise ValueError(f"dis_loss must be 'l1' or 'l2', not {dis_loss!r}")
+    loss_acc = _need(loss_acc, torch.float32, "loss_acc", optional=True)
+    if loss_acc is not None and loss_acc.numel() < DICE_LOSS_TERMS:
+        raise ValueError("DICE loss_acc holds six float32")
+    lib, ws = _lib.load(), st.ws(B)
+    check(lib.pda_dice_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(mask), B, d, float(w_int), float(w_con),
+                                float(regs), float(reg_div), ptr(st.gU), ptr(st.gI), ptr(st.tagU), ptr(st.tagI), int(step), ptr(ws), ptr(loss_acc),
+                                stream_ptr()), "pda_dice_step_f32")
+    check(lib.pda_dice_dis_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], B, d, DICE_DIS_KINDS[dis_loss], float(dis_pen), ptr(st.gU), ptr(st.gI), ptr(ws), ptr(loss_acc),
+                               stream_ptr()), "pda_dice_dis_f32")
+
+
+def dice_adam_step(U, I, users, pos, neg, mask, st: DiceState, *, w_int: float, w_con: float, dis_pen: float, dis_loss: str = "l1", regs: float,
+                   reg_div: float, step: int, lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, cache_policy: int = ADAM_CACHE_AUTO,
+                   loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_dice_adam_step_f32: one DICE train step (gradients, L_dis, TF-1.14 dense-decay Adam over both tables); graph-capturable."""
+    d, B = _dice_check(U, I, users, pos, neg, mask, check_ids)
+    if dis_loss not in DICE_DIS_KINDS:
+        raise ValueError(f"dis_loss must be 'l1' or 'l2', not {dis_loss!r}")
+    loss_acc = _need(loss_acc, torch.float32, "loss_acc", optional=True)
+    if loss_acc is not None and loss_acc.numel() < DICE_LOSS_TERMS:
+        raise ValueError("DICE loss_acc holds six float32")
+    check(_lib.load().pda_dice_adam_step_f32(ptr(U), ptr(st.mU), ptr(st.vU), ptr(st.gU), ptr(st.tagU), U.shape[0], ptr(I), ptr(st.mI), ptr(st.vI),
+                                             ptr(st.gI), ptr(st.tagI), I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(mask), B, d, float(w_int),
+                                             float(w_con), DICE_DIS_KINDS[dis_loss], float(dis_pen), float(regs), float(reg_div), int(step),
+                                             float(lr_t), beta1, beta2, eps, int(cache_policy), ptr(st.ws(B)), ptr(loss_acc), stream_ptr()),
+          "pda_dice_adam_step_f32")
+    mark_modified(U, I)
+
+
+class DicePop:
+    """What PNSM reads besides the train CSR: pop int32 [n_items] (train interactions per item), order (items ascending by (pop, id)) and
+    sorted_pop = pop[order], built once on the host from the CSR's column ids."""
+
+    def __init__(self, train_indices: torch.Tensor, n_items: int):
+        import numpy as np
+        idx = train_indices.detach().cpu().numpy().astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_items):
+            raise ValueError("a train item id lies outside the catalogue")
+        pop = np.bincount(idx, minlength=int(n_items)).astype(np.int32)
+        order = np.lexsort((np.arange(n_items), pop)).astype(np.int32)
+        dev = train_indices.device
+        self.n_items = int(n_items)
+        self.pop, self.order = torch.from_numpy(pop).to(dev), torch.from_numpy(order).to(dev)
+        self.sorted_pop = torch.from_numpy(np.ascontiguousarray(pop[order])).to(dev)
+
+
+def _dice_sample_out(B, dev, out):
+    if out is None:
+        return tuple(torch.empty(B, dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.int32, torch.uint8))
+    users, pos, neg, mask = out
+    for t, dt, n in ((users, torch.int32, "users"), (pos, torch.int32, "pos"), (neg, torch.int32, "neg"), (mask, torch.uint8, "mask")):
+        if _need(t, dt, n).numel() != B:
+            raise ValueError("PNSM output buffers hold one entry per triplet")
+    return out
+
+
+def dice_sample(train_indptr, train_indices, dp: DicePop, B: int, *, margin: float, seed: int, step: int, users=None, user_pool=None,
+                n_pool: int = 0):
+    """pda_dice_sample -> (users, pos, neg, mask) on the device: PNSM with the users and positives of sample_triplets(seed, step)."""
+    if not float(margin) >= 0.0:
+        raise ValueError("the PNSM margin must be >= 0")
+    gen = users is None
+    out = _dice_sample_out(int(B), train_indptr.device, None)
+    if not gen:
+        out = (_need(users, torch.int32, "users"),) + out[1:]
+    check(_lib.load().pda_dice_sample(ptr(out[0]), int(gen), ptr(user_pool), int(n_pool), int(B), ptr(_need(train_indptr, torch.int64, "train_indptr")),
+                                      ptr(_need(train_indices, torch.int32, "train_indices")), dp.n_items, ptr(dp.order), ptr(dp.sorted_pop),
+                                      ptr(dp.pop), float(margin), seed & (2 ** 64 - 1), int(step), ptr(out[1]), ptr(out[2]), ptr(out[3]),
+                                      stream_ptr()), "pda_dice_sample")
+    return out
+
+
+def dice_sample_into(out, train_indptr, train_indices, dp: DicePop, *, margin_dev: torch.Tensor, seed: int, step_dev: torch.Tensor,
+                     parity: Optional[int] = None, user_pool=None, n_pool: int = 0):
+    """pda_dice_sample_dev: one batch into out = (users, pos, neg, mask), step and margin read from device memory (graph-capturable).
+    step_dev int64 [1]: read only.  step_dev int64 [2] + parity p: read from slot p, step + 1 stored to slot 1 - p (sample_triplets_into)."""
+    out = _dice_sample_out(out[0].numel(), train_indptr.device, out)
+    margin_dev = _need(margin_dev, torch.float32, "margin_dev")
+    step_dev = _need(step_dev, torch.int64, "step_dev")
+    if parity is None:
+        src, nxt = step_dev, None
+    else:
+        if step_dev.numel() != 2:
+            raise ValueError("parity mode needs a two-slot step counter")
+        src, nxt = step_dev[parity:parity + 1], step_dev[1 - parity:2 - parity]
+    check(_lib.load().pda_dice_sample_dev(ptr(out[0]), 1, ptr(user_pool), int(n_pool), out[0].numel(), ptr(_need(train_indptr, torch.int64, "train_indptr")),
+                                          ptr(_need(train_indices, torch.int32, "train_indices")), dp.n_items, ptr(dp.order), ptr(dp.sorted_pop),
+                                          ptr(dp.pop), ptr(margin_dev), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(out[1]), ptr(out[2]),
+                                          ptr(out[3]), stream_ptr()), "pda_dice_sample_dev")
+    return out

@@ -79,6 +79,13 @@ _EXTENSION_FLAGS = [
     ("xq_candidates", int, 1000, "xQuAD: candidates per user the re-ranking selects from, max(Ks) .. 1024 (above 54 they come from the deep path)"),
     ("xq_head_share", float, 0.8, "xQuAD: the short head is the most popular items that hold this share of the train interactions, strictly inside 0 .. 1"),
     ("xq_variant", str, "smooth", "xQuAD: smooth | binary"),
+    ("dice_int_weight", float, 0.1, "DICE (--train dice): weight of the interest loss L_int"),
+    ("dice_con_weight", float, 0.1, "DICE: weight of the conformity loss L_con"),
+    ("dice_dis_pen", float, 0.01, "DICE: weight of the discrepancy term (the loss takes -dice_dis_pen * L_dis)"),
+    ("dice_dis_loss", str, "l1", "DICE: the discrepancy between the interest and the conformity embeddings, l1 | l2"),
+    ("dice_margin", float, 40.0, "DICE: the popularity margin M of the negative sampler (PNSM), in train interactions"),
+    ("dice_margin_decay", float, 0.9, "DICE: M is multiplied by this at the start of every epoch after the first"),
+    ("dice_loss_decay", float, 0.9, "DICE: dice_int_weight and dice_con_weight are multiplied by this at the start of every epoch after the first"),
 ]
 
 

@@ -10,7 +10,10 @@ yielding, per step, a tuple of sequences of length batch_size -- (users, pos, ne
                      yields python lists like the reference, for drop-in use and for injecting fixed batches.
     DeviceSampler    pda_sample_triplets (HIP): counter-based, O(B) per batch, tensors never leave HBM.
                      Not stream-identical to the host generators -- parity is defined on injected batches
-                     (last bullet).
+                     (last bullet).  mode="dice": PNSM, DICE's popularity-margin negative sampler
+                     (pda_dice_sample): (users, pos, neg, mask), and the margin's schedule (start_epoch).
+    HostDiceSampler  PNSM in numpy, the debugging twin of mode="dice" (--sampler host): the same algorithm on the
+                     host's random streams -- NOT draw for draw the device stream.
 """
 from __future__ import annotations
 
@@ -88,6 +91,8 @@ def host_generator_with_temp(data):
 def to_device_batch(batch, device):
     """Tuple of python lists / numpy arrays (sampler protocol) -> int32/float32 device tensors."""
     out = [torch.as_tensor(np.asarray(b, dtype=np.int32), device=device) for b in batch[:3]]
+    if len(batch) == 4:           # DICE: the mask of the triplets
+        out.append(torch.as_tensor(np.asarray(batch[3], dtype=np.uint8), device=device))
     if len(batch) == 5:
         out += [torch.as_tensor(np.asarray(b, dtype=np.float32), device=device) for b in batch[3:]]
     return tuple(out)
@@ -98,9 +103,17 @@ class DeviceSampler:
     batches as well, :178-220).  The batches are bit for bit those of ahead = 1 (one pda_sample_triplets launch per step); a
     batch handed out is a row view of the queue and stays valid until `ahead` further batches have been taken."""
 
-    def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0):
+    def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0, mode: str = "bpr",
+                 margin: float = 40.0, margin_decay: float = 0.9):
+        if mode not in ("bpr", "dice"):
+            raise ValueError("DeviceSampler mode must be 'bpr' or 'dice', not %r" % (mode,))
+        if mode == "dice" and (with_pop or temp_slots > 0 or neg_range is not None):
+            raise ValueError("mode='dice' draws (users, pos, neg, mask) over the whole catalogue: no popularity columns, no time slots, no neg_range")
+        self.mode = mode
         self.data, self.device, self.with_pop, self.seed = data, torch.device(device), with_pop or temp_slots > 0, seed
         self.indptr, self.indices, self.slots = data.train_csr(self.device)
+        self.margin, self.margin_decay = float(margin), float(margin_decay)
+        self.dice_pop = ops.DicePop(self.indices, data.n_items) if mode == "dice" else None
         pool = np.fromiter(data.train_user_list.keys(), dtype=np.int32)   # all_users = users with train rows
         self.pool = torch.from_numpy(pool).to(self.device)
         self.pop = None
@@ -144,8 +157,18 @@ class DeviceSampler:
         self._calls += 1
         self._left = n
 
+    def start_epoch(self, epoch: int) -> float:
+        """mode="dice": the margin's schedule -- multiplied by margin_decay at the start of every epoch after the first.  -> the margin."""
+        if epoch > 0:
+            self.margin *= self.margin_decay
+        return self.margin
+
     def batch(self):
         self.step += 1
+        if self.mode == "dice":       # one pda_dice_sample launch per step; the margin travels by value
+            self.plan = None
+            return ops.dice_sample(self.indptr, self.indices, self.dice_pop, self.data.batch_size, margin=self.margin, seed=self.seed,
+                                   step=self.step, user_pool=self.pool, n_pool=self.pool.numel())
         if self.ahead == 1:
             u, p, n, pp, pn = ops.sample_triplets(self.indptr, self.indices, self.data.batch_size, seed=self.seed,
                                                   step=self.step, user_pool=self.pool, n_pool=self.pool.numel(),
@@ -165,3 +188,65 @@ class DeviceSampler:
         """Zero-argument generator: one epoch of device-tensor batches."""
         for _ in range(n_batches(self.data)):
             yield self.batch()
+
+
+def pnsm_ranges(sorted_pop: np.ndarray, pop_p, margin):
+    """PNSM's two ranges of `order` for positives of popularity pop_p (fp32 arithmetic, like the kernel): H = [hi_at, n) holds the items with
+    pop > pop_p + margin, L = [0, lo_end) those with pop < pop_p - margin.  -> (hi_at, lo_end)."""
+    sp = np.asarray(sorted_pop).astype(np.float32)
+    P, M = np.asarray(pop_p).astype(np.float32), np.float32(margin)
+    return np.searchsorted(sp, P + M, side="right"), np.searchsorted(sp, P - M, side="left")
+
+
+class HostDiceSampler:
+    """PNSM on the host (--sampler host with --train dice): users and positives like host_generator, the negative from the more popular
+    side H or the less popular side L of the positive (a fair coin where both exist, the whole catalogue where neither does), uniform
+    inside the side with rejection against the user's train items (REJECT_CAP tries, then the last draw stays).  Yields python lists
+    (users, pos, neg, mask).  The algorithm of pda_dice_sample on Python's and numpy's generators: not the device's stream."""
+    REJECT_CAP = 4096
+
+    def __init__(self, data, margin: float = 40.0, margin_decay: float = 0.9):
+        self.data, self.margin, self.margin_decay = data, float(margin), float(margin_decay)
+        pop = np.zeros(data.n_items, dtype=np.int32)
+        for items in data.train_user_list.values():
+            np.add.at(pop, np.asarray(items, dtype=np.int64), 1)
+        self.pop = pop
+        self.order = np.lexsort((np.arange(data.n_items), pop)).astype(np.int32)
+        self.sorted_pop = pop[self.order]
+
+    def start_epoch(self, epoch: int) -> float:
+        if epoch > 0:
+            self.margin *= self.margin_decay
+        return self.margin
+
+    def draw_negative(self, p: int, clicked):
+        """-> (neg, mask) for one positive and the user's train items."""
+        n_items = self.data.n_items
+        hi_at, lo_end = (int(x) for x in pnsm_ranges(self.sorted_pop, self.pop[p], self.margin))
+        nH, nL = n_items - hi_at, lo_end
+        whole = nH == 0 and nL == 0
+        from_h = nH > 0 and (nL == 0 or rd.random() < 0.5)
+        start, span = (0, n_items) if whole else ((hi_at, nH) if from_h else (0, nL))
+        clicked = set(clicked)
+        for _ in range(self.REJECT_CAP):
+            at = start + rd.randrange(span)
+            n = at if whole else int(self.order[at])
+            if n not in clicked:
+                break
+        return n, int(self.pop[n] > self.pop[p]) if whole else int(from_h)
+
+    def __call__(self):
+        data = self.data
+        all_users = list(data.train_user_list.keys())
+        bs = data.batch_size
+        for _ in range(n_batches(data)):
+            users = rd.sample(all_users, bs) if bs <= data.n_users else [rd.choice(all_users) for _ in range(bs)]
+            pos, neg, mask = [], [], []
+            for u in users:
+                clicked = data.train_user_list[u]
+                p = clicked[np.random.randint(len(clicked))] if clicked else 0
+                n, m = self.draw_negative(p, clicked)
+                pos.append(p)
+                neg.append(n)
+                mask.append(m)
+            yield (users, pos, neg, mask)

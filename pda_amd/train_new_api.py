@@ -28,9 +28,9 @@ import torch
 
 from . import ops
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import BPRMF, BPRMFTempPop, ConditionalBPRMF, Fetch
+from .model_api import BPRMF, DICE, BPRMFTempPop, ConditionalBPRMF, Fetch, check_dice
 from .parse import parse_args
-from .sampler import DeviceSampler, host_generator, host_generator_with_temp, to_device_batch
+from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
 # module-level singletons of the reference (MF/batch_test.py:6-19), filled by configure()/main()
 args = None
@@ -127,6 +127,11 @@ class DatasetApi_Model:
             self.input_type = "without_pop"                                  # :558-559
             print("dataset api without pop")
             self.Recommender = BPRMF(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train == "dice":
+            # DICE: two embeddings per row, ranked by the raw head like a BPRMF; batches carry the sampler's mask
+            self.input_type = "without_pop"
+            print("dataset api without pop")
+            self.Recommender = DICE(args, data_config, use_dataset_api=True, device=self.device)
         else:
             raise NotImplementedError("not implement this model: " + args.train)   # :590
         # the device sampler draws a batch's users without replacement (like the reference, :380-381): the fused SGD step may
@@ -434,6 +439,10 @@ def main(argv=None):
     print(os.getcwd())
     configure(argv)
     check_topk_max(args)                   # (refusals before anything is built)
+    if args.train == "dice":
+        check_dice(args)
+        if args.test not in ("normal", "dice"):
+            raise NotImplementedError("--train dice goes with --test normal (DICE and DICE-A) or --test dice, not --test " + str(args.test))
     random.seed(2020)                      # :934-936
     np.random.seed(2020)
     torch.manual_seed(2021)
@@ -453,9 +462,9 @@ def main(argv=None):
     linear_predict_popularity = np.power(linear_predict_popularity, popularity_exp)
 
     with_pop = False
-    if args.model == "mf" and args.train == "normal":                            # :963-970
+    if args.model == "mf" and args.train in ("normal", "dice"):                  # :963-970 (DICE is evaluated like a BPRMF: --test normal = DICE-A)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
-        print("normal MF... ")
+        print("normal MF... " if args.train == "normal" else "-------    running DICE  ----------------")
         last_stage_popualarity_ori = pop_item_all[:, -2]
         linear_predict_popularity_ori = pop_item_all[:, -2] + 0.5 * (pop_item_all[:, -2] - pop_item_all[:, -3])
         # the reference masks with the already-powered array (a quirk): kept
@@ -488,6 +497,11 @@ def main(argv=None):
             sampler = DeviceSampler(data, device, False, temp_slots=config["temp_num"])
         else:
             sampler = (lambda: host_generator_with_temp(data))
+    elif args.train == "dice":
+        if args.sampler == "device":
+            sampler = DeviceSampler(data, device, False, mode="dice", margin=args.dice_margin, margin_decay=args.dice_margin_decay)
+        else:
+            sampler = HostDiceSampler(data, args.dice_margin, args.dice_margin_decay)
     elif args.sampler == "device":
         sampler = DeviceSampler(data, device, with_pop)
     else:
@@ -531,6 +545,8 @@ def main(argv=None):
         torch.save(rec.state_dict(), save_ckpt_dir + name)
 
     for epoch in range(args.epoch):
+        if args.train == "dice":                        # DICE's schedule: the margin and the two loss weights decay at the start of an epoch
+            rec.start_epoch(epoch, sampler.start_epoch(epoch))
         model.switch_to_training_or_reinitsampler(sess)
         rec.start_loss_rows(n_batch + 1)                # losses stay on the device, a row per step: one reduction and one sync per epoch
         extra = torch.zeros(3, dtype=torch.float64, device=device)
@@ -539,7 +555,7 @@ def main(argv=None):
                 before = rec._loss_row_i
                 row = sess.run_async(fetches)
                 if rec._loss_row_i == before:           # (a generator longer than n_batch + 1 steps: the step fell back to the ring's rows)
-                    extra += row
+                    extra += row[:3]
         except OutOfRangeError:
             pass
         acc = rec.finish_loss_rows() + extra
@@ -572,7 +588,7 @@ def main(argv=None):
             print("||------------PDA/PDGA injecting linear predicted popularity testing : time: ", int(time() - ttt1))
             _print_result(ret2)
             ret = ret1
-        elif args.test == "temp_pop":                                            # :1192-1200
+        elif args.test in ("temp_pop", "dice"):                                  # :1192-1200 (--test dice: the main_branch head alone)
             print(perf_str)
             ttt1 = time()
             evaluation_model.set_testing_popularity(None)
@@ -670,10 +686,10 @@ def main(argv=None):
             print("|||---BPRMF-A with injecting %s:" % name)
             _print_result(r)
         print("----------------------------")
-    elif args.test == "temp_pop":                                                # :1310-1314
+    elif args.test in ("temp_pop", "dice"):                                      # :1310-1314
         evaluation_model.set_testing_popularity(None)
         ret = evaluation_model.eval(model, sess, rec_type="main_branch")
-        print("---- result with last pop bias for temp_pop model:")
+        print("---- result with last pop bias for temp_pop model:" if args.test == "temp_pop" else "---- DICE result (interest + conformity):")
         _print_result(ret)
     print("training and testing end!!!!")
     print("|||  ------------------------ best performance for model selected by PD/PDG/BPRMF ------------------- |||")

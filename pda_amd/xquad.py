@@ -165,7 +165,7 @@ def main(argv=None):
     from . import train_new_api as t
     t.configure(argv)
     args, data = t.args, t.data
-    if not (args.model == "mf" and args.train == "normal"):
+    if not (args.model == "mf" and args.train in ("normal", "dice")):
         raise NotImplementedError("Not implement this training method.....")
     K = check_flags(args, t.Ks)
     t.check_topk_max(args)
@@ -180,7 +180,7 @@ def main(argv=None):
     args.wd = args.regs
     path = checkpoint_dir(args) + "best_ckpt.ckpt"
     if not os.path.exists(path):
-        raise FileNotFoundError("xQuAD restores a --train normal checkpoint, and there is none at %s (train with the same flags first)" % path)
+        raise FileNotFoundError("xQuAD restores a --train %s checkpoint, and there is none at %s (train with the same flags first)" % (args.train, path))
     n_candidates = min(int(args.xq_candidates), data.n_items)
     if n_candidates < int(args.xq_candidates):
         print("xquad: the catalogue holds %d items: %d candidates per user" % (data.n_items, n_candidates))

@@ -87,6 +87,33 @@ int pda_score_topk4_phase_bf16(const uint16_t* U, const uint16_t* I_shard, const
 int pda_score_topk4_phase_image_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs);
 int pda_score_topk4_phase_user_image(const void* U, int bf16, const int32_t* users, int n_users_blk, int d, void* ufrag, float* unorm,
                                      void* stream);
+/* The warm-position masks once per history and visiting order.  The exact warm-up of pda_score_topk4_* needs, for every block row, the
+ * train items among the first 256 visiting positions: 8 words per row, bit (pos & 31) of word (pos >> 5).  A call finds them by walking
+ * the histories of its block (inside the warm-up kernel, or from 98 304 users on in a kernel of its own).  For a history BY USER ID they
+ * depend on the train set and the visiting order only -- and the popularity head's order on pop alone, which survives weight updates:
+ *   pda_score_topk4_phase_mask_table    table u32 [n_rows][8] for every row of the CSR (n_rows = its rows), from the prep's positions
+ *   pda_score_topk4_phase_masked_f32 / _bf16   pda_score_topk4_* with the table as one more input: where one warm-up covers the front of the
+ *            whole order (n_splits == 1, or the shared warm-up of several splits) and the history is by user id, the warm-up gathers a row's
+ *            32 bytes at users[row] and no history is walked; otherwise (and with mask_table NULL) the call is pda_score_topk4_*.
+ *            Same keys.  A smaller warm-up (PDA_SWEEP_WARM_TILES) uses a prefix of the words.  Every users[row] must be < mask_table_rows
+ *            (a row beyond gets no mask).
+ *   pda_score_topk4_phase_mask_rows     the per-call kernel on one block as a call of its own: out u32 [n_users_blk rounded up to 128][8]
+ *   pda_score_topk4_phase_mask_offsets  offs[0 .. 1] = byte offset and bytes of the per-call kernel's words in the workspace of pda_score_topk4_*
+ * (tests compare the three). */
+int pda_score_topk4_phase_mask_table(const void* prep, int n_items_local, int d, int item_offset, const int64_t* hist_indptr,
+                                     const int32_t* hist_indices, int n_rows, uint32_t* table, void* stream);
+int pda_score_topk4_phase_masked_f32(const float* U, const float* I_shard, const void* prep, const float* pop_shard, const int32_t* users,
+                                     int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr,
+                                     const int32_t* hist_indices, int hist_row_mode, int K, int head, int early_stop, int n_splits,
+                                     const uint32_t* mask_table, int mask_table_rows, uint64_t* out_keys, void* workspace, void* stream);
+int pda_score_topk4_phase_masked_bf16(const uint16_t* U, const uint16_t* I_shard, const void* prep, const float* pop_shard, const int32_t* users,
+                                      int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr,
+                                      const int32_t* hist_indices, int hist_row_mode, int K, int head, int early_stop, int n_splits,
+                                      const uint32_t* mask_table, int mask_table_rows, uint64_t* out_keys, void* workspace, void* stream);
+int pda_score_topk4_phase_mask_rows(const void* prep, const int32_t* users, int n_users_blk, int item_offset, int n_items_local, int d,
+                                    const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int warm_tiles, uint32_t* out,
+                                    void* stream);
+int pda_score_topk4_phase_mask_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs);
 
 /* ---- train step variants -------------------------------------------------------------------------------------------------------------- */
 /* ---- The exact mini-batch SGD step without atomics (round 3; pda_bpr_plan.hip): plan + two launches -------------------------

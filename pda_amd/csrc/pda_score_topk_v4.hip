@@ -125,6 +125,11 @@ struct Args4 {
     unsigned char* ufrag_out;
     float* unorm_out;
     float* kth_ws;
+    // the warm-position masks of EVERY user id, built once per history and visiting order (warm_mask_table4_kernel): [hmask_tab_rows][2 kWarmTiles],
+    // row u = the words warm_mask4_kernel computes for a block row whose user is u.  Set only for a history by user id and one warm-up over the
+    // front of the whole order (n_splits == 1 in the warm-up's launch): warm4_kernel gathers a row's 32 bytes at its user id, nobody walks.
+    const uint32_t* hmask_tab;
+    int hmask_tab_rows;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -472,6 +477,24 @@ __global__ void __launch_bounds__(kThreads) warm_mask4_kernel(Args4 g, uint32_t*
     for (int q = tid; q < kUserTile * 2 * kWarmTiles; q += kThreads) dst[q] = hmask[q];
 }
 
+// The same for EVERY row of the history at once, once per history and visiting order: table[r][2 kWarmTiles], row r = the masks of the
+// history's row r over the first kWarmTiles tiles of the whole order.  For a history by user id that is what warm_mask4_kernel computes for
+// a block row whose user is r, whatever the block -- the result depends on the train set and the order alone (the popularity head's order
+// on pop alone: it survives weight updates).  g: hist_row_mode = PDA_HIST_BY_BLOCK_ROW over all n_users_blk = n_rows rows, n_splits = 1.
+__global__ void __launch_bounds__(kThreads) warm_mask_table4_kernel(Args4 g, uint32_t* __restrict__ table) {
+    __shared__ unsigned hmask[kUserTile * 2 * kWarmTiles];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int utile = blockIdx.x;
+    const int nwarm = min(g.warm_tiles, g.n_tiles);
+    for (int q = tid; q < kUserTile * 2 * kWarmTiles; q += kThreads) hmask[q] = 0u;
+    __syncthreads();
+    warm_hist_walk(g, hmask, utile, 0, nwarm, wave, lane);
+    __syncthreads();
+    const size_t r0 = (size_t)utile * kUserTile;
+    for (int q = tid; q < kUserTile * 2 * kWarmTiles; q += kThreads)
+        if (r0 + (size_t)(q / (2 * kWarmTiles)) < (size_t)g.n_users_blk) table[r0 * (2 * kWarmTiles) + q] = hmask[q];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // warm-up: the first kWarmTiles tiles of every split, exact (fp32 matrix cores, k order of v1), lists -> out_keys
 // ---------------------------------------------------------------------------------------------------------------------
@@ -511,8 +534,14 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) warm4_kernel(Arg
     }
     for (int q = tid; q < kUserTile * 2 * kWarmTiles; q += kThreads) hmask[q] = 0u;
     __syncthreads();
-    // train items among the warm positions: precomputed by warm_mask4_kernel (hmask_ws), or walked here
-    if (g.hmask_ws != nullptr) {
+    // train items among the warm positions: gathered from the table of all users (hmask_tab: 16 bytes per lane at the row's user id, beside
+    // the loads of its user row), precomputed by warm_mask4_kernel (hmask_ws), or walked here
+    if (g.hmask_tab != nullptr) {
+        static_assert(2 * kWarmTiles == 8, "two 16-byte loads per row");
+        if (row_ok && (unsigned)uid < (unsigned)g.hmask_tab_rows)
+            *reinterpret_cast<u32x4*>(hmask + (wave * 32 + j) * (2 * kWarmTiles) + 4 * h) =
+                *reinterpret_cast<const u32x4*>(g.hmask_tab + (size_t)uid * (2 * kWarmTiles) + 4 * h);
+    } else if (g.hmask_ws != nullptr) {
         const uint32_t* src = g.hmask_ws + (size_t)blockIdx.x * kUserTile * 2 * kWarmTiles;
         for (int q = tid; q < kUserTile * 2 * kWarmTiles; q += kThreads) hmask[q] = src[q];
     } else if (g.hist_indptr != nullptr && !(PDA_W4_ABL & 1)) {
@@ -2092,7 +2121,8 @@ extern "C" size_t pda_score_topk4_workspace_bytes(int n_users_blk, int n_items_l
 int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, const float* pop_shard, const int32_t* users,
                int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr, const int32_t* hist_indices,
                int hist_row_mode, int K, int head, int early_stop, int n_splits, uint64_t* out_keys, void* workspace, hipStream_t s,
-               int phase = 3, const float* seed = nullptr, int warm_tiles = 0, const int* n_users_dev = nullptr) {
+               int phase = 3, const float* seed = nullptr, int warm_tiles = 0, const int* n_users_dev = nullptr,
+               const uint32_t* mask_table = nullptr, int mask_table_rows = 0) {
     if (!U || !I_shard || !prep || !users || !out_keys || !workspace) return PDA_ERR_ARG;
     if (n_users_blk <= 0 || n_items_local <= 0 || item_offset < 0) return PDA_ERR_ARG;
     if (K < 1 || K > PDA_MAX_K) return PDA_ERR_ARG;
@@ -2184,7 +2214,13 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
         PDA_CHECK_LAUNCH();
         g.bloom = bloom;
     }
-    if (hist_indptr && (phase & 1) && n_users_blk >= 98304) {
+    // the warm-position masks: from the caller's table of all users (pda_score_topk4_phase_mask_table) wherever ONE warm-up covers the front
+    // of the whole visiting order -- blocks of any size; no walk, no warm_mask4_kernel
+    if (mask_table != nullptr && hist_indptr && hist_row_mode == PDA_HIST_BY_USER_ID && (phase & 1) && n_users_dev == nullptr &&
+        (n_splits == 1 || g.warm_shared)) {
+        g.hmask_tab = mask_table;
+        g.hmask_tab_rows = mask_table_rows;
+    } else if (hist_indptr && (phase & 1) && n_users_blk >= 98304) {
         // the train-item bits of the warm positions, by a kernel of its own (see warm_mask4_kernel) -- where it pays for its launch:
         // 1.35 -> 1.29 ms per early-terminating sweep of 262 144 users, but 0.267 -> 0.277 ms at 50 000
         uint32_t* hm = reinterpret_cast<uint32_t*>(wsb + W.hmask);
@@ -2375,6 +2411,13 @@ extern "C" int pda_debug_v5_log(unsigned* out, int n_words, int reset) {
     return PDA_OK;
 }
 #endif
+#ifdef PDA_V5_EXITPROF
+extern "C" int pda_debug_v5_exitprof(unsigned long long* out, int n_workgroups) {     /* [n_workgroups][4 waves][8] of the LAST sweep5_kernel launch */
+    if (!out || n_workgroups < 1 || n_workgroups > kXpMaxWg) return PDA_ERR_ARG;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pda_v5_exitprof), (size_t)n_workgroups * 4 * 8 * sizeof(unsigned long long)) != hipSuccess) return PDA_ERR_LAUNCH;
+    return PDA_OK;
+}
+#endif
 #ifdef PDA_V4_PROF
 extern "C" int pda_debug_prof4(unsigned long long* out16, int reset) {     /* 24 words */
     if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(pda_prof4), sizeof(unsigned long long) * 24) != hipSuccess) return PDA_ERR_LAUNCH;
@@ -2479,6 +2522,78 @@ extern "C" int pda_score_topk4_bf16(const uint16_t* U, const uint16_t* I_shard, 
                                     uint64_t* out_keys, void* workspace, void* stream) {
     return run_score4(U, I_shard, true, prep, pop_shard, users, n_users_blk, item_offset, n_items_local, d, hist_indptr, hist_indices,
                       hist_row_mode, K, head, early_stop, n_splits, out_keys, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The one call with the warm-position masks of all users as one more input (see Args4::hmask_tab; NULL: pda_score_topk4_*)
+extern "C" int pda_score_topk4_phase_masked_f32(const float* U, const float* I_shard, const void* prep, const float* pop_shard, const int32_t* users,
+                                                int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr,
+                                                const int32_t* hist_indices, int hist_row_mode, int K, int head, int early_stop, int n_splits,
+                                                const uint32_t* mask_table, int mask_table_rows, uint64_t* out_keys, void* workspace, void* stream) {
+    if (mask_table != nullptr && mask_table_rows <= 0) return PDA_ERR_ARG;
+    return run_score4(U, I_shard, false, prep, pop_shard, users, n_users_blk, item_offset, n_items_local, d, hist_indptr, hist_indices,
+                      hist_row_mode, K, head, early_stop, n_splits, out_keys, workspace, reinterpret_cast<hipStream_t>(stream), 3, nullptr, 0, nullptr,
+                      mask_table, mask_table_rows);
+}
+extern "C" int pda_score_topk4_phase_masked_bf16(const uint16_t* U, const uint16_t* I_shard, const void* prep, const float* pop_shard, const int32_t* users,
+                                                 int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr,
+                                                 const int32_t* hist_indices, int hist_row_mode, int K, int head, int early_stop, int n_splits,
+                                                 const uint32_t* mask_table, int mask_table_rows, uint64_t* out_keys, void* workspace, void* stream) {
+    if (mask_table != nullptr && mask_table_rows <= 0) return PDA_ERR_ARG;
+    return run_score4(U, I_shard, true, prep, pop_shard, users, n_users_blk, item_offset, n_items_local, d, hist_indptr, hist_indices,
+                      hist_row_mode, K, head, early_stop, n_splits, out_keys, workspace, reinterpret_cast<hipStream_t>(stream), 3, nullptr, 0, nullptr,
+                      mask_table, mask_table_rows);
+}
+
+// The warm-position masks as calls of their own.  Both walk with the prep's pos_of; one warm-up over the front of the whole order (n_splits = 1).
+static Args4 mask_args4(const void* prep, const int32_t* users, int n_rows, int item_offset, int n_items_local, int d, const int64_t* hist_indptr,
+                        const int32_t* hist_indices, int hist_row_mode, int warm_tiles) {
+    const Prep4Layout L = prep4_layout(n_items_local, d);
+    const unsigned char* pb = reinterpret_cast<const unsigned char*>(prep);
+    Args4 g{};
+    g.users = users;
+    g.hist_indptr = hist_indptr;
+    g.hist_indices = hist_indices;
+    g.pos_of = reinterpret_cast<const int*>(pb + L.pos_of);
+    g.n_users_blk = n_rows;
+    g.item_offset = item_offset;
+    g.n_items_local = n_items_local;
+    g.hist_row_mode = hist_row_mode;
+    g.n_splits = 1;
+    g.n_tiles = L.n_tiles;
+    g.warm_tiles = warm_tiles;
+    return g;
+}
+//   pda_score_topk4_phase_mask_table   table u32 [n_rows][8]: every row of the history (n_rows = rows of the CSR), all four warm tiles
+extern "C" int pda_score_topk4_phase_mask_table(const void* prep, int n_items_local, int d, int item_offset, const int64_t* hist_indptr,
+                                                const int32_t* hist_indices, int n_rows, uint32_t* table, void* stream) {
+    if (!prep || !hist_indptr || !hist_indices || !table || n_rows <= 0 || n_items_local <= 0 || item_offset < 0) return PDA_ERR_ARG;
+    if (d != 64 && d != 128 && d != 256) return PDA_ERR_UNSUPPORTED;
+    const Args4 g = mask_args4(prep, nullptr, n_rows, item_offset, n_items_local, d, hist_indptr, hist_indices, PDA_HIST_BY_BLOCK_ROW, kWarmTiles);
+    hipLaunchKernelGGL(warm_mask_table4_kernel, dim3((unsigned)((n_rows + kUserTile - 1) / kUserTile)), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), g, table);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+//   pda_score_topk4_phase_mask_rows    warm_mask4_kernel on one block: out u32 [n_users_blk rounded up to 128][8] (tests compare the table with it)
+extern "C" int pda_score_topk4_phase_mask_rows(const void* prep, const int32_t* users, int n_users_blk, int item_offset, int n_items_local, int d,
+                                               const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int warm_tiles, uint32_t* out,
+                                               void* stream) {
+    if (!prep || !users || !hist_indptr || !hist_indices || !out || n_users_blk <= 0 || n_items_local <= 0 || item_offset < 0) return PDA_ERR_ARG;
+    if (warm_tiles < 1 || warm_tiles > kWarmTiles) return PDA_ERR_ARG;
+    if (d != 64 && d != 128 && d != 256) return PDA_ERR_UNSUPPORTED;
+    const Args4 g = mask_args4(prep, users, n_users_blk, item_offset, n_items_local, d, hist_indptr, hist_indices, hist_row_mode, warm_tiles);
+    hipLaunchKernelGGL(warm_mask4_kernel, dim3((unsigned)((n_users_blk + kUserTile - 1) / kUserTile)), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), g, out);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+//   pda_score_topk4_phase_mask_offsets offs[0 .. 1] = byte offset and bytes, in the workspace of pda_score_topk4_*, of the words warm_mask4_kernel
+//                                      leaves there (blocks from 98 304 users on, no table): [128-user tiles x warm-up splits][128][8]
+extern "C" int pda_score_topk4_phase_mask_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs) {
+    if (n_users_blk <= 0 || n_items_local <= 0 || (d != 64 && d != 128 && d != 256) || !offs) return PDA_ERR_ARG;
+    if (n_splits <= 0) n_splits = pda_score_topk4_auto_splits(n_users_blk, n_items_local, d);
+    const Ws4 W = ws4_layout(n_users_blk, d, n_splits);
+    offs[0] = W.hmask;
+    offs[1] = W.regroup - W.hmask;
+    return PDA_OK;
 }
 
 // What a phase-2 sweep of the huge geometry makes of a user block by itself (uprep5_kernel), as a call of its own, and where the one-call path

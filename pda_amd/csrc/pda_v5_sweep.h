@@ -47,6 +47,18 @@ __device__ unsigned pda_v5_log[1 << 18];      // debug build: [0] = entries used
 #else
 #define V5LOG(kind, a, b) do {} while (0)
 #endif
+#ifdef PDA_V5_EXITPROF
+// profiling build (tools/build_variant.sh exitprof -DPDA_V5_EXITPROF; read by tools/time_huge_exits.py): what a wave spends OUTSIDE its asm loops,
+// in ticks of the constant 100 MHz wall clock -- per (workgroup, wave): [0] in extract, [1] in rescore_ring behind the extracts, [2] from the end
+// of an exit's work to the next call of a loop body (thresholds, the decided half-tile, the barrier; the AGPR reload and the restart of the DMA
+// pipeline happen inside the asm statement and are not separable here), [3] everything between a loop's return and the next loop's call,
+// [4] exits (returns with a flag), [5] the whole kernel, [6] before the first entry, [7] sort and emit.  No code in the product build.
+constexpr int kXpMaxWg = 4096;
+__device__ unsigned long long pda_v5_exitprof[kXpMaxWg * 4 * 8];
+#define XP(...) __VA_ARGS__
+#else
+#define XP(...)
+#endif
 constexpr int kRing5 = 192;           // candidate ring entries per wave (u64 each); a push needs 64 free
 
 
@@ -78,6 +90,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x % g.n_splits, utile = blockIdx.x / g.n_splits;
+    XP(unsigned long long xp[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long xp_k0 = wall_clock64(); unsigned long long xp_out = 0, xp_re = 0;)
     // the exact lists: the hand-over rows of the warm-up IN PLACE (a one-call sweep; the rows of the workgroup's padding do not exist
     // and are never touched: no candidate, no output), else the workgroup's rows of the workspace
     uint64_t* lists = g.handover != nullptr ? g.handover + ((size_t)split * g.n_users_blk + (size_t)utile * UT) * kCap4
@@ -332,6 +345,9 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             n_cand += ring_n;
             ring_n = 0;
         };
+#ifdef PDA_V5_EXTRACT_OLD
+        // (A/B build, tools/build_variant.sh extractold -DPDA_V5_EXTRACT_OLD: the exit path before the fused extract -- one call per half-tile,
+        // one user block at a time, the user fragments loaded twice)
         // ---- a half-tile that raised a flag, scored again with compiler-visible MFMAs: every pair whose bound reaches the user's
         // threshold -> the ring
         auto extract = [&](unsigned ft) __attribute__((always_inline)) {
@@ -386,6 +402,141 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
                 }
             }
         };
+#else
+        // ---- the two half-tiles behind an exit at half-tile hx (hx - 2 raised the flag, the flags of hx - 1 were still being worked out), scored
+        // again with compiler-visible MFMAs in ONE pass over the user blocks: every pair whose bound reaches the user's threshold -> the ring.
+        // With one wave per SIMD nothing hides a round trip to the user image (the rows cannot stay in AGPRs across the asm statements), and a pass
+        // per half-tile over one block at a time was 2 NU exposed round trips per exit: here both half-tiles' item fragments are read from their LDS
+        // slots once (d >= 128: once per batch), a block's user fragments are loaded once for both, and the blocks come in batches of BU whose loads are all in flight together
+        // (64 VGPRs of fragments), the next batch requested behind the last MFMA of the current one, over its pushes -- NU / BU waits.
+        // (Two batches in flight -- the next one requested BEFORE the current one's MFMAs -- cost 120 - 430 bytes of scratch per lane at d >= 128;
+        // with a batch's MFMAs at a quarter of a round trip, more loads per wait beat the overlap anyway.)  The thresholds are read once per batch:
+        // a rescoring inside the batch may have raised one since, which only sends a pair to the exact rescoring that the old path would have
+        // dropped (keys cannot change).  A batch's masks travel as one 64-bit word per lane to a rolled loop of pushes: one copy of the push code
+        // (and of rescore_ring) instead of one per block.
+        auto extract2 = [&](unsigned hx, unsigned hl) __attribute__((always_inline)) {     // hl: hlim, the end handed to the tested body
+            // (below hl: what the tested body scored behind its end are copies of half-tile hl - 1)
+            const bool on0 = hx >= 2u && hx - 2u < hl, on1 = hx >= 1u && hx - 1u < hl;
+            if (!on0 && !on1) return;
+            constexpr int NR = 8, BU = D == 256 ? 2 : 4, NB = NU / BU, NF = BU * NK;
+            static_assert(NU % BU == 0 && 2 * BU * NR <= 64, "the masks of a batch: one 64-bit word per lane");
+            // an absent half-tile is stood in for by the present one (valid addresses; its masks are dropped)
+            const unsigned f0 = on0 ? hx - 2u : hx - 1u, f1 = on1 ? hx - 1u : hx - 2u;
+            // accumulator register r of the lane <-> item of the half-tile (r = 4 ib + register of chain ib)
+            auto item_of = [&](int r) __attribute__((always_inline)) -> unsigned {
+                return 16u * (r >> 2) + 4u * hh + (r & 3);
+            };
+            unsigned pos00 = 0, pos01 = 0;                               // visiting position of each half-tile's first item
+            float ctv[2], pmx[2];
+            const unsigned char* tbv[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const unsigned ft = t ? f1 : f0;
+                const unsigned T = t0 + (ft >> 1) * (unsigned)g.n_splits;                   // its 64-item tile
+                if (t) pos01 = T * 64u + (ft & 1u) * 32u; else pos00 = T * 64u + (ft & 1u) * 32u;
+                const float2 mt = *reinterpret_cast<const float2*>(g.meta5 + 4 * (size_t)(2u * T + (ft & 1u)));
+                ctv[t] = __builtin_fmaf(eu, mt.y, mt.x);
+                pmx[t] = mt.x;
+                tbv[t] = tiles + (ft & (kNSlot5 - 1)) * SS + j * (2 * D);
+            }
+            // a half-tile's item fragments: 8 NK VGPRs.  d = 64: both half-tiles' stay in registers for the whole pass; d >= 128 (32 / 64 VGPRs
+            // each): one at a time, read from its LDS slot again for every batch (a fraction of the batch's round trip to the user image) -- both
+            // at once cost sweep5_kernel<128> 120 bytes of scratch per lane
+            constexpr bool AF_ONCE = D == 64;
+            u32x4 af[AF_ONCE ? 2 : 1][2 * NK];
+            auto load_af = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+                for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+                    for (int k = 0; k < NK; ++k)
+                        af[AF_ONCE ? t : 0][ib * NK + k] = *reinterpret_cast<const u32x4*>(tbv[t] + ib * 16 * (2 * D) + (((4 * k + hh) ^ swz5<D>(j)) << 4));
+            };
+            // the fragments of batch b: blocks BU b .. BU b + BU - 1, NK k-steps each -- NF consecutive 1 KiB fragments of the wave's image
+            // (addresses: a uniform base per batch, the lane's 32-bit offset per 4 KiB and an immediate.  The offset passes through an empty asm
+            // statement: formed from the loop-invariant lane16 alone, the 14 per-lane 64-bit addresses were hoisted out of the sweep's loop, over
+            // the asm loops, and spilled -- 112 bytes of scratch per lane)
+            unsigned l16 = lane16;
+            asm volatile("" : "+v"(l16));
+            u32x4 cur[NF];
+            auto load_cur = [&](int b) __attribute__((always_inline)) {
+                const unsigned char* pb = my_ufrag + (size_t)b * (NF * 1024);
+#pragma unroll
+                for (int i = 0; i < NF; ++i) cur[i] = *reinterpret_cast<const u32x4*>(pb + (size_t)(l16 + (unsigned)(i >> 2) * 4096u) + (i & 3) * 1024);
+            };
+            if constexpr (AF_ONCE) {
+                load_af(0);
+                load_af(1);
+            }
+            load_cur(0);
+#pragma unroll 1
+            for (int b = 0; b < NB; ++b) {
+                float tlv[BU];
+#pragma unroll
+                for (int ub = 0; ub < BU; ++ub) tlv[ub] = thr_of(b * BU + ub);
+                uint64_t mm = 0ull;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    if constexpr (!AF_ONCE) load_af(t);
+#pragma unroll
+                    for (int ub = 0; ub < BU; ++ub) {
+                        const float tl = tlv[ub];
+                        const bool clampy = pmx[t] > tl;
+                        uint32_t m = 0;
+#pragma unroll
+                        for (int ib = 0; ib < 2; ++ib) {
+                            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int k = 0; k < NK; ++k)
+                                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[AF_ONCE ? t : 0][ib * NK + k]), __builtin_bit_cast(bf16x8, cur[ub * NK + k]), acc, 0, 0, 0);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) m |= (acc[r] + ctv[t] > tl) ? (1u << (4 * ib + r)) : 0u;
+                        }
+                        if (__any(clampy)) {
+                            // (rare: a user whose threshold lies below a popularity of this half-tile -- a head pop x exp(s), s <= 0, may qualify)
+#pragma unroll
+                            for (int r = 0; r < NR; ++r) {
+                                const unsigned pp = (t ? pos01 : pos00) + item_of(r);
+                                const float pi = clampy ? *reinterpret_cast<const float*>(g.rows + (size_t)pp * RB4 + 2 * D + 32) : 0.f;
+                                m |= (clampy && pi > tl) ? (1u << r) : 0u;
+                            }
+                        }
+                        if (!(t ? on1 : on0)) m = 0u;
+                        mm |= (uint64_t)m << (NR * (2 * ub + t));
+                    }
+                }
+                // (the fragments are consumed: the next batch's loads travel over the pushes below)
+                const int bn = min(b + 1, NB - 1);
+                if (b + 1 < NB) load_cur(bn);
+                if (__any(mm != 0ull)) {
+#pragma unroll 1
+                    for (int q = 0; q < 2 * BU; ++q) {                   // (block q >> 1 of the batch, half-tile q & 1)
+                        uint32_t m = (uint32_t)(mm >> (NR * q)) & ((1u << NR) - 1u);
+                        const int u = b * BU + (q >> 1);
+                        const unsigned pos0 = (q & 1) ? pos01 : pos00;
+                        while (__any(m != 0u)) {
+                            if (ring_n + 64u > (unsigned)kRing5) {
+                                // (a full ring in mid-pass, rare: the fragments are not carried across the rescoring -- 64 VGPRs of table rows -- but
+                                // read again behind it)
+                                rescore_ring();
+                                if constexpr (AF_ONCE) {
+                                    load_af(0);
+                                    load_af(1);
+                                }
+                                load_cur(bn);
+                            }
+                            const bool act = m != 0u;
+                            const int r = __builtin_ctz(m | 0x10000u);
+                            m &= ~(1u << r);
+                            const uint64_t pm = __ballot(act);
+                            const unsigned slot = ring_n + (unsigned)__builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0));
+                            if (act) my_ring[slot] = ((uint64_t)(unsigned)(UBW * u + j) << 32) | (uint64_t)(pos0 + item_of(r));
+                            ring_n += (unsigned)__popcll(pm);
+                        }
+                    }
+                }
+            }
+        };
+#endif
 
         // ---- the workgroup's DECIDED half-tile: the first local half-tile from which no pair of the rest of the split can reach ANY row's
         // threshold -- the criterion that ends generation 4's early-terminating sweeps (stop_predict4_kernel, the votes of sweep4_kernel),
@@ -440,6 +591,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
                 if (h < hend) {
                     ++n_entries;
                     n_free = hend - h;
+                    XP(if (xp_out != 0) { const unsigned long long t_ = wall_clock64(); xp[3] += t_ - xp_out; xp[2] += t_ - xp_re; xp_out = 0; } else xp[6] = wall_clock64() - xp_k0;)
                     Loop6Free<D, NU>::run(h, issued, hend, ring_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits, (unsigned)img, (unsigned)(img >> 32), my_ufrag, lane16);
                     V5LOG(14u, h, n_free);
                 }
@@ -447,8 +599,10 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             }
             hlim = min(hlim, hf);
             ++n_entries;
+            XP(if (xp_out != 0) { const unsigned long long t_ = wall_clock64(); xp[3] += t_ - xp_out; xp[2] += t_ - xp_re; } else xp[6] = wall_clock64() - xp_k0;)
             Loop6<D, NU>::run(h, issued, reason, hlim, ring_lds, flags_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits,
                               (unsigned)img, (unsigned)(img >> 32), (unsigned)meta, (unsigned)(meta >> 32), eu, tmin, my_ufrag, thr, lane16);
+            XP(xp_out = wall_clock64(); xp_re = xp_out;)
             V5LOG(reason, h, issued);
             if (reason == 0u) {
                 if (hlim == hend) break;
@@ -473,12 +627,18 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             // every wave of the workgroup left at half-tile h because SOME wave's lanes flagged h - 2; the flags of h - 1 were still being
             // worked out: both are scored again here (a half-tile without a candidate of this wave costs its 8 NK MFMAs)
             [[maybe_unused]] const unsigned before = ring_n + n_cand;
+#ifdef PDA_V5_EXTRACT_OLD
             // (below hlim: what the tested body scored behind its end are copies of half-tile hlim - 1)
             if (h >= 2u && h - 2u < hlim) extract(h - 2u);
             if (h >= 1u && h - 1u < hlim) extract(h - 1u);
+#else
+            extract2(h, hlim);
+#endif
+            XP(const unsigned long long xp_a = wall_clock64(); xp[0] += xp_a - xp_out; xp[4] += 1;)
             V5LOG(10u, h, ring_n + n_cand - before);
             // (thresholds rise only through the lists: rescoring a ring that holds a pass's worth keeps them fresh enough)
             if (ring_n >= (unsigned)CPP) rescore_ring();
+            XP(xp_re = wall_clock64(); xp[1] += xp_re - xp_a;)
         }
         if (ring_n > 0u) rescore_ring();
         if (lane == 0) atomicAdd(g.stats + 1, n_cand);
@@ -494,6 +654,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
     // global memory was a dependent round trip per four keys (0.87 ms of a 9.0 ms launch -> 0.2).  A wave emits its own 256 rows.
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
+    XP(const unsigned long long xp_e0 = wall_clock64();)
     {
         constexpr int EB = 8;
         uint64_t* scr = crings + wave * kRing5;                          // (the rings are empty now)
@@ -558,6 +719,8 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             }
         }
     }
+    XP(xp[7] = wall_clock64() - xp_e0; xp[5] = wall_clock64() - xp_k0;
+       if (lane == 0 && blockIdx.x < (unsigned)kXpMaxWg) for (int q = 0; q < 8; ++q) pda_v5_exitprof[((size_t)blockIdx.x * 4 + wave) * 8 + q] = xp[q];)
 }
 
 template <int D, bool BF, bool S16, int UPW>

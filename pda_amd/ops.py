@@ -343,6 +343,35 @@ def hist_reordered(hist: "HistoryCSR", prep_ord: torch.Tensor, order: torch.Tens
     return out
 
 
+WARM_MASK_TABLE_BUDGET = 64 << 20      # bytes: 32 per row of the history, i.e. 2 M users (config 5's 10 M users keep the per-call kernel)
+
+
+def warm_mask_table(hist: "HistoryCSR", prep: torch.Tensor, order: Optional[torch.Tensor], item_offset: int, n: int, d: int) -> Optional[torch.Tensor]:
+    """pda_score_topk4_phase_mask_table: uint32 [rows of the history, 8], row u = the train-item bits of visiting positions 0 .. 255 for user id u
+    (what warm_mask4_kernel computes per call for a row whose user is u).  It depends on the train set and the visiting order only, so it is
+    cached on the HistoryCSR per (prep object, order object, item_offset, n, device), as hist_reordered is; a new order drops the old table.
+    None: a history by block row, a table beyond WARM_MASK_TABLE_BUDGET, or PDA_WARM_MASK_TABLE=0 (A/B runs, tests) -- the call then
+    walks the histories itself, as before."""
+    if hist is None or hist.mode != HIST_BY_USER_ID or os.environ.get("PDA_WARM_MASK_TABLE", "") == "0":
+        return None
+    rows = hist.indptr.numel() - 1
+    if rows <= 0 or rows * 32 > WARM_MASK_TABLE_BUDGET:
+        return None
+    cache = hist.__dict__.setdefault("_warm_mask_cache", [])
+    for pr, o, off, nn, dv, tab in cache:
+        if pr() is prep and (o() if o is not None else None) is order and off == item_offset and nn == n and dv == prep.device:
+            return tab
+    # the prep buffer and the order are held weakly, as _PREP4_CACHE holds its tensors: the history pins neither (hundreds of MB at config 3).
+    # A table goes when its prep or order died, or when its prep has a new order.
+    cache[:] = [c for c in cache if c[0]() is not None and (c[1] is None or c[1]() is not None)
+                and not (c[0]() is prep and c[2] == item_offset and c[3] == n)][-3:]
+    tab = torch.empty((rows, 8), dtype=torch.int32, device=prep.device)
+    check(_lib.load().pda_score_topk4_phase_mask_table(ptr(prep), n, d, item_offset, ptr(hist.indptr), ptr(hist.indices), rows, ptr(tab), stream_ptr()),
+          "pda_score_topk4_phase_mask_table")
+    cache.append((weakref.ref(prep), weakref.ref(order) if order is not None else None, item_offset, n, prep.device, tab))
+    return tab
+
+
 def mark_modified(*tensors):
     """Tell torch that a kernel wrote these tensors through raw pointers: bumps tensor._version, which is what keys
     the item_prep cache (and autograd's in-place checks)."""
@@ -625,10 +654,19 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
         es = hint | ((min(4, max(0, int(warm_tiles))) & 7) << 4)
         if os.environ.get("PDA_WARM_PER_SPLIT"):      # A/B measurements and cross-checks: every item split warms up on its own tiles (before round 4)
             es |= SWEEP_WARM_PER_SPLIT
-        fn = lib.pda_score_topk4_bf16 if bf else lib.pda_score_topk4_f32
-        check(fn(ptr(U), ptr(I_shard), ptr(prep), ptr(pop_shard), ptr(users), nu, item_offset, nloc, d,
-                 ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
-                 K, head, es, n_splits, ptr(out), ptr(ws), stream_ptr()), "pda_score_topk4")
+        # the warm-position masks of every user, built once per history and order: the call gathers them instead of walking the histories
+        # (one warm-up over the front of the whole order: one split, or the shared warm-up of several)
+        tab = warm_mask_table(hist, prep, order, item_offset, nloc, d) if hist and (n_splits == 1 or not (es & SWEEP_WARM_PER_SPLIT)) else None
+        if tab is not None:
+            fn = lib.pda_score_topk4_phase_masked_bf16 if bf else lib.pda_score_topk4_phase_masked_f32
+            check(fn(ptr(U), ptr(I_shard), ptr(prep), ptr(pop_shard), ptr(users), nu, item_offset, nloc, d,
+                     ptr(hist.indptr), ptr(hist.indices), hist.mode, K, head, es, n_splits, ptr(tab), tab.shape[0],
+                     ptr(out), ptr(ws), stream_ptr()), "pda_score_topk4_phase_masked")
+        else:
+            fn = lib.pda_score_topk4_bf16 if bf else lib.pda_score_topk4_f32
+            check(fn(ptr(U), ptr(I_shard), ptr(prep), ptr(pop_shard), ptr(users), nu, item_offset, nloc, d,
+                     ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
+                     K, head, es, n_splits, ptr(out), ptr(ws), stream_ptr()), "pda_score_topk4")
         if os.environ.get("PDA_CHECK_SWEEP_ERRORS"):          # (tests: synchronising) a bounded wait of the sweep ran out, or the huge geometry's self-check failed
             err = int(ws[0:4].view(torch.int32)[0])
             if err != 0:
@@ -643,6 +681,7 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
             stats["error"] = ws[0:4].view(torch.int32)           # 0, or which bounded wait of the sweep ran out (1 .. 4: hand-over words; 5, 6: huge geometry)
             stats["workspace"] = ws                               # (tests read the huge geometry's user image out of it: huge_image_offsets)
             stats["n_splits"] = n_splits
+            stats["warm_mask_table"] = tab                        # the cached table handed to the call, or None (that the library reads it: test_an_altered_table_changes_the_keys)
         return out
     if impl == "v2" and prune:
         prep, order = item_prep_ordered(I_shard, pop_shard if head == HEAD_POP else None)
@@ -763,6 +802,25 @@ def huge_image_offsets(nu: int, nloc: int, d: int, n_splits: int):
     offs = (C.c_size_t * 4)()
     check(_lib.load().pda_score_topk4_phase_image_offsets(nu, nloc, d, n_splits, C.cast(offs, C.c_void_p)), "pda_score_topk4_phase_image_offsets")
     return int(offs[0]), int(offs[1]), int(offs[2]), int(offs[3])
+
+
+def warm_mask_offsets(nu: int, nloc: int, d: int, n_splits: int):
+    """pda_score_topk4_phase_mask_offsets -> (byte offset, bytes) of the warm-position masks warm_mask4_kernel leaves in the workspace of a
+    pda_score_topk4_* call: uint32 [128-user tiles x warm-up splits][128][8]."""
+    offs = (C.c_size_t * 2)()
+    check(_lib.load().pda_score_topk4_phase_mask_offsets(nu, nloc, d, n_splits, C.cast(offs, C.c_void_p)), "pda_score_topk4_phase_mask_offsets")
+    return int(offs[0]), int(offs[1])
+
+
+def warm_mask_rows(prep: torch.Tensor, users: torch.Tensor, hist: "HistoryCSR", item_offset: int, nloc: int, d: int, warm_tiles: int = 4) -> torch.Tensor:
+    """pda_score_topk4_phase_mask_rows: warm_mask4_kernel on a block as a call of its own (one warm-up over the front of the whole order)
+    -> int32 [block rows padded to whole 128-user tiles, 8]."""
+    users = _need(users, torch.int32, "users")
+    nu = users.numel()
+    out = torch.empty((-(-nu // 128) * 128, 8), dtype=torch.int32, device=users.device)
+    check(_lib.load().pda_score_topk4_phase_mask_rows(ptr(prep), ptr(users), nu, item_offset, nloc, d, ptr(hist.indptr), ptr(hist.indices), hist.mode,
+                                                      warm_tiles, ptr(out), stream_ptr()), "pda_score_topk4_phase_mask_rows")
+    return out
 
 
 def huge_user_image(U: torch.Tensor, users: torch.Tensor):

@@ -114,6 +114,14 @@ int pda_score_topk4_phase_mask_rows(const void* prep, const int32_t* users, int 
                                     const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int warm_tiles, uint32_t* out,
                                     void* stream);
 int pda_score_topk4_phase_mask_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs);
+/* early_stop bit 11 of pda_score_topk4_* (beside PDA_SWEEP_WARM_PER_SPLIT, bit 10; results never depend on it).  The dense call of the
+ * huge geometry (PDA_SWEEP_HUGE, popularity head, no early termination, d <= 128, one warm-up over the front of the whole order) runs its
+ * exact warm-up as TWO kernels: a score kernel that keeps the 256 warm item rows in the LDS and only multiplies, and a select kernel at
+ * eight waves per SIMD that turns every row of 256 scores into its sorted best K (1 KB of scores per user through the workspace).  With
+ * this bit the call runs the one-kernel warm-up of every other sweep instead (A/B measurements; tests compare the two in one process).
+ * The word at workspace + 32 says which ran: 0 = the one kernel, 5 = the two.  Blocks of more than 2^21 users (2 GB of scores: the score
+ * kernel's 32-bit offsets) run the one kernel whatever the bit. */
+#define PDA_SWEEP_WARM_ONE_KERNEL 2048
 
 /* ---- train step variants -------------------------------------------------------------------------------------------------------------- */
 /* ---- The exact mini-batch SGD step without atomics (round 3; pda_bpr_plan.hip): plan + two launches -------------------------

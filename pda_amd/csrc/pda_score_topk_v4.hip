@@ -130,6 +130,9 @@ struct Args4 {
     // front of the whole order (n_splits == 1 in the warm-up's launch): warm4_kernel gathers a row's 32 bytes at its user id, nobody walks.
     const uint32_t* hmask_tab;
     int hmask_tab_rows;
+    // the dense call's exact warm-up as two kernels (warm_score5_kernel, warm_select5_kernel): [256 local item ids of the warm positions |
+    // n_users_blk x 64 warm_tiles scores as ordered uints, 0 = not a candidate].  NULL: warm4_kernel.
+    uint32_t* wscore;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -832,6 +835,364 @@ __global__ void __launch_bounds__(kThreads, (D <= 128 ? 2 : 1)) warm4_kernel(Arg
             g.pred_ws[2 * (size_t)rb] = predt[wave * 32 + lane];
             g.pred_ws[2 * (size_t)rb + 1] = nul[wave * 32 + lane];
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the dense call's warm-up as two kernels: the two halves of warm4_kernel want opposite shapes
+// ---------------------------------------------------------------------------------------------------------------------
+// warm_score5_kernel: the matrix half.  A persistent grid; every workgroup gathers the 64 warm_tiles item rows of the front of the whole
+// visiting order ONCE (fp32, warm4_kernel's swizzled row layout, ids and popularities beside them) and then only multiplies: a wave owns
+// 32 users at a time (unit u = 32 block rows; wave w of workgroup b takes the units b + G (w + 8 k), so small blocks spread over the CUs
+// first), holds their rows in registers, and has the next unit's rows and mask words in flight under the MFMAs of the current one.  No
+// barrier and no communication between waves behind the gather.  MFMAs, head and masks are warm4_kernel's, instruction for instruction;
+// the scores leave as ordered uints [user][position] (a half-wave writes 128 contiguous bytes per accumulator register).  It also writes
+// what warm4_kernel writes under ufrag_out -- the sweep's user image, the padded norms, the padding rows -- and counts the warm tiles.
+constexpr int kWS5Waves = 8, kWS5Threads = 64 * kWS5Waves;
+constexpr int kWarmPos = 64 * kWarmTiles;
+constexpr size_t warm_score5_lds(int d) { return (size_t)kWarmPos * d * 4 + kWarmPos * 8 + (size_t)kWS5Waves * 32 * 2 * kWarmTiles * 4; }
+
+template <int D, bool BF>
+__global__ void __launch_bounds__(kWS5Threads) warm_score5_kernel(Args4 g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int RB = row_bytes(D);
+    constexpr int NC = D / 8;
+    constexpr int CPR4 = D / 4;
+    float* Bt = reinterpret_cast<float*>(smem);                                   // [kWarmPos][D] fp32, swizzled
+    float* popw = Bt + kWarmPos * D;                                              // [kWarmPos]
+    int* idw = reinterpret_cast<int*>(popw + kWarmPos);                           // [kWarmPos]
+    unsigned* hmask = reinterpret_cast<unsigned*>(idw + kWarmPos);                // [waves][32][2 kWarmTiles]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int nwarm = g.warm_tiles;               // (the host runs this path only where the order is longer than the warm-up)
+    const int npos = 64 * nwarm;
+    for (int p = tid; p < npos; p += kWS5Threads) {
+        const float* tl = reinterpret_cast<const float*>(g.rows + (size_t)p * RB + 2 * D + 32);
+        popw[p] = tl[0];
+        idw[p] = reinterpret_cast<const int*>(tl)[1];
+    }
+    __syncthreads();
+    // (null items of a tail tile carry id 0: a valid row, masked by okw below)
+    for (int id = tid; id < npos * CPR4; id += kWS5Threads) {
+        const int jj = id / CPR4, ch = id % CPR4;
+        *reinterpret_cast<f32x4*>(Bt + jj * D + 4 * (ch ^ swz<D>(jj & 31))) = pda_load4<BF>(g.I, (size_t)idw[jj] * D + 4 * ch);
+    }
+    if (blockIdx.x == 0) {
+        for (int p = tid; p < kWarmPos; p += kWS5Threads) g.wscore[p] = p < npos ? (uint32_t)idw[p] : 0u;
+        if (tid == 0) g.stats[8] = 5u;            // which warm-up ran (workspace + 32): 0 = warm4_kernel, 5 = these two kernels
+    }
+    __syncthreads();
+
+    uint32_t* scores = g.wscore + kWarmPos;
+    const int utiles_w = (g.n_users_blk + kUserTile - 1) / kUserTile;
+    const int nunits = utiles_w * (kUserTile / 32);
+    const int G = (int)gridDim.x, stride = G * kWS5Waves;
+    unsigned* hm_l = hmask + wave * 32 * 2 * kWarmTiles;
+    static_assert(2 * kWarmTiles == 8, "two 16-byte loads per row");
+
+    // (rows beyond the block read user 0's row: a valid address, zeroed where the unit is consumed -- no branch per load)
+    auto row_uid = [&](int unit) -> int {
+        const int rb = unit * 32 + j;
+        return (unit < nunits && rb < g.n_users_blk) ? g.users[rb] : 0;
+    };
+    // a unit's user rows (this lane: half h of every 8-float chunk of row j) and its eight mask words (this lane: four of them; hm_on: they
+    // exist).  A unit beyond the block: nothing is requested and nothing may be read.
+    auto load_rows = [&](int unit_x, int uid, f32x4 (&a)[NC], u32x4& hm, bool& hm_on) __attribute__((always_inline)) {
+        if (unit_x >= nunits) return;                  // (wave-uniform)
+        const int rb = unit_x * 32 + j;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a[c] = pda_load4<BF>(g.U, (size_t)uid * D + 4 * h + 8 * c);
+        hm_on = false;
+        if (g.hmask_tab != nullptr) {
+            hm_on = rb < g.n_users_blk && (unsigned)uid < (unsigned)g.hmask_tab_rows;
+            hm = *reinterpret_cast<const u32x4*>(g.hmask_tab + (size_t)(hm_on ? uid : 0) * (2 * kWarmTiles) + 4 * h);
+        } else if (g.hmask_ws != nullptr) {
+            hm_on = true;
+            hm = *reinterpret_cast<const u32x4*>(g.hmask_ws + (size_t)rb * (2 * kWarmTiles) + 4 * h);
+        }
+    };
+    unsigned long long n_tiles_done = 0ull;
+    auto run_unit = [&](const int unit_in, f32x4 (&areg)[NC], const u32x4& hm_in, const bool hm_on) __attribute__((always_inline)) {
+        // (the unit's number, wave-uniform, read into a scalar register: everything derived from it is formed here, per unit, instead of
+        // living as thirty loop-carried induction variables in scratch memory)
+        const int unit = __builtin_amdgcn_readfirstlane(unit_in);
+        const int row_blk = unit * 32 + j;
+        if (unit * 32 + 32 > g.n_users_blk) {           // (wave-uniform: the block's last unit) rows beyond the block are zero rows
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < NC; ++c) areg[c] = row_blk < g.n_users_blk ? areg[c] : z;
+        }
+        const u32x4 hz = {0u, 0u, 0u, 0u};
+        const u32x4 hmv = hm_on ? hm_in : hz;
+        *reinterpret_cast<u32x4*>(hm_l + j * (2 * kWarmTiles) + 4 * h) = hmv;
+        {
+            // the huge geometry's user image and padded norms: warm4_kernel's bytes (see there), the norm summed in its order
+            constexpr int NK5 = D / 32;
+            unsigned char* fb = g.ufrag_out + ((size_t)(row_blk >> 4) * (NK5 * 64) + (size_t)(row_blk & 15)) * 16 + 8 * h;
+            float ssc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const f32x4 v = areg[c];
+                uint2 w;
+                w.x = bf16_rne(v[0]) | (bf16_rne(v[1]) << 16);
+                w.y = bf16_rne(v[2]) | (bf16_rne(v[3]) << 16);
+                *reinterpret_cast<uint2*>(fb + ((c >> 2) * 64 + 16 * (c & 3)) * 16) = w;
+                float ss = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float sq = v[k] * v[k];
+                    ss += sq + __shfl_xor(sq, 32, 64);
+                }
+                ssc[c] = ss;
+                __builtin_amdgcn_sched_barrier(0);      // (one chunk's squares and shuffles at a time: all 64 at once do not fit beside two units' rows)
+            }
+#pragma unroll
+            for (int o = NC / 2; o > 0; o >>= 1)
+#pragma unroll
+                for (int c = 0; c < o; ++c) ssc[c] += ssc[c + o];
+            if (h == 0) g.unorm_out[row_blk] = sqrtf(ssc[0]) * 1.0009765625f * 1.0001f;
+        }
+        if ((unit & (kUserTile / 32 - 1)) == 0) n_tiles_done += (unsigned long long)(2 * nwarm);
+        pda_wave_sync();
+        const int j_lane = j, h_lane = h;
+#pragma unroll 1
+        for (int ht = 0; ht < 2 * nwarm; ++ht) {
+            // (the lane's coordinates pass through an empty asm statement per half-tile: the sixteen swizzled LDS offsets, the sixteen store
+            // offsets and the sixteen shuffle sources derived from them are formed here, a few VALU instructions beside 4 096 cycles of
+            // MFMAs, instead of being hoisted over the loop into fifty registers that the two units' user rows need)
+            int j = j_lane, h = h_lane;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(j), "+v"(h));
+#endif
+            const int bswz = swz<D>(j);
+            const float* brow = Bt + (ht * 32 + j) * D;
+            f32x16 acc0 = zero16v(), acc1 = zero16v();
+            // (the item chunks of step c + 2 are read in front of the MFMAs of step c, and the scheduler is kept from reading further ahead:
+            // with all sixteen chunks in flight the loop does not fit 256 registers beside two units' user rows)
+            f32x4 b0 = *reinterpret_cast<const f32x4*>(brow + 4 * (h ^ bswz));
+            f32x4 b1 = *reinterpret_cast<const f32x4*>(brow + 4 * ((2 + h) ^ bswz));
+#pragma unroll
+            for (int c = 0; c < NC; c += 2) {
+                f32x4 n0 = b0, n1 = b1;
+                if (c + 2 < NC) {
+                    n0 = *reinterpret_cast<const f32x4*>(brow + 4 * ((2 * c + 4 + h) ^ bswz));
+                    n1 = *reinterpret_cast<const f32x4*>(brow + 4 * ((2 * c + 6 + h) ^ bswz));
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[c][q], b0[q], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[c + 1][q], b1[q], acc1, 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                b0 = n0;
+                b1 = n1;
+            }
+            const f32x16 accx = acc0 + acc1;
+            const bool okw = (ht * 32 + j) < g.n_items_local;
+            const float pv = popw[ht * 32 + j];
+            const unsigned hb_mine = hm_l[j * (2 * kWarmTiles) + ht];
+            const bool any_hb = __any(hb_mine != 0u);
+            // (32-bit element offsets from one uniform base: the host keeps n_users_blk x 256 words below 2^31)
+            const uint32_t soff = (uint32_t)(unit * 32 + 4 * h) * (uint32_t)npos + (uint32_t)(ht * 32 + j);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                float sc = accx[r];
+                sc = (sc > 0.0f ? sc + 1.0f : __expf(sc)) * pv;
+                bool p = okw && (sc >= -INFINITY);                                             // (NaN never ranks)
+                if (any_hb) {
+                    const uint32_t hbr = (uint32_t)__shfl((int)hb_mine, row, 64);              // train items never enter
+                    if ((hbr >> j) & 1u) p = false;
+                }
+                // (no test of the row: the region holds whole 128-user tiles)
+                scores[soff + (uint32_t)((r & 3) + 8 * (r >> 2)) * (uint32_t)npos] = p ? pda_ordf(sc + 0.0f) : 0u;
+            }
+        }
+        pda_wave_sync();
+    };
+    // two register sets take turns (no copies): the next unit's rows and mask words are requested before the MFMAs of the current one
+    int unit = (int)blockIdx.x + G * wave;
+    f32x4 ra[NC], rb_[NC];
+    u32x4 ha = {0u, 0u, 0u, 0u}, hb = {0u, 0u, 0u, 0u};
+    bool oa = false, ob = false;
+    load_rows(unit, row_uid(unit), ra, ha, oa);
+    int uid_n = row_uid(unit + stride);
+    while (unit < nunits) {
+        load_rows(unit + stride, uid_n, rb_, hb, ob);
+        uid_n = row_uid(unit + 2 * stride);
+        run_unit(unit, ra, ha, oa);
+        unit += stride;
+        if (unit >= nunits) break;
+        load_rows(unit + stride, uid_n, ra, ha, oa);
+        uid_n = row_uid(unit + 2 * stride);
+        run_unit(unit, rb_, hb, ob);
+        unit += stride;
+    }
+    if (lane == 0 && n_tiles_done != 0ull) atomicAdd(reinterpret_cast<unsigned long long*>(g.stats + 2), n_tiles_done);
+    // rows of the sweep's padding (whole 1 024-user workgroups) behind the last 128-user tile: zeros, norm 0
+    if ((int)blockIdx.x == (nunits - 1) % G) {
+        const size_t r0 = (size_t)utiles_w * kUserTile, r1 = ((size_t)g.n_users_blk + kUT5 - 1) / kUT5 * kUT5;
+        const u32x4 z = {0u, 0u, 0u, 0u};
+        for (size_t q = r0 * (2 * D) + (size_t)tid * 16; q < r1 * (2 * D); q += (size_t)kWS5Threads * 16) *reinterpret_cast<u32x4*>(g.ufrag_out + q) = z;
+        for (size_t r = r0 + tid; r < r1; r += kWS5Threads) g.unorm_out[r] = 0.f;
+    }
+}
+
+// warm_select5_kernel: the selection half, written for occupancy (eight waves per SIMD hide the dependent compare -> ballot -> popcount
+// chains).  One row per wave-operation: its 64 warm_tiles scores are one coalesced load, four per lane.  Two rows at a time (independent
+// chains share the issue slots): a bisection over the ordered-uint domain to a threshold with K <= count <= kCap4 -- everything about it
+// is wave-uniform --, the survivors compacted into an LDS list as keys, ranked against each other (compact_list's unsorted path), the
+// best K written out sorted.  More than kCap4 survivors at the converged threshold (ties at the K-th value): the descent goes on over the
+// key's low word, so the smaller item ids win -- keys are unique, the result is the same set warm4_kernel's general append path keeps.
+constexpr int kSelRows = 16;          // rows per wave
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) warm_select5_kernel(Args4 g) {
+    constexpr int CAP = kCap4;
+    __shared__ uint64_t lists[4][2][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = g.K, n = g.n_users_blk;
+    const int npos = 64 * g.warm_tiles;
+    const uint32_t* scores = g.wscore + kWarmPos;
+    const int rb0 = ((int)blockIdx.x * 4 + wave) * kSelRows;
+    if (rb0 >= n) return;
+    // the low words of this lane's four positions (the same for every row)
+    const u32x4 idv = *reinterpret_cast<const u32x4*>(g.wscore + 4 * lane);
+    uint32_t klo[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) klo[q] = 0xFFFFFFFFu - (uint32_t)(g.item_offset + (int)idv[q]);
+    const bool lane_on = 4 * lane < npos;
+    float kth_mine = -INFINITY;
+
+    auto count32 = [&](const u32x4& v, uint32_t t) __attribute__((always_inline)) -> int {
+        return __popcll(__ballot(v[0] >= t)) + __popcll(__ballot(v[1] >= t)) + __popcll(__ballot(v[2] >= t)) + __popcll(__ballot(v[3] >= t));
+    };
+    auto key_of = [&](const u32x4& v, int q) __attribute__((always_inline)) -> uint64_t { return ((uint64_t)v[q] << 32) | (uint64_t)klo[q]; };
+    auto count64 = [&](const u32x4& v, uint64_t t) __attribute__((always_inline)) -> int {
+        int c = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c += __popcll(__ballot(key_of(v, q) >= t));
+        return c;
+    };
+
+#pragma unroll 1
+    for (int it = 0; it < kSelRows; it += 2) {
+        if (rb0 + it >= n) break;
+        u32x4 v[2];
+        uint32_t t[2], hi[2];
+        int ct[2];
+        bool need[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int rb = rb0 + it + s;
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            v[s] = (lane_on && rb < n) ? *reinterpret_cast<const u32x4*>(scores + (size_t)rb * npos + 4 * lane) : z;
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            ct[s] = count32(v[s], 1u);
+            t[s] = 1u;
+            hi[s] = 0u;
+            need[s] = ct[s] > CAP;
+        }
+        if (need[0] || need[1]) {
+            // between the row's smallest and largest score (~ the log domain for positive scores: a handful of steps); invariant:
+            // #(>= t) = ct >= K, #(>= hi) < K
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                uint32_t mx = max(max(v[s][0], v[s][1]), max(v[s][2], v[s][3])), mn = 0xFFFFFFFFu;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) mn = min(mn, v[s][q] != 0u ? v[s][q] : 0xFFFFFFFFu);
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+                    mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
+                }
+                hi[s] = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx) + 1u;          // (mx < 0xFFFFFFFF: NaNs are not candidates)
+                if (need[s]) t[s] = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
+            }
+            for (int step = 0; step < 40; ++step) {
+                const bool open0 = need[0] && ct[0] > CAP && hi[0] - t[0] > 1u;
+                const bool open1 = need[1] && ct[1] > CAP && hi[1] - t[1] > 1u;
+                if (!(open0 || open1)) break;
+                const uint32_t mid0 = open0 ? t[0] + ((hi[0] - t[0]) >> 1) : t[0];
+                const uint32_t mid1 = open1 ? t[1] + ((hi[1] - t[1]) >> 1) : t[1];
+                const int c0 = count32(v[0], mid0), c1 = count32(v[1], mid1);
+                if (open0) {
+                    if (c0 >= K) { t[0] = mid0; ct[0] = c0; } else { hi[0] = mid0; }
+                }
+                if (open1) {
+                    if (c1 >= K) { t[1] = mid1; ct[1] = c1; } else { hi[1] = mid1; }
+                }
+            }
+        }
+        uint64_t thr[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            thr[s] = (uint64_t)t[s] << 32;
+            if (ct[s] > CAP) {
+                // ties: more than CAP scores equal the converged threshold t (#(>= t + 1) < K).  On over the whole key between (t, 0) and
+                // (t + 1, 0): keys are unique, so the count reaches K .. CAP at the latest when the interval is one key wide
+                uint64_t lo64 = thr[s], hi64 = (uint64_t)(t[s] + 1u) << 32;
+                for (int step = 0; step < 40 && ct[s] > CAP && hi64 - lo64 > 1ull; ++step) {
+                    const uint64_t mid = lo64 + ((hi64 - lo64) >> 1);
+                    const int c = count64(v[s], mid);
+                    if (c >= K) { lo64 = mid; ct[s] = c; } else { hi64 = mid; }
+                }
+                thr[s] = lo64;
+            }
+        }
+        // the survivors -> LDS, one key per slot (any order), zeros behind them
+        int cs[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            uint64_t* buf = lists[wave][s];
+            int run = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint64_t key = key_of(v[s], q);
+                const bool p = key >= thr[s];
+                const uint64_t bm = __ballot(p);
+                const int slot = run + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0));
+                if (p && slot < 64) buf[slot] = key;
+                run += __popcll(bm);
+            }
+            cs[s] = min(run, CAP);
+            if (lane >= cs[s]) buf[lane] = 0ull;
+        }
+        pda_wave_sync();
+        uint64_t key[2];
+        int rank[2] = {0, 0};
+        key[0] = lists[wave][0][lane];
+        key[1] = lists[wave][1][lane];
+        const int cm = max(cs[0], cs[1]);
+        for (int jj = 0; jj < cm; jj += 4) {                  // (slots behind a row's count hold zeros: never above a key; 60 + 3 < 64)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const uint64_t* buf = lists[wave][s];
+                const uint64_t k0 = buf[jj], k1 = buf[jj + 1], k2 = buf[jj + 2], k3 = buf[jj + 3];
+                rank[s] += ((k0 > key[s]) ? 1 : 0) + ((k1 > key[s]) ? 1 : 0) + ((k2 > key[s]) ? 1 : 0) + ((k3 > key[s]) ? 1 : 0);
+            }
+        }
+        pda_wave_sync();
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if (lane < cs[s]) lists[wave][s][rank[s]] = key[s];
+        pda_wave_sync();
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int rb = rb0 + it + s;
+            if (rb < n) {
+                // (a row shorter than K: its keys at ranks 0 .. c - 1, zeros behind)
+                if (lane < K) g.out_keys[(size_t)rb * K + lane] = lists[wave][s][lane];
+                const uint64_t kl = lists[wave][s][K - 1];
+                if (lane == it + s) kth_mine = cs[s] >= K ? pda_unordf((uint32_t)(kl >> 32)) : -INFINITY;
+            }
+        }
+        pda_wave_sync();
+    }
+    if (lane < kSelRows && rb0 + lane < n) {
+        g.kth_ws[rb0 + lane] = kth_mine;
+        if (g.seed_out != nullptr) g.seed_out[rb0 + lane] = kth_mine;
     }
 }
 
@@ -2031,15 +2392,45 @@ int launch4_sweep(const Args4& g, hipStream_t stream, int geometry);
 
 template <int D, int HEAD, bool BF>
 int launch4(const Args4& g, int phase, hipStream_t stream, int geometry) {      // phase: 1 = warm-up only, 2 = sweep only, 3 = both
-    if (phase & 1) {
+    bool warm_two = false;
+    if constexpr (HEAD == PDA_HEAD_POP && D <= 128) warm_two = (phase & 1) && g.wscore != nullptr;
+    if constexpr (HEAD == PDA_HEAD_POP && D <= 128) {
+        if (warm_two) {
+            // the dense call of the huge geometry: score kernel + select kernel in place of warm4_kernel (run_score4 decides where)
+            constexpr size_t smem = warm_score5_lds(D);
+            // (the attribute and the CU count belong to a device: a process may drive several)
+            constexpr int kMaxDev = 64;
+            static int cu_of_dev[kMaxDev] = {};
+            int dev = 0;
+            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return PDA_ERR_LAUNCH;
+            if (cu_of_dev[dev] == 0) {
+                int cus = 0;
+                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return PDA_ERR_LAUNCH;
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&warm_score5_kernel<D, BF>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)smem) != hipSuccess)
+                    return PDA_ERR_LAUNCH;
+                cu_of_dev[dev] = cus;
+            }
+            const int n_cu = cu_of_dev[dev];
+            const int nunits = (g.n_users_blk + kUserTile - 1) / kUserTile * (kUserTile / 32);
+            hipLaunchKernelGGL((warm_score5_kernel<D, BF>), dim3((unsigned)(n_cu < nunits ? n_cu : nunits)), dim3(kWS5Threads), smem, stream, g);
+            PDA_CHECK_LAUNCH();
+            hipLaunchKernelGGL(warm_select5_kernel, dim3((unsigned)((g.n_users_blk + 4 * kSelRows - 1) / (4 * kSelRows))), dim3(256), 0, stream, g);
+            PDA_CHECK_LAUNCH();
+        }
+    }
+    if ((phase & 1) && !warm_two) {
         constexpr int CAP = kCap4;
         const size_t smem = 32 * D * 4 + (size_t)kUserTile * (CAP * 8 + 8) + kUserTile * 2 * kWarmTiles * 4 + 256 + kUserTile * 8;
-        static int attr_set = 0;
-        if (!attr_set) {
+        constexpr int kMaxDev = 64;
+        static char attr_set[kMaxDev] = {};      // (per device, as above)
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return PDA_ERR_LAUNCH;
+        if (!attr_set[dev]) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&warm4_kernel<D, HEAD, BF>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)smem) != hipSuccess)
                 return PDA_ERR_LAUNCH;
-            attr_set = 1;
+            attr_set[dev] = 1;
         }
         const int utiles = (g.n_users_blk + kUserTile - 1) / kUserTile;
         Args4 gw = g;
@@ -2082,7 +2473,7 @@ static bool lists_in_hbm4(int) { return true; }       // (every d may run with i
 // the workspace of the pda_score_topk4_* calls: [counters of pda_score_topk_workspace_bytes | list slots of every workgroup when the
 // lists live in HBM | Bloom filters, 128 B per user | warm-position train-item masks, 32 B per user and split | regrouping: 1024 bins, bin and sweep row of every user]
 struct Ws4 {
-    size_t lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, kth, total;
+    size_t lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, kth, wscore, total;
 };
 static Ws4 ws4_layout(int n_users_blk, int d, int n_splits) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2110,6 +2501,8 @@ static Ws4 ws4_layout(int n_users_blk, int d, int n_splits) {
     w.total = w.seed + al((size_t)n_users_blk * 4);
     w.kth = w.total;                                    // the dense call of the huge geometry: the K-th value of every warm-up row (Args4::kth_ws)
     w.total = w.kth + al((size_t)n_splits * (size_t)n_users_blk * 4);
+    w.wscore = w.total;                                 // the two-kernel warm-up: 256 item ids, then 256 ordered scores per user (Args4::wscore)
+    w.total = w.wscore + al((size_t)kWarmPos * 4 + ((size_t)n_users_blk + kUserTile - 1) / kUserTile * kUserTile * kWarmPos * 4);       // (whole 128-user tiles)
     return w;
 }
 extern "C" size_t pda_score_topk4_workspace_bytes(int n_users_blk, int n_items_local, int d, int n_splits) {
@@ -2126,8 +2519,9 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     if (!U || !I_shard || !prep || !users || !out_keys || !workspace) return PDA_ERR_ARG;
     if (n_users_blk <= 0 || n_items_local <= 0 || item_offset < 0) return PDA_ERR_ARG;
     if (K < 1 || K > PDA_MAX_K) return PDA_ERR_ARG;
-    if (early_stop < 0 || (early_stop & ~0x7FF) != 0) return PDA_ERR_ARG;
+    if (early_stop < 0 || (early_stop & ~0xFFF) != 0) return PDA_ERR_ARG;
     const bool warm_per_split = (early_stop & PDA_SWEEP_WARM_PER_SPLIT) != 0;
+    const bool warm_one_kernel = (early_stop & PDA_SWEEP_WARM_ONE_KERNEL) != 0;
     // geometry hints (Geo4<D, 3>, sweep5_kernel): results do not depend on them, and every geometry takes any n_splits and any user count
     // (tests/test_gpu_score_topk.py runs each with 1 / 2 / 3 / 8 splits and ragged blocks)
     // (PDA_SWEEP_FEW_CANDIDATES, PDA_SWEEP_WIDE and the two PDA_SWEEP_HUGE_* sub-variants named geometries that round 5 removed -- each
@@ -2207,7 +2601,16 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
         g.warm_shared = 1;
         g.seed_out = reinterpret_cast<float*>(wsb + W.seed);
     }
-    if (hist_indptr && (phase & 2)) {
+    // the exact warm-up of that call as a score kernel and a select kernel (warm_score5_kernel; PDA_SWEEP_WARM_ONE_KERNEL restores
+    // warm4_kernel): one warm-up over the front of the whole order, d <= 128 (a 256 KB fp32 image does not fit the LDS), and at most
+    // 2^21 users per block -- the score kernel addresses its region with 32-bit word offsets (2^21 x 256 words = 2 GB of scores); larger
+    // blocks run warm4_kernel, and the witness word says so
+    const bool warm_two = g.ufrag_out != nullptr && g.kth_ws != nullptr && d <= 128 && !warm_one_kernel && (n_splits == 1 || g.warm_shared) &&
+                          n_users_blk <= (1 << 21);
+    if (warm_two) g.wscore = reinterpret_cast<uint32_t*>(wsb + W.wscore);
+    // (sweep5_kernel masks train items through the history itself and never reads the Bloom filters: no launch where launch4_sweep takes it)
+    const bool sweep5 = head == PDA_HEAD_POP && geometry == 4 && !early_stop && g.prep_hdr_pop != 0;
+    if (hist_indptr && (phase & 2) && !sweep5) {
         uint32_t* bloom = reinterpret_cast<uint32_t*>(wsb + W.bloom);
         hipLaunchKernelGGL(hist_bloom4_kernel, dim3((unsigned)((n_users_blk + 31) / 32)), dim3(256), 0, s, users, hist_indptr, hist_indices,
                            hist_row_mode, n_users_blk, bloom, reinterpret_cast<const int*>(pb + L.hdr), head == PDA_HEAD_POP ? 1 : 0);
@@ -2220,7 +2623,7 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
         (n_splits == 1 || g.warm_shared)) {
         g.hmask_tab = mask_table;
         g.hmask_tab_rows = mask_table_rows;
-    } else if (hist_indptr && (phase & 1) && n_users_blk >= 98304) {
+    } else if (hist_indptr && (phase & 1) && (n_users_blk >= 98304 || warm_two)) {        // (warm_score5_kernel walks no history: always in front of it)
         // the train-item bits of the warm positions, by a kernel of its own (see warm_mask4_kernel) -- where it pays for its launch:
         // 1.35 -> 1.29 ms per early-terminating sweep of 262 144 users, but 0.267 -> 0.277 ms at 50 000
         uint32_t* hm = reinterpret_cast<uint32_t*>(wsb + W.hmask);

@@ -163,6 +163,7 @@ def item_prep_ordered(I_shard: torch.Tensor, pop_shard: Optional[torch.Tensor], 
 
 _PREP4_CACHE = {}      # id(I_shard) -> (weakref(I), I._version, order|None, pop weakref|None, pop _version, prep buffer)
 SWEEP_WARM_PER_SPLIT = 1024   # PDA_SWEEP_WARM_PER_SPLIT (include/pda_hip.h)
+SWEEP_WARM_ONE_KERNEL = 2048  # PDA_SWEEP_WARM_ONE_KERNEL (include/pda_hip_experimental.h)
 TOPK_K_V4 = 54         # pda_score_topk4_*: K <= 54 (57 list slots per user)
 
 
@@ -654,6 +655,8 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
         es = hint | ((min(4, max(0, int(warm_tiles))) & 7) << 4)
         if os.environ.get("PDA_WARM_PER_SPLIT"):      # A/B measurements and cross-checks: every item split warms up on its own tiles (before round 4)
             es |= SWEEP_WARM_PER_SPLIT
+        if os.environ.get("PDA_WARM_ONE_KERNEL"):     # A/B measurements and tests: the dense call's warm-up as warm4_kernel, not as score + select kernel
+            es |= SWEEP_WARM_ONE_KERNEL
         # the warm-position masks of every user, built once per history and order: the call gathers them instead of walking the histories
         # (one warm-up over the front of the whole order: one split, or the shared warm-up of several)
         tab = warm_mask_table(hist, prep, order, item_offset, nloc, d) if hist and (n_splits == 1 or not (es & SWEEP_WARM_PER_SPLIT)) else None
@@ -678,6 +681,7 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
             stats["kernel_id"] = ws[16:20].view(torch.int32)     # written by the sweep kernel itself: see kernel_identity()
             stats["huge_entries"] = ws[20:24].view(torch.int32)  # huge geometry: entries of its asm loop, summed over the waves (1 per wave + 1 per flagged half-tile)
             stats["huge_free_halftiles"] = ws[28:32].view(torch.int32)  # huge geometry: 32-item half-tiles run without threshold tests (behind the decided half-tile), summed over the workgroups
+            stats["warm_kernels"] = ws[32:36].view(torch.int32)  # which exact warm-up ran: 0 = warm4_kernel, 5 = warm_score5_kernel + warm_select5_kernel
             stats["error"] = ws[0:4].view(torch.int32)           # 0, or which bounded wait of the sweep ran out (1 .. 4: hand-over words; 5, 6: huge geometry)
             stats["workspace"] = ws                               # (tests read the huge geometry's user image out of it: huge_image_offsets)
             stats["n_splits"] = n_splits

@@ -6,7 +6,11 @@ exits   what the waves of sweep5_kernel spend OUTSIDE their asm loops: needs the
         outside sets the kernel's time).  The counters slow the kernel a little: times of the call itself come from a product build.
 mask    the warm-position mask table (ops.warm_mask_table): its one-time build, and a call with and without it at several block sizes
             python tools/time_huge_exits.py mask c3 2048,50000,262144 [order|stop]
-usage: time_huge_exits.py exits|mask [workload=c3] [users per block(s)] [sweep]"""
+warm    the dense call with its warm-up as one kernel (PDA_WARM_ONE_KERNEL=1) and as score + select kernel, at several block sizes
+            python tools/time_huge_exits.py warm c3 2048,4096,50000,262144 [order [row]]
+        row: the block's histories as a CSR by block row (no mask table: warm_mask4_kernel in front of the score kernel).  Blocks under
+        4 096 users get the huge geometry only when forced: PDA_SCORE_LISTS=huge in front of the command
+usage: time_huge_exits.py exits|mask|warm [workload=c3] [users per block(s)] [sweep] [row]"""
 import ctypes as C
 import os
 import sys
@@ -27,8 +31,17 @@ W = synthetic.make_workload(wl, dev, table_dtype=td)
 hist = ops.HistoryCSR(W.hist_indptr, W.hist_indices, by_user=True)
 
 
+by_row = len(sys.argv) > 5 and sys.argv[5] == "row"
+
+
 def call(users, st=None):
-    return ops.score_topk_keys(W.U, W.I, users, 50, ops.HEAD_POP, W.pop_last, hist, prune=sweep, stats=st)
+    h = hist
+    if by_row:          # (users are the first rows of the table: their part of the CSR is the block's CSR by block row)
+        h = call.__dict__.get(len(users))
+        if h is None:
+            ip = W.hist_indptr[:len(users) + 1].clone()
+            h = call.__dict__[len(users)] = ops.HistoryCSR(ip, W.hist_indices[:int(ip[-1])].clone(), by_user=False)
+    return ops.score_topk_keys(W.U, W.I, users, 50, ops.HEAD_POP, W.pop_last, h, prune=sweep, stats=st)
 
 
 def timed(fn, n):
@@ -88,6 +101,20 @@ else:
     for Bu in sizes:
         Bu = min(Bu, W.n_users)
         users = torch.arange(Bu, dtype=torch.int32, device=dev)
+        if mode == "warm":
+            # the dense call's warm-up as warm4_kernel (PDA_WARM_ONE_KERNEL=1) against score + select kernel, whole call, four alternating rounds
+            res, wit = {"1": [], "": []}, {}
+            for flag in ("1", "", "1", "", "1", "", "1", ""):
+                os.environ["PDA_WARM_ONE_KERNEL"] = flag
+                st = {}
+                call(users, st)
+                wit[flag] = int(st["warm_kernels"][0])
+                res[flag].append(timed(lambda: call(users), 20 if Bu <= 65536 else 6))
+            os.environ.pop("PDA_WARM_ONE_KERNEL")
+            print("  %7d users%s, sweep %s, %s: one kernel (witness %d) %s ms | two kernels (witness %d) %s ms" %
+                  (Bu, " by block row" if by_row else "", sweep, ops.kernel_identity(st["kernel_id"][0]).get("geometry"), wit["1"], " / ".join("%.4f" % x for x in res["1"]),
+                   wit[""], " / ".join("%.4f" % x for x in res[""])))
+            continue
         res = {}
         for flag in ("0", "1", "0", "1"):
             os.environ["PDA_WARM_MASK_TABLE"] = flag

@@ -702,7 +702,6 @@ extern "C" int pda_topk_merge(const uint64_t* in_keys, int R, int n_users_blk, i
     if (!in_keys || R < 1 || n_users_blk <= 0 || K < 1 || K > PDA_MAX_K) return PDA_ERR_ARG;
     if (!out_keys && !out_idx) return PDA_ERR_ARG;
     if (hist_indptr && (!hist_indices || (hist_row_mode == PDA_HIST_BY_USER_ID && !users))) return PDA_ERR_ARG;
-#ifndef PDA_MERGE_R1_GENERAL        // (A/B build: R = 1 through the general kernel -- tools/build_variant.sh merge1 -DPDA_MERGE_R1_GENERAL)
     // one list per user: an unpack (topk_unpack1_kernel); its 16-byte accesses want 16-byte aligned arrays -- anything else takes the general kernel
     if (R == 1 && ((reinterpret_cast<uintptr_t>(in_keys) | reinterpret_cast<uintptr_t>(out_keys) | reinterpret_cast<uintptr_t>(out_idx) |
                     reinterpret_cast<uintptr_t>(out_val)) & 15u) == 0) {
@@ -712,7 +711,6 @@ extern "C" int pda_topk_merge(const uint64_t* in_keys, int R, int n_users_blk, i
         PDA_CHECK_LAUNCH();
         return PDA_OK;
     }
-#endif
     const size_t smem = 4 * (((size_t)R * K + PDA_MAX_K) * sizeof(uint64_t) + (((size_t)R * 4 + 7) & ~(size_t)7));
     if (smem > 160 * 1024) return PDA_ERR_UNSUPPORTED;
     static int attr_set = 0;

@@ -48,9 +48,6 @@ constexpr int kMainWaves = 8;
 #ifndef PDA_W4_ABL
 #define PDA_W4_ABL 0      // warm-up timing ablations (results are wrong): 1 no history walk, 2 no appends, 4 no final sort, 8 no MFMA, 16 no gather
 #endif
-#ifndef PDA_V4_ABL
-#define PDA_V4_ABL 0      // timing-only ablations (results are wrong): 1 no filter, 2 no hand-over between MFMA waves, 4 no tile loads, 8 rescoring waves leave at once
-#endif
 #ifdef PDA_V4_PROF
 // profiling build only (tools/build_variant.sh prof -DPDA_V4_PROF): cycle counters summed over waves
 __device__ unsigned long long pda_prof4[24];
@@ -134,6 +131,36 @@ struct Args4 {
     // n_users_blk x 64 warm_tiles scores as ordered uints, 0 = not a candidate].  NULL: warm4_kernel.
     uint32_t* wscore;
 };
+
+// What ONE call launches.  run_score4 forms every decision here, once, from the call's arguments; the launchers follow it and ask nothing
+// about the call themselves.
+struct Call4 {
+    enum Warm { kNoWarm, kWarm4, kWarmTwo };                    // none (phases 2 and 4), warm4_kernel, or warm_score5_kernel + warm_select5_kernel
+    enum Sweep { kNoSweep, kSweep4, kSweep4Many, kSweep5 };     // none (phase 1), sweep4_kernel<GM = 0>, sweep4_kernel<GM = 3> or sweep5_kernel
+    Warm warm;
+    bool warm_whole;       // ONE warm-up over the front of the whole visiting order (a single split, or a shared warm-up), not one per split
+    bool mask_kernel;      // warm_mask4_kernel in front of the warm-up
+    bool bloom;            // hist_bloom4_kernel: the Bloom filters of the block's train items, for sweep4_kernel's rescoring waves
+    bool uprep5;           // sweep5_kernel's user image by uprep5_kernel; false: the warm-up of this call writes it (Args4::ufrag_out)
+    Sweep sweep;
+    bool early_stop;       // sweep4_kernel<ES>
+    bool regroup;          // the users regrouped by predicted stopping tile in front of the sweep (stop_predict4_kernel)
+    bool ends_in_warm;     // every split ends inside its warm-up: the warm-up's sorted lists are the answer, no sweep runs
+};
+
+// A kernel's dynamic-LDS limit is an attribute of a (kernel, device) pair and a process may drive several devices: set once per device.
+// done: the caller's static flags of ONE kernel; dev_out: the current device, for whatever else the caller keeps per device.
+constexpr int kMaxDev4 = 64;
+int dynamic_lds_once(const void* kernel, size_t bytes, char (&done)[kMaxDev4], int* dev_out = nullptr) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev4) return PDA_ERR_LAUNCH;
+    if (!done[dev]) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return PDA_ERR_LAUNCH;
+        done[dev] = 1;
+    }
+    if (dev_out != nullptr) *dev_out = dev;
+    return PDA_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // prep: padded rows in visiting order
@@ -404,10 +431,7 @@ __device__ __forceinline__ bool append_keys(bool p, int lrow, float tt, uint64_t
 // gathers, the rest index arithmetic -- in THIS form as in the four-rows-at-a-time form of rounds 2 - 5: the rewrite bought nothing measurable there
 // (0.197 vs 0.186 - 0.200 ms lease to lease) and is kept for its bounded worst case (a single 800-item row used to cost 13 dependent pairs).
 __device__ __forceinline__ void warm_hist_walk(const Args4& g, unsigned* hmask, int utile, int split, int nwarm, int wave, int lane) {
-#ifndef PDA_W4_WALK_UN
-#define PDA_W4_WALK_UN 8
-#endif
-    constexpr int UN = PDA_W4_WALK_UN;
+    constexpr int UN = 8;
     long long hb_l = 0;
     int len_l = 0;
     {
@@ -1218,47 +1242,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) w
 // could not keep up: the MFMA waves waited 39 % of their time for tiles); d = 256 (168 VGPRs): 8 + 2 + 2.
 
 #include "pda_v4_block_asm.h"
-#ifndef PDA_V4_ASM
-#define PDA_V4_ASM 1      // d <= 128: the reads and MFMAs of a block as ONE inline-asm statement with a counted software pipeline
-#endif
-#ifndef PDA_V4_RSLEEP
-#define PDA_V4_RSLEEP 8     // idle rescoring waves: s_sleep between polls of their rings (x 64 cycles)
-#endif
-#ifndef PDA_V4_LSLEEP
-#define PDA_V4_LSLEEP 1     // loaders: s_sleep between polls for a free slot
-#endif
-#ifndef PDA_V4_GL
-#define PDA_V4_GL 2       // exact lists: 0 in LDS, 1 in HBM, 2 = in HBM for d = 256
-#endif
-#ifndef PDA_V4_HANDOVER_WS
-#define PDA_V4_HANDOVER_WS 1   // one-call sweeps: warm-up lists handed over through the workspace with K .. kCap4 keys per row
-#endif
-#ifndef PDA_V4_ROWS_INTERLEAVED
-#define PDA_V4_ROWS_INTERLEAVED 1   // rescoring: a candidate's lanes share every load (d <= 128)
-#endif
-#ifndef PDA_V4_RESCORE_AHEAD
-#define PDA_V4_RESCORE_AHEAD 1   // rescoring waves request the rows of the next pass before the appends of this one
-#endif
-#ifndef PDA_V4_RING_MANY
-#define PDA_V4_RING_MANY 128   // candidate ring entries of the many-candidates geometry (256 / 512: no faster -- later thresholds, more candidates)
-#endif
-#ifndef PDA_V4_L256
-#define PDA_V4_L256 3          // d = 256: loader waves (three: config-5 shard 27.78 -> 26.21 ms dense, 0.51 of the roof; 35 DMA pieces per 64-item block were
-                              // too many for two) (of the four waves beside the eight MFMA waves; the rest rescore)
-#endif
-#ifndef PDA_V4_ASM256
-#define PDA_V4_ASM256 1       // d = 256: the block as one asm statement too (config-5 shard: 29.15 -> 28.24 ms dense, 5.43 -> 5.08 ms early-terminating)
-#endif
-#ifndef PDA_V4_NB256
-#define PDA_V4_NB256 2        // d = 256: half-tiles per block.  64-item blocks = two accumulator chains per wave: config-5 shard 30.65 -> 29.10 ms dense,
-                              // 5.87 -> 5.39 ms early-terminating (one chain per wave, two waves per SIMD, left the matrix pipe waiting on dependent MFMAs)
-#endif
-#ifndef PDA_V4_NSLOT_MAX
-#define PDA_V4_NSLOT_MAX 5   // (timing experiments raise it: the votes of the early termination are then wrong)
-#endif
-#ifndef PDA_V4_NSLOT
-#define PDA_V4_NSLOT 4    // tile slots in LDS when the lists live in HBM (<= 5: the vote words of the early termination)
-#endif
+constexpr int kPF4 = 4;          // B fragments in flight per MFMA wave (the compiler keeps fewer when registers are short)
+constexpr int kRSleep4 = 8;       // idle rescoring waves: s_sleep between polls of their rings (x 64 cycles)
+constexpr int kLSleep4 = 1;       // loaders: s_sleep between polls for a free slot
+constexpr int kRingMany4 = 128;   // candidate ring entries of the many-candidates geometry (256 / 512: no faster -- later thresholds, more candidates)
+constexpr int kLoaders256 = 3;    // d = 256: loader waves (three: config-5 shard 27.78 -> 26.21 ms dense, 0.51 of the roof; 35 DMA pieces per 64-item block were
+                                  // too many for two) (of the four waves beside the eight MFMA waves; the rest rescore)
+constexpr int kNB256 = 2;         // d = 256: half-tiles per block.  64-item blocks = two accumulator chains per wave: config-5 shard 30.65 -> 29.10 ms dense,
+                                  // 5.87 -> 5.39 ms early-terminating (one chain per wave, two waves per SIMD, left the matrix pipe waiting on dependent MFMAs)
+constexpr int kNSlotMax4 = 5;     // (more slots: the votes of the early termination are then wrong)
+constexpr int kNSlot4 = 4;        // tile slots in LDS when the lists live in HBM (<= 5: the vote words of the early termination)
 // GLX (d <= 128; round 3): the exact lists in the workspace instead of the LDS, which pays for FOUR tile slots and loaders that run
 // ahead.  With two slots the loaders can start on block b + 2 only when the SLOWEST MFMA wave has released block b, and need
 // ~900 cycles from there (5 pieces of ~136 issue cycles per loader, then the latency) against ~1 150 cycles of a block's MFMAs:
@@ -1273,14 +1266,10 @@ struct Geo4 {
     static constexpr int UA = 1;                                      // A operands per B read: 32 UA user rows per MFMA wave
     // the exact lists in HBM (workspace) free the LDS for four tile slots (d = 256: 8.1 instead of 9.0 ms on a config-5 shard);
     // 512 users x 57 x 8 B would not fit the LDS anyway
-    static constexpr bool GL = PDA_V4_GL == 2 ? D > 128 : PDA_V4_GL != 0;
-#ifdef PDA_V4_NBX   /* timing experiment only (results are wrong): NBX half-tiles per block at d <= 128 */
-    static constexpr int NB = D <= 128 ? PDA_V4_NBX : 1;
-#else
-    static constexpr int NB = D <= 128 ? 2 : PDA_V4_NB256;          // half-tiles (32 items) per block; accumulator chains per wave = NB UA
-#endif
-    static constexpr int LOADERS = D <= 128 ? 4 : PDA_V4_L256;
-    static constexpr int RESCORERS = MANY ? 8 : (D <= 128 ? 4 : 4 - PDA_V4_L256);
+    static constexpr bool GL = D > 128;
+    static constexpr int NB = D <= 128 ? 2 : kNB256;                // half-tiles (32 items) per block; accumulator chains per wave = NB UA
+    static constexpr int LOADERS = D <= 128 ? 4 : kLoaders256;
+    static constexpr int RESCORERS = MANY ? 8 : (D <= 128 ? 4 : 4 - kLoaders256);
     static constexpr int ROWS = 32 * UA;                 // user rows per MFMA wave
     // candidate rings: one per MFMA wave, or (MANY) two -- rows 0..15 and 16..31 of the wave -- each with a rescoring wave of its own
     static constexpr int NRINGS = MW > RESCORERS ? MW : RESCORERS;
@@ -1295,16 +1284,16 @@ struct Geo4 {
     static constexpr int NP = (BB + 1023) / 1024;        // 1 KiB DMA pieces per block; the last one may be half a piece (32 lanes)
     static constexpr int LASTL = (BB % 1024) ? (BB % 1024) / 16 : 64;
     // (MANY: 128 users' lists leave the LDS room for four slots)
-    static constexpr int NSLOT = (GL || MANY) ? PDA_V4_NSLOT : 2;
+    static constexpr int NSLOT = (GL || MANY) ? kNSlot4 : 2;
     static constexpr size_t lds_tiles = NSLOT * (size_t)BB;
     // list slots per user row: a full list is compacted to its best K, i.e. every CAP - K insertions (half of what a candidate costs
     // its rescoring wave); 128 users leave the LDS room for 64
     static constexpr int CAP = MANY ? 64 : kCap4;
     static constexpr size_t lds_lists = GL ? 0 : (size_t)UT * CAP * 8;
-    static constexpr int RING = MANY ? PDA_V4_RING_MANY : kRing4;      // entries per candidate ring (a push needs 64 free)
+    static constexpr int RING = MANY ? kRingMany4 : kRing4;      // entries per candidate ring (a push needs 64 free)
     static constexpr size_t lds_total = lds_tiles + lds_lists + (size_t)UT * 8 + kMainWaves * RING * 4 + 512;
     static_assert(NRINGS <= kMainWaves && RPW * MW == NRINGS && MPR * RESCORERS == NRINGS, "ring bookkeeping: eight words each");
-    static_assert(NSLOT >= 2 && NSLOT <= PDA_V4_NSLOT_MAX, "vote timing of the early termination");
+    static_assert(NSLOT >= 2 && NSLOT <= kNSlotMax4, "vote timing of the early termination");
 };
 
 // ES: exact early termination on (sufA / sufB non-NULL).  Two instantiations: the votes and the dead-wave path are a handful of
@@ -1349,13 +1338,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
     const int n_blk = NB > 2 ? (2 * n_it) / NB : n_it * (2 / NB);                           // blocks: block b = half-tiles NB b .. NB b + NB - 1 of that sequence
     // block row of sweep row rb (rb < n_users_blk): the users of an early-terminating sweep are regrouped (stop_predict4_kernel)
     auto orig_row = [&](int rb) __attribute__((always_inline)) -> int { if constexpr (!ES) return rb; else return (g.row_perm != nullptr && rb < g.n_users_blk) ? g.row_perm[rb] : rb; };
-#ifdef PDA_V4_STAMP      /* debug build: phase clocks (100 MHz) of a few workgroups, printed */
-    const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0;
-#define PDA_STAMP(x) x = __builtin_amdgcn_s_memrealtime()
-#else
-#define PDA_STAMP(x)
-#endif
     if (tid < 128) sync[tid] = tid >= 112 ? 0xFFFFFFFFu : 0u;       // (words 112 .. 127: every list comes in unsorted, see s_uns)
     // kernel identity (workspace + 16; tests read it back to prove WHICH kernel and geometry a call ran):
     // generation 4 | geometry << 8 | early-terminating << 12 | head << 13 | bf16 tables << 14 | d / 64
@@ -1402,7 +1384,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
 #ifdef PDA_V4_PROF
     unsigned long long prof[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    PDA_STAMP(st1);
 
     if (wave >= MW + kLoaders) {
         // ============================== rescoring wave ==============================
@@ -1458,7 +1439,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
 #pragma unroll
         for (int z = 0; z < kMPR; ++z) head[z] = 0;
         constexpr int LPC = D / 32;                 // lanes per candidate
-        constexpr bool kRowsInterleaved = D <= 128 && PDA_V4_ROWS_INTERLEAVED != 0;
+        constexpr bool kRowsInterleaved = D <= 128;
         constexpr int CPP = 64 / LPC;               // candidates per pass
         const int q = lane % LPC, ci = lane / LPC;
         int sel = 0;                                // the ring looked at last
@@ -1577,7 +1558,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
             return true;
         };
         for (;;) {
-            if constexpr ((PDA_V4_ABL & 8) != 0) break;
             PROF_T0(tp0);
             if (!have) {
                 unsigned dn = 1u;
@@ -1593,7 +1573,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
                     }
                     if (++idle > kSpinMax) { if (lane == 0) g.stats[0] = 3u; break; }
                     PROF_T0(ti);
-                    __builtin_amdgcn_s_sleep(PDA_V4_RSLEEP);
+                    __builtin_amdgcn_s_sleep(kRSleep4);
                     PROF_T1(ti, 7);
                     continue;
                 }
@@ -1682,7 +1662,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
             float tt = (valid && q == LPC - 1) ? sc : -INFINITY;
             have = false;
             PROF_T1(tp1, 17);
-#if PDA_V4_RESCORE_AHEAD
             PROF_T0(tp4);
             {
                 // ---- the next pass: its rows travel while this one's survivors go through the history and the lists
@@ -1696,7 +1675,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
 #endif
             }
             PROF_T1(tp4, 21);
-#endif
             PROF_T0(tp2);
             const int lrow = row0 + row;
             const int item = g.item_offset + loc;
@@ -1755,7 +1733,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
         bool stop = false;
         for (int b = 0; b < n_blk && !stop; ++b) {
             PROF_T0(tl0);
-            if (b >= NSLOT && !(PDA_V4_ABL & 2)) {                 // slot b % NSLOT is free once every MFMA wave has released block b - NSLOT
+            if (b >= NSLOT) {                 // slot b % NSLOT is free once every MFMA wave has released block b - NSLOT
                 const unsigned want = (unsigned)(b - NSLOT + 1);
                 unsigned spin = 0;
                 auto min_released = [&]() __attribute__((always_inline)) -> unsigned {
@@ -1767,7 +1745,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
                 while (min_released() < want) {
                     if (lds_ld(s_stop)) { stop = true; break; }
                     if (++spin > kSpinMax) { if (lane == 0) g.stats[0] = 4u; stop = true; break; }
-                    __builtin_amdgcn_s_sleep(PDA_V4_LSLEEP);
+                    __builtin_amdgcn_s_sleep(kLSleep4);
                 }
                 if (stop) break;
             }
@@ -1780,7 +1758,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
 #pragma unroll
             for (int c = 0; c < MYP; ++c) {
                 const int piece = l + kLoaders * c;
-                if (piece < NP && (piece < NP - 1 || lane < G::LASTL) && !(PDA_V4_ABL & 4)) {
+                if (piece < NP && (piece < NP - 1 || lane < G::LASTL)) {
 #if defined(__HIP_DEVICE_COMPILE__)
                     unsigned keep;
                     const unsigned char* gsrc = src + (size_t)piece * 1024;
@@ -1841,9 +1819,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
         ss += __shfl_xor(ss, 32, 64);
         nu_row[u] = sqrtf(ss) * 1.0009765625f * 1.0001f;           // padded ||u||
     }
-    PDA_STAMP(st2);
     __syncthreads();                       // lists, thresholds and hand-over words are initialised
-    PDA_STAMP(st3);
 
     // threshold of the lane's own row (finite: +-1e30 stand for +-inf), lowered by 2^-16 relative (the rounding of the
     // extra k-step, pda_score_topk_v3.hip), as the A operand of the extra k-step:
@@ -1885,9 +1861,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
     };
     refresh_thr();
     unsigned tver_seen = 0, landed_c = 0;
-#ifdef PDA_V4_PRIO
-    if (w < 4) __builtin_amdgcn_s_setprio(PDA_V4_PRIO);     // experiment: the first-dispatched MFMA wave of every SIMD goes first
-#endif
 
     // ring RPW w + rg of this wave takes the candidates of rows rg RPR .. rg RPR + RPR - 1
     unsigned tail[RPW], head_c[RPW];        // wave-uniform
@@ -1929,7 +1902,7 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
     };
     auto ensure_landed = [&](int b) __attribute__((always_inline)) {
         const unsigned want = (unsigned)(b + 1);
-        if (landed_c < want && !(PDA_V4_ABL & 2)) {
+        if (landed_c < want) {
             unsigned spin = 0;
             PROF_T0(te);
             do {
@@ -1947,22 +1920,10 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
     // (raw head: a prep built WITH a popularity carries 1/pop pieces in its test operands -- header word 1)
     [[maybe_unused]] const bool raw_on_pop_prep = HEAD == PDA_HEAD_RAW && g.prep_hdr[1] != 0;
 
-#ifndef PDA_V4_PF
-#define PDA_V4_PF 4       // B fragments in flight per MFMA wave (the compiler keeps fewer when registers are short)
-#endif
-#ifndef PDA_V4_STAGGER
-#define PDA_V4_STAGGER 0
-#endif
-    // The two MFMA waves of a SIMD (w and w + 4) half a block apart: while one waits for its last MFMA and tests the
-    // accumulators, the other one's MFMAs keep the pipe busy.
-    if (PDA_V4_STAGGER > 0 && w >= 4) __builtin_amdgcn_s_sleep(PDA_V4_STAGGER);
     PROF_T0(tm0);
     int n_done = 0;
     bool stopped = false;
-#ifndef PDA_V4_VOTE_EVERY
-#define PDA_V4_VOTE_EVERY 2
-#endif
-    constexpr int kVoteEvery = PDA_V4_VOTE_EVERY;      // a vote in front of every kVoteEvery-th tile (1, 2 or 4)
+    constexpr int kVoteEvery = 2;                      // a vote in front of every kVoteEvery-th tile (1, 2 or 4)
     constexpr int kVL = (NSLOT + 2) / 2;               // a vote is about the tile kVL behind the one it is stored in front of
     float sa_nx = 0.0f, sb_nx = 0.0f;          // suffix bounds at tile it + kVL of the coming vote
     bool nx_ok = ES && kVoteEvery - 1 + kVL < n_it;
@@ -1971,8 +1932,10 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
         sa_nx = g.sufA[tn];
         sb_nx = g.sufB[tn];
     }
-    constexpr int S = NB * NM, PF = S < PDA_V4_PF ? S : PDA_V4_PF;
-    constexpr bool kAsmGeo = PDA_V4_ASM != 0 && (D <= 128 || PDA_V4_ASM256 != 0) && UA == 1 && NB == 2;     // the block as one asm statement (below)
+    constexpr int S = NB * NM, PF = S < kPF4 ? S : kPF4;
+    // the block as ONE inline-asm statement with a counted software pipeline (below); d = 256 too: config-5 shard 29.15 -> 28.24 ms dense,
+    // 5.43 -> 5.08 ms early-terminating
+    constexpr bool kAsmGeo = UA == 1 && NB == 2;
     constexpr bool PFX = !kAsmGeo && NSLOT >= 3 && S % PF == 0;          // prefetch across the block boundary
     u32x4 bq[PF];
     int dead_from = 0x7FFFFFFF;                // first tile from which no row of this wave can be reached (early termination)
@@ -2135,44 +2098,36 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
         PDA_CBAR();
         // ---- the filter: "some register of the lane is negative" = the sign bit of the OR of the bit patterns.  (This stalls
         // the wave until its MFMAs are through; the other MFMA wave of the SIMD has the matrix pipe meanwhile.) ----
-        if constexpr ((PDA_V4_ABL & 1) != 0) {
-#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-            for (int cb = 0; cb < NB; ++cb)
-                for (int u = 0; u < UA; ++u) asm volatile("" ::"v"(acc[u][cb]));       // timing only: no filter, but the MFMAs stay
-#endif
-        } else {
+        for (int cb = 0; cb < NB; ++cb) {
 #pragma unroll
-            for (int cb = 0; cb < NB; ++cb) {
+            for (int u = 0; u < UA; ++u) {
+                uint32_t mo = 0;
 #pragma unroll
-                for (int u = 0; u < UA; ++u) {
-                    uint32_t mo = 0;
+                for (int r = 0; r < 16; ++r) mo |= (uint32_t)__float_as_int(acc[u][cb][r]);
+                bool clampy = false;
+                if constexpr (HEAD == PDA_HEAD_POP) clampy = __any(popv[cb] > thr_min[u]);     // s~ + eps < 0: head <= pop; rare once the lists are warm
+                if (__any((int)mo < 0) || clampy) {
+                    PROF_T0(ts);
+                    PROF_INC(4, 1);
+                    uint32_t mcb = 0;
+                    if (__any((int)mo < 0)) {
+                        // the exact mask: bit 15 - r <-> register r is negative (v_alignbit shifts the sign bit in)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) mo |= (uint32_t)__float_as_int(acc[u][cb][r]);
-                    bool clampy = false;
-                    if constexpr (HEAD == PDA_HEAD_POP) clampy = __any(popv[cb] > thr_min[u]);     // s~ + eps < 0: head <= pop; rare once the lists are warm
-                    if (__any((int)mo < 0) || clampy) {
-                        PROF_T0(ts);
-                        PROF_INC(4, 1);
-                        uint32_t mcb = 0;
-                        if (__any((int)mo < 0)) {
-                            // the exact mask: bit 15 - r <-> register r is negative (v_alignbit shifts the sign bit in)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) mcb = __builtin_amdgcn_alignbit(mcb, (uint32_t)__float_as_int(acc[u][cb][r]), 31);
-                        }
-                        if (clampy) {
-                            int hv = h;
-#if defined(__HIP_DEVICE_COMPILE__)
-                            asm volatile("" : "+v"(hv));
-#endif
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) mcb |= (popv[cb] > thr_of(r, hv, u)) ? (1u << (15 - r)) : 0u;
-                        }
-                        push_mask(mcb, locv[cb], u);
-                        PDA_CBAR();
-                        publish_tails();
-                        PROF_T1(ts, 3);
+                        for (int r = 0; r < 16; ++r) mcb = __builtin_amdgcn_alignbit(mcb, (uint32_t)__float_as_int(acc[u][cb][r]), 31);
                     }
+                    if (clampy) {
+                        int hv = h;
+#if defined(__HIP_DEVICE_COMPILE__)
+                        asm volatile("" : "+v"(hv));
+#endif
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) mcb |= (popv[cb] > thr_of(r, hv, u)) ? (1u << (15 - r)) : 0u;
+                    }
+                    push_mask(mcb, locv[cb], u);
+                    PDA_CBAR();
+                    publish_tails();
+                    PROF_T1(ts, 3);
                 }
             }
         }
@@ -2196,13 +2151,11 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
     if (stopped) lds_st(s_stop, 1u);
     if (lane == 0 && w == 0) atomicAdd(reinterpret_cast<unsigned long long*>(g.stats + 2), (unsigned long long)(2 * n_done * (UT / kUserTile)));
     }
-    PDA_STAMP(st4);
     // ================================== all waves: sort and emit ==================================
     // Behind this barrier every candidate has been rescored and nobody appends any more (the rescoring waves arrive last).  The
     // lists are exact; what is left is their order -- rows the rescoring waves did not get to in their idle time -- and the
     // copy out: shared by all waves (64 rows per rescoring wave, one after the other, were the tail of every workgroup).
     __syncthreads();
-    PDA_STAMP(st5);
     // (The sort is bound by the compares -- ~57 x 3 issue slots per row, four waves per SIMD at it: 20 - 35 us of a workgroup's
     // ~130 in an early-terminating sweep; ranking four rows at a time, on the 32-bit score halves, measured no faster.)
     constexpr int EB = 8;                  // (the rows' places in out_keys: eight loads of the permutation in flight)
@@ -2226,13 +2179,6 @@ __global__ void __launch_bounds__((64 * Geo4<D, GM>::WAVES)) sweep4_kernel(Args4
             }
         }
     }
-#ifdef PDA_V4_STAMP
-    if (ES && lane == 0 && (wave == 0 || wave == G::WAVES - 1) && (blockIdx.x % 100) == 7) {
-        const unsigned long long st6 = __builtin_amdgcn_s_memrealtime();
-        printf("wg %4d wave %2d start %llu: prologue %llu  A rows %llu  barrier %llu  sweep %llu  wait-all %llu  epilogue %llu (x10 ns) tiles %d\n", (int)blockIdx.x, wave,
-               st0, st1 - st0, st2 - st1, st3 - st2, st4 - st3, st5 - st4, st6 - st5, n_it);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2339,139 +2285,100 @@ __global__ void __launch_bounds__(1024) stop_scatter4_kernel(const int* __restri
 
 #include "pda_v5_sweep.h"
 
-template <int D, int HEAD, bool BF, int GM>
-int launch_sweep4(const Args4& g, hipStream_t stream) {
+template <int D, int HEAD, bool BF, bool ES, int GM>
+int launch_sweep4_kernel(const Args4& g, hipStream_t stream) {
     using G = Geo4<D, GM>;
-    constexpr bool kHasES = true;
-    static int attr_set = 0;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep4_kernel<D, HEAD, BF, false, GM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)G::lds_total) != hipSuccess)
-            return PDA_ERR_LAUNCH;
-        if constexpr (kHasES) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep4_kernel<D, HEAD, BF, true, GM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)G::lds_total) != hipSuccess)
-                return PDA_ERR_LAUNCH;
-        }
-        attr_set = 1;
-    }
+    static char attr_done[kMaxDev4] = {};
+    if (const int rc = dynamic_lds_once(reinterpret_cast<const void*>(&sweep4_kernel<D, HEAD, BF, ES, GM>), G::lds_total, attr_done)) return rc;
     const int utiles = (g.n_users_blk + G::UT - 1) / G::UT;
-    if constexpr (kHasES) {
-        if (g.sufA != nullptr && g.regroup_ws != nullptr) {
-            Args4 gp = g;
-            int* bins = g.regroup_ws;
-            int* bin_of = bins + 1024;
-            int32_t* perm = bin_of + g.n_users_blk;
-            if (hipMemsetAsync(bins, 0, 1024 * sizeof(int), stream) != hipSuccess) return PDA_ERR_LAUNCH;
-            hipLaunchKernelGGL((stop_predict4_kernel<D, BF>), dim3((unsigned)((g.n_users_blk + 31) / 32)), dim3(256), 0, stream, g, bin_of);
-            const unsigned hb = (unsigned)((g.n_users_blk + 4095) / 4096);
-            hipLaunchKernelGGL(stop_hist4_kernel, dim3(hb), dim3(1024), 0, stream, bin_of, g.n_users_blk, bins);
-            hipLaunchKernelGGL(stop_scan4_kernel, dim3(1), dim3(1024), 0, stream, bins);
-            hipLaunchKernelGGL(stop_scatter4_kernel, dim3(hb), dim3(1024), 0, stream, bin_of, bins, g.n_users_blk, perm);
-            PDA_CHECK_LAUNCH();
-            gp.row_perm = perm;
-            hipLaunchKernelGGL((sweep4_kernel<D, HEAD, BF, true, GM>), dim3((unsigned)(utiles * g.n_splits)), dim3(64 * G::WAVES), G::lds_total, stream, gp);
-            PDA_CHECK_LAUNCH();
-            return PDA_OK;
-        }
-        if (g.sufA != nullptr) {
-            hipLaunchKernelGGL((sweep4_kernel<D, HEAD, BF, true, GM>), dim3((unsigned)(utiles * g.n_splits)), dim3(64 * G::WAVES), G::lds_total, stream, g);
-            PDA_CHECK_LAUNCH();
-            return PDA_OK;
-        }
-    } else if (g.sufA != nullptr) {
-        return PDA_ERR_ARG;
+    hipLaunchKernelGGL((sweep4_kernel<D, HEAD, BF, ES, GM>), dim3((unsigned)(utiles * g.n_splits)), dim3(64 * G::WAVES), G::lds_total, stream, g);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
+template <int D, int HEAD, bool BF, int GM>
+int launch_sweep4(const Args4& g, const Call4& c, hipStream_t stream) {
+    if (!c.early_stop) return launch_sweep4_kernel<D, HEAD, BF, false, GM>(g, stream);
+    if (!c.regroup) return launch_sweep4_kernel<D, HEAD, BF, true, GM>(g, stream);
+    int* bins = g.regroup_ws;
+    int* bin_of = bins + 1024;
+    int32_t* perm = bin_of + g.n_users_blk;
+    if (hipMemsetAsync(bins, 0, 1024 * sizeof(int), stream) != hipSuccess) return PDA_ERR_LAUNCH;
+    hipLaunchKernelGGL((stop_predict4_kernel<D, BF>), dim3((unsigned)((g.n_users_blk + 31) / 32)), dim3(256), 0, stream, g, bin_of);
+    const unsigned hb = (unsigned)((g.n_users_blk + 4095) / 4096);
+    hipLaunchKernelGGL(stop_hist4_kernel, dim3(hb), dim3(1024), 0, stream, bin_of, g.n_users_blk, bins);
+    hipLaunchKernelGGL(stop_scan4_kernel, dim3(1), dim3(1024), 0, stream, bins);
+    hipLaunchKernelGGL(stop_scatter4_kernel, dim3(hb), dim3(1024), 0, stream, bin_of, bins, g.n_users_blk, perm);
+    PDA_CHECK_LAUNCH();
+    Args4 gp = g;
+    gp.row_perm = perm;
+    return launch_sweep4_kernel<D, HEAD, BF, true, GM>(gp, stream);
+}
+
+// the exact warm-up of a call: the mask kernel where the call has one, then warm4_kernel or the score kernel and the select kernel
+template <int D, int HEAD, bool BF>
+int launch_warm4(const Args4& g, const Call4& c, hipStream_t stream) {
+    Args4 gw = g;
+    if (c.warm_whole) {              // ONE warm-up per user: "split 0 of 1" scores tiles 0 .. warm_tiles - 1 of the whole order
+        gw.n_splits = 1;
+        gw.warm_shared = 0;
     }
-    hipLaunchKernelGGL((sweep4_kernel<D, HEAD, BF, false, GM>), dim3((unsigned)(utiles * g.n_splits)), dim3(64 * G::WAVES), G::lds_total, stream, g);
+    const int utiles = (g.n_users_blk + kUserTile - 1) / kUserTile;
+    if (c.mask_kernel) {
+        hipLaunchKernelGGL(warm_mask4_kernel, dim3((unsigned)(utiles * gw.n_splits)), dim3(kThreads), 0, stream, gw, const_cast<uint32_t*>(g.hmask_ws));
+        PDA_CHECK_LAUNCH();
+    }
+    if constexpr (HEAD == PDA_HEAD_POP && D <= 128) {
+        if (c.warm == Call4::kWarmTwo) {
+            constexpr size_t smem = warm_score5_lds(D);
+            static char attr_done[kMaxDev4] = {};
+            static int cu_of_dev[kMaxDev4] = {};         // (the CU count belongs to a device as well)
+            int dev = 0;
+            if (const int rc = dynamic_lds_once(reinterpret_cast<const void*>(&warm_score5_kernel<D, BF>), smem, attr_done, &dev)) return rc;
+            if (cu_of_dev[dev] == 0) {
+                int cus = 0;
+                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return PDA_ERR_LAUNCH;
+                cu_of_dev[dev] = cus;
+            }
+            const int n_cu = cu_of_dev[dev];
+            const int nunits = utiles * (kUserTile / 32);
+            hipLaunchKernelGGL((warm_score5_kernel<D, BF>), dim3((unsigned)(n_cu < nunits ? n_cu : nunits)), dim3(kWS5Threads), smem, stream, gw);
+            PDA_CHECK_LAUNCH();
+            hipLaunchKernelGGL(warm_select5_kernel, dim3((unsigned)((g.n_users_blk + 4 * kSelRows - 1) / (4 * kSelRows))), dim3(256), 0, stream, gw);
+            PDA_CHECK_LAUNCH();
+            return PDA_OK;
+        }
+    }
+    if (c.warm != Call4::kWarm4) return PDA_ERR_ARG;      // (a warm-up this instantiation does not have)
+    constexpr size_t smem = 32 * D * 4 + (size_t)kUserTile * (kCap4 * 8 + 8) + kUserTile * 2 * kWarmTiles * 4 + 256 + kUserTile * 8;
+    static char attr_done[kMaxDev4] = {};
+    if (const int rc = dynamic_lds_once(reinterpret_cast<const void*>(&warm4_kernel<D, HEAD, BF>), smem, attr_done)) return rc;
+    hipLaunchKernelGGL((warm4_kernel<D, HEAD, BF>), dim3((unsigned)(utiles * gw.n_splits)), dim3(kThreads), smem, stream, gw);
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
 
 template <int D, int HEAD, bool BF>
-int launch4_sweep(const Args4& g, hipStream_t stream, int geometry);
-
-template <int D, int HEAD, bool BF>
-int launch4(const Args4& g, int phase, hipStream_t stream, int geometry) {      // phase: 1 = warm-up only, 2 = sweep only, 3 = both
-    bool warm_two = false;
-    if constexpr (HEAD == PDA_HEAD_POP && D <= 128) warm_two = (phase & 1) && g.wscore != nullptr;
-    if constexpr (HEAD == PDA_HEAD_POP && D <= 128) {
-        if (warm_two) {
-            // the dense call of the huge geometry: score kernel + select kernel in place of warm4_kernel (run_score4 decides where)
-            constexpr size_t smem = warm_score5_lds(D);
-            // (the attribute and the CU count belong to a device: a process may drive several)
-            constexpr int kMaxDev = 64;
-            static int cu_of_dev[kMaxDev] = {};
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return PDA_ERR_LAUNCH;
-            if (cu_of_dev[dev] == 0) {
-                int cus = 0;
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return PDA_ERR_LAUNCH;
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&warm_score5_kernel<D, BF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)smem) != hipSuccess)
-                    return PDA_ERR_LAUNCH;
-                cu_of_dev[dev] = cus;
-            }
-            const int n_cu = cu_of_dev[dev];
-            const int nunits = (g.n_users_blk + kUserTile - 1) / kUserTile * (kUserTile / 32);
-            hipLaunchKernelGGL((warm_score5_kernel<D, BF>), dim3((unsigned)(n_cu < nunits ? n_cu : nunits)), dim3(kWS5Threads), smem, stream, g);
-            PDA_CHECK_LAUNCH();
-            hipLaunchKernelGGL(warm_select5_kernel, dim3((unsigned)((g.n_users_blk + 4 * kSelRows - 1) / (4 * kSelRows))), dim3(256), 0, stream, g);
-            PDA_CHECK_LAUNCH();
-        }
+int launch4(const Args4& g, const Call4& c, hipStream_t stream) {
+    if (c.warm != Call4::kNoWarm) {
+        if (const int rc = launch_warm4<D, HEAD, BF>(g, c, stream)) return rc;
     }
-    if ((phase & 1) && !warm_two) {
-        constexpr int CAP = kCap4;
-        const size_t smem = 32 * D * 4 + (size_t)kUserTile * (CAP * 8 + 8) + kUserTile * 2 * kWarmTiles * 4 + 256 + kUserTile * 8;
-        constexpr int kMaxDev = 64;
-        static char attr_set[kMaxDev] = {};      // (per device, as above)
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return PDA_ERR_LAUNCH;
-        if (!attr_set[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&warm4_kernel<D, HEAD, BF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem) != hipSuccess)
-                return PDA_ERR_LAUNCH;
-            attr_set[dev] = 1;
-        }
-        const int utiles = (g.n_users_blk + kUserTile - 1) / kUserTile;
-        Args4 gw = g;
-        if (g.warm_shared) {             // ONE warm-up per user: "split 0 of 1" scores tiles 0 .. warm_tiles - 1 of the whole order
-            gw.n_splits = 1;
-            gw.warm_shared = 0;
-        }
-        hipLaunchKernelGGL((warm4_kernel<D, HEAD, BF>), dim3((unsigned)(utiles * gw.n_splits)), dim3(kThreads), smem, stream, gw);
-        PDA_CHECK_LAUNCH();
+    if (c.sweep == Call4::kNoSweep || c.ends_in_warm) return PDA_OK;
+    // the huge geometry (pda_v5_sweep.h): 1 024-user workgroups, or (d = 256, config 5) 512-user ones: 128 users per wave fill the 256 AGPRs
+    if constexpr (HEAD == PDA_HEAD_POP) {
+        if (c.sweep == Call4::kSweep5) return launch_sweep5<D, BF, true, D == 256 ? 128 : 256>(g, c, stream);
     }
-    if ((g.n_tiles + g.n_splits - 1) / g.n_splits <= g.warm_tiles) return PDA_OK;      // every split ends inside its warm-up
-    if (phase & 2) {
-        Args4 gs = g;
-        if (g.warm_shared) gs.seed = g.seed_out;      // every split prunes against the shared warm-up's K-th value
-        return launch4_sweep<D, HEAD, BF>(gs, stream, geometry);
+    if constexpr (D <= 128) {
+        if (c.sweep == Call4::kSweep4Many) return launch_sweep4<D, HEAD, BF, 3>(g, c, stream);
     }
-    return PDA_OK;
-}
-
-template <int D, int HEAD, bool BF>
-int launch4_sweep(const Args4& g, hipStream_t stream, int geometry) {
-    {
-        // the huge geometry (pda_v5_sweep.h): dense sweeps of the popularity head on a prep built WITH that popularity -- 1 024-user workgroups,
-        // or (d = 256, config 5) 512-user ones: 128 users per wave fill the 256 AGPRs.  Anything else asked for with that hint: the default.
-        if constexpr (HEAD == PDA_HEAD_POP) {
-            if (geometry == 4 && g.sufA == nullptr && g.prep_hdr_pop != 0) return launch_sweep5<D, BF, true, D == 256 ? 128 : 256>(g, stream);
-        }
-        if constexpr (D <= 128) {
-            if (geometry == 3) return launch_sweep4<D, HEAD, BF, 3>(g, stream);
-        }
-        return launch_sweep4<D, HEAD, BF, 0>(g, stream);
-    }
-    return PDA_OK;
+    if (c.sweep != Call4::kSweep4) return PDA_ERR_ARG;    // (a sweep this instantiation does not have)
+    return launch_sweep4<D, HEAD, BF, 0>(g, c, stream);
 }
 
 int user_tile4(int d) { return d == 64 ? Geo4<64>::UT : d == 128 ? Geo4<128>::UT : Geo4<256>::UT; }
-static bool lists_in_hbm4(int) { return true; }       // (every d may run with its lists in the workspace since round 3: Geo4<D, true>)
-// the workspace of the pda_score_topk4_* calls: the counters of pda_score_topk_workspace_bytes, then (workgroups of 512 users:
-// d <= 128) the list slots of every workgroup
-// the workspace of the pda_score_topk4_* calls: [counters of pda_score_topk_workspace_bytes | list slots of every workgroup when the
-// lists live in HBM | Bloom filters, 128 B per user | warm-position train-item masks, 32 B per user and split | regrouping: 1024 bins, bin and sweep row of every user]
+// the workspace of the pda_score_topk4_* calls: [counters of pda_score_topk_workspace_bytes | list slots of every workgroup (the lists of
+// every d may live in HBM) | Bloom filters, 128 B per user | warm-position train-item masks, 32 B per user and split | regrouping: 1024 bins,
+// bin and sweep row of every user]
 struct Ws4 {
     size_t lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, kth, wscore, total;
 };
@@ -2480,10 +2387,8 @@ static Ws4 ws4_layout(int n_users_blk, int d, int n_splits) {
     Ws4 w{};
     w.lists = al(pda_score_topk_workspace_bytes(n_users_blk));
     size_t b = w.lists;
-    if (lists_in_hbm4(d)) {
-        const size_t ut = 1024;         // (the widest user tile of any geometry: the huge one's)
-        b += ((size_t)n_users_blk + ut - 1) / ut * (size_t)n_splits * ut * kCap4 * 8 + 256;
-    }
+    const size_t ut = 1024;             // (the widest user tile of any geometry: the huge one's)
+    b += ((size_t)n_users_blk + ut - 1) / ut * (size_t)n_splits * ut * kCap4 * 8 + 256;
     w.bloom = al(b);
     w.hmask = al(w.bloom + (size_t)n_users_blk * 128);
     w.regroup = al(w.hmask + ((size_t)n_users_blk + kUserTile - 1) / kUserTile * (size_t)n_splits * kUserTile * 2 * kWarmTiles * 4);
@@ -2536,10 +2441,7 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     if (K > kCap4 - 3) return PDA_ERR_UNSUPPORTED;
     if ((uint64_t)n_items_local > (1ull << 26)) return PDA_ERR_UNSUPPORTED;          // ring words: 6-bit row, 26-bit local item id
     if (warm_tiles < 0 || warm_tiles > kWarmTiles) return PDA_ERR_ARG;
-#ifndef PDA_V4_WARM_DEFAULT
-#define PDA_V4_WARM_DEFAULT kWarmTiles
-#endif
-    if (warm_tiles == 0) warm_tiles = d <= 128 ? PDA_V4_WARM_DEFAULT : kWarmTiles;
+    if (warm_tiles == 0) warm_tiles = kWarmTiles;
     // phase 4: a sweep of the WHOLE shard from empty lists against the caller's seed (no warm-up on this catalogue)
     const bool from_empty = phase == 4;
     if (from_empty) {
@@ -2551,105 +2453,122 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     }
     if (n_splits <= 0) n_splits = pda_score_topk4_auto_splits(n_users_blk, n_items_local, d);
     const Prep4Layout L = prep4_layout(n_items_local, d);
+    const bool pop_head = head == PDA_HEAD_POP;
+    const bool hist = hist_indptr != nullptr;
+
+    // ---- what the call launches: every decision formed here, once
+    Call4 c{};
+    c.ends_in_warm = (L.n_tiles + n_splits - 1) / n_splits <= warm_tiles;
+    c.early_stop = early_stop != 0;
+    // the huge geometry (pda_v5_sweep.h): dense sweeps of the popularity head.  (The prep is the caller's, built by pda_item_prep4_* with the
+    // SAME pop_shard it passes here: ops.item_prep4 keys its cache on it, so the image is scaled by the popularities being ranked.)  Anything
+    // else asked for with that hint, and the many-candidates hint at d = 256: the default geometry.
+    c.sweep = !(phase & 2) ? Call4::kNoSweep
+              : (geometry == 4 && pop_head && !early_stop) ? Call4::kSweep5
+              : (geometry == 3 && d <= 128) ? Call4::kSweep4Many : Call4::kSweep4;
+    // the dense call of the huge geometry: sweep5_kernel behind a warm-up of this call
+    const bool dense5 = phase == 3 && c.sweep == Call4::kSweep5 && !c.ends_in_warm;
+    c.uprep5 = !(dense5 && n_users_dev == nullptr);        // (the warm-up writes the image only for a block whose size the host knows)
+    // one call over several item splits: ONE exact warm-up per user instead of one per split (warm_tiles_of; PDA_SWEEP_WARM_PER_SPLIT)
+    const bool warm_shared = phase == 3 && n_splits > 1 && seed == nullptr && !warm_per_split && L.n_tiles > n_splits * warm_tiles;
+    c.warm_whole = n_splits == 1 || warm_shared;
+    // the exact warm-up of the dense call as a score kernel and a select kernel (warm_score5_kernel; PDA_SWEEP_WARM_ONE_KERNEL restores
+    // warm4_kernel): where the warm-up writes the sweep's user image, one warm-up over the front of the whole order, d <= 128 (a 256 KB fp32
+    // image does not fit the LDS), and at most 2^21 users per block -- the score kernel addresses its region with 32-bit word offsets
+    // (2^21 x 256 words = 2 GB of scores); larger blocks run warm4_kernel, and the witness word says so
+    c.warm = !(phase & 1) ? Call4::kNoWarm
+             : (!c.uprep5 && d <= 128 && !warm_one_kernel && c.warm_whole && n_users_blk <= (1 << 21)) ? Call4::kWarmTwo : Call4::kWarm4;
+    // (sweep5_kernel masks train items through the history itself and never reads the Bloom filters)
+    c.bloom = hist && (c.sweep == Call4::kSweep4 || c.sweep == Call4::kSweep4Many);
+    // the warm-position masks: from the caller's table of all users (pda_score_topk4_phase_mask_table) wherever ONE warm-up covers the front
+    // of the whole visiting order -- blocks of any size; no walk, no warm_mask4_kernel.  Else by a kernel of its own (see warm_mask4_kernel)
+    // where it pays for its launch -- 1.35 -> 1.29 ms per early-terminating sweep of 262 144 users, but 0.267 -> 0.277 ms at 50 000 -- and
+    // always in front of warm_score5_kernel, which walks no history
+    const bool mask_from_table = mask_table != nullptr && hist && hist_row_mode == PDA_HIST_BY_USER_ID && (phase & 1) && n_users_dev == nullptr && c.warm_whole;
+    c.mask_kernel = !mask_from_table && hist && (phase & 1) && (n_users_blk >= 98304 || c.warm == Call4::kWarmTwo);
+    // users regrouped by predicted stopping tile (stop_predict4_kernel): where the workgroups come in more than one round
+    constexpr int kRegroupMin = 98304;
+    c.regroup = early_stop && (phase & 2) && n_splits == 1 && n_users_blk >= kRegroupMin;
+
+    // ---- the kernels' arguments
     const unsigned char* pb = reinterpret_cast<const unsigned char*>(prep);
-    if (((phase & 1) || from_empty) && hipMemsetAsync(workspace, 0, pda_score_topk_workspace_bytes(n_users_blk), s) != hipSuccess) return PDA_ERR_LAUNCH;
-    const Ws4 W = ws4_layout(n_users_blk, d, n_splits);
     unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
-    const float* sA = reinterpret_cast<const float*>(pb + (head == PDA_HEAD_POP ? L.sufA : L.sufB));
-    const float* sB = reinterpret_cast<const float*>(pb + (head == PDA_HEAD_POP ? L.sufB : L.sufR));
-    // raw head: bound = ||u|| max ||i||: sufA := 0 is not stored -- the raw-head vote uses (sufB' = sufR, sufA' = 0) through
-    // the same fma; a zero array is the front of sufA of a prep WITHOUT popularity (tile_bound4_kernel, has_pop = 0)
-    Args4 g{U, I_shard, pop_shard, users, hist_indptr, hist_indices, out_keys, pb + L.rows,
-            early_stop ? sA : nullptr, early_stop ? sB : nullptr, reinterpret_cast<const int*>(pb + L.pos_of),
-            reinterpret_cast<unsigned*>(workspace), reinterpret_cast<uint64_t*>(wsb + W.lists), nullptr, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const int*>(pb + L.hdr), seed, n_users_blk, item_offset, n_items_local, hist_row_mode, K, n_splits, L.n_tiles, warm_tiles,
-            // sorted hand-over when nobody sorts behind the warm-up: phase 1 alone, or a catalogue that ends inside the warm-up
-#ifdef PDA_V4_WARM_SORTED
-            1, nullptr, pb + L.rows5, reinterpret_cast<const float*>(pb + L.meta5), nullptr, nullptr, 0};
-#else
-            (phase == 1 || (L.n_tiles + n_splits - 1) / n_splits <= warm_tiles) ? 1 : 0, nullptr,
-            pb + L.rows5, reinterpret_cast<const float*>(pb + L.meta5), nullptr, nullptr, 0};
-#endif
-    // warm-up and sweep in one call: K .. kCap4 keys per row through the workspace (see warm4_kernel)
-    if (phase == 3 && !g.warm_sorted && PDA_V4_HANDOVER_WS) g.handover = reinterpret_cast<uint64_t*>(wsb + W.handover);
+    const Ws4 W = ws4_layout(n_users_blk, d, n_splits);
+    Args4 g{};
+    g.U = U;
+    g.I = I_shard;
+    g.pop = pop_shard;
+    g.users = users;
+    g.hist_indptr = hist_indptr;
+    g.hist_indices = hist_indices;
+    g.out_keys = out_keys;
+    g.rows = pb + L.rows;
+    // (raw head: bound = ||u|| max ||i||: the vote uses (sufB' = sufR, sufA' = 0) through the same fma; a zero array is sufA of a prep
+    // WITHOUT popularity -- tile_bound4_kernel, has_pop = 0)
+    g.sufA = early_stop ? reinterpret_cast<const float*>(pb + L.sufA) : nullptr;
+    g.sufB = early_stop ? reinterpret_cast<const float*>(pb + (pop_head ? L.sufB : L.sufR)) : nullptr;
+    g.pos_of = reinterpret_cast<const int*>(pb + L.pos_of);
+    g.stats = reinterpret_cast<unsigned*>(workspace);
+    g.lists_ws = reinterpret_cast<uint64_t*>(wsb + W.lists);
+    g.prep_hdr = reinterpret_cast<const int*>(pb + L.hdr);
+    g.seed = seed;
+    g.n_users_blk = n_users_blk;
+    g.item_offset = item_offset;
+    g.n_items_local = n_items_local;
+    g.hist_row_mode = hist_row_mode;
+    g.K = K;
+    g.n_splits = n_splits;
+    g.n_tiles = L.n_tiles;
+    g.warm_tiles = warm_tiles;
+    // sorted hand-over when nobody sorts behind the warm-up: phase 1 alone, or a catalogue that ends inside the warm-up
+    g.warm_sorted = (phase == 1 || c.ends_in_warm) ? 1 : 0;
+    g.rows5 = pb + L.rows5;
+    g.meta5 = reinterpret_cast<const float*>(pb + L.meta5);
     g.ufrag = wsb + W.ufrag;
     g.unorm = reinterpret_cast<const float*>(wsb + W.unorm);
-    // (the prep is the caller's, built by pda_item_prep4_* with the SAME pop_shard it passes here for the popularity head: ops.item_prep4
-    // keys its cache on it; a prep built without one carries an unscaled image and the huge geometry falls back to the default one)
-    g.prep_hdr_pop = (head == PDA_HEAD_POP && pop_shard != nullptr) ? 1 : 0;
-    g.warm_final = (geometry >= 4 && phase == 3 && g.handover != nullptr && g.prep_hdr_pop && !early_stop) ? 1 : 0;
+    g.prep_hdr_pop = pop_head ? 1 : 0;
     g.lists_empty = from_empty ? 1 : 0;
     g.n_users_dev = n_users_dev;
-    // the dense call of the huge geometry (launch4_sweep's conditions for sweep5_kernel, behind a warm-up of this call):
-#ifndef PDA_V5_HANDOVER             // (A/B build: the warm-up's rows through the hand-over AND out_keys -- tools/build_variant.sh handover -DPDA_V5_HANDOVER)
-    if (g.warm_final && geometry == 4) {            // no hand-over copy: sorted rows to out_keys, K-th values to the workspace
-        g.handover = nullptr;
+    if (dense5) {                        // no hand-over copy: the warm-up's sorted rows to out_keys, their K-th values to the workspace
+        g.warm_final = 1;
         g.kth_ws = reinterpret_cast<float*>(wsb + W.kth);
+    } else if (phase == 3 && !c.ends_in_warm) {
+        // warm-up and sweep in one call: K .. kCap4 keys per row through the workspace (see warm4_kernel)
+        g.handover = reinterpret_cast<uint64_t*>(wsb + W.handover);
     }
-#endif
-#ifndef PDA_V5_UPREP                // (A/B build: uprep5_kernel in every call -- tools/build_variant.sh uprep -DPDA_V5_UPREP)
-    if (geometry == 4 && phase == 3 && g.prep_hdr_pop && !early_stop && n_users_dev == nullptr && (L.n_tiles + n_splits - 1) / n_splits > warm_tiles) {
-        g.ufrag_out = wsb + W.ufrag;                // warm4_kernel writes the sweep's user image: launch_sweep5 launches no uprep5_kernel
+    if (!c.uprep5) {                     // the warm-up writes the sweep's user image: launch_sweep5 launches no uprep5_kernel
+        g.ufrag_out = wsb + W.ufrag;
         g.unorm_out = reinterpret_cast<float*>(wsb + W.unorm);
     }
-#endif
-    if (g.prep_hdr_pop) {                // the suffix bounds of the popularities being ranked: the huge geometry's decided half-tile
+    if (pop_head) {                      // the suffix bounds of the popularities being ranked: the huge geometry's decided half-tile
         g.tailA = reinterpret_cast<const float*>(pb + L.sufA);
         g.tailB = reinterpret_cast<const float*>(pb + L.sufB);
     }
-    // one call over several item splits: ONE exact warm-up per user instead of one per split (warm_tiles_of; PDA_SWEEP_WARM_PER_SPLIT)
-    if (phase == 3 && n_splits > 1 && seed == nullptr && !warm_per_split && L.n_tiles > n_splits * warm_tiles) {
+    if (warm_shared) {                   // the warm-up leaves every row's K-th value, and every split prunes against it
         g.warm_shared = 1;
         g.seed_out = reinterpret_cast<float*>(wsb + W.seed);
+        g.seed = g.seed_out;
     }
-    // the exact warm-up of that call as a score kernel and a select kernel (warm_score5_kernel; PDA_SWEEP_WARM_ONE_KERNEL restores
-    // warm4_kernel): one warm-up over the front of the whole order, d <= 128 (a 256 KB fp32 image does not fit the LDS), and at most
-    // 2^21 users per block -- the score kernel addresses its region with 32-bit word offsets (2^21 x 256 words = 2 GB of scores); larger
-    // blocks run warm4_kernel, and the witness word says so
-    const bool warm_two = g.ufrag_out != nullptr && g.kth_ws != nullptr && d <= 128 && !warm_one_kernel && (n_splits == 1 || g.warm_shared) &&
-                          n_users_blk <= (1 << 21);
-    if (warm_two) g.wscore = reinterpret_cast<uint32_t*>(wsb + W.wscore);
-    // (sweep5_kernel masks train items through the history itself and never reads the Bloom filters: no launch where launch4_sweep takes it)
-    const bool sweep5 = head == PDA_HEAD_POP && geometry == 4 && !early_stop && g.prep_hdr_pop != 0;
-    if (hist_indptr && (phase & 2) && !sweep5) {
-        uint32_t* bloom = reinterpret_cast<uint32_t*>(wsb + W.bloom);
-        hipLaunchKernelGGL(hist_bloom4_kernel, dim3((unsigned)((n_users_blk + 31) / 32)), dim3(256), 0, s, users, hist_indptr, hist_indices,
-                           hist_row_mode, n_users_blk, bloom, reinterpret_cast<const int*>(pb + L.hdr), head == PDA_HEAD_POP ? 1 : 0);
-        PDA_CHECK_LAUNCH();
-        g.bloom = bloom;
-    }
-    // the warm-position masks: from the caller's table of all users (pda_score_topk4_phase_mask_table) wherever ONE warm-up covers the front
-    // of the whole visiting order -- blocks of any size; no walk, no warm_mask4_kernel
-    if (mask_table != nullptr && hist_indptr && hist_row_mode == PDA_HIST_BY_USER_ID && (phase & 1) && n_users_dev == nullptr &&
-        (n_splits == 1 || g.warm_shared)) {
+    if (c.warm == Call4::kWarmTwo) g.wscore = reinterpret_cast<uint32_t*>(wsb + W.wscore);
+    if (c.bloom) g.bloom = reinterpret_cast<uint32_t*>(wsb + W.bloom);
+    if (mask_from_table) {
         g.hmask_tab = mask_table;
         g.hmask_tab_rows = mask_table_rows;
-    } else if (hist_indptr && (phase & 1) && (n_users_blk >= 98304 || warm_two)) {        // (warm_score5_kernel walks no history: always in front of it)
-        // the train-item bits of the warm positions, by a kernel of its own (see warm_mask4_kernel) -- where it pays for its launch:
-        // 1.35 -> 1.29 ms per early-terminating sweep of 262 144 users, but 0.267 -> 0.277 ms at 50 000
-        uint32_t* hm = reinterpret_cast<uint32_t*>(wsb + W.hmask);
-        const int utiles = (n_users_blk + kUserTile - 1) / kUserTile;
-        Args4 gm = g;
-        if (g.warm_shared) {
-            gm.n_splits = 1;
-            gm.warm_shared = 0;
-        }
-        hipLaunchKernelGGL(warm_mask4_kernel, dim3((unsigned)(utiles * gm.n_splits)), dim3(kThreads), 0, s, gm, hm);
-        PDA_CHECK_LAUNCH();
-        g.hmask_ws = hm;
     }
-#ifndef PDA_V4_REGROUP_MIN
-#define PDA_V4_REGROUP_MIN 98304
-#endif
-    // users regrouped by predicted stopping tile (stop_predict4_kernel): where the workgroups come in more than one round
-    if (early_stop && (phase & 2) && n_splits == 1 && n_users_blk >= PDA_V4_REGROUP_MIN) {
+    if (c.mask_kernel) g.hmask_ws = reinterpret_cast<uint32_t*>(wsb + W.hmask);
+    if (c.regroup) {
         g.regroup_ws = reinterpret_cast<int32_t*>(wsb + W.regroup);
         if (phase & 1) g.pred_ws = reinterpret_cast<float*>(g.regroup_ws + 1024 + 2 * (size_t)n_users_blk);       // (a sweep of its own reads the lists)
     }
-    if (head == PDA_HEAD_RAW) {
-        g.sufA = early_stop ? reinterpret_cast<const float*>(pb + L.sufA) : nullptr;     // all zero for a raw prep
-        g.sufB = early_stop ? reinterpret_cast<const float*>(pb + L.sufR) : nullptr;
+
+    // ---- the launches
+    if (((phase & 1) || from_empty) && hipMemsetAsync(workspace, 0, pda_score_topk_workspace_bytes(n_users_blk), s) != hipSuccess) return PDA_ERR_LAUNCH;
+    if (c.bloom) {
+        hipLaunchKernelGGL(hist_bloom4_kernel, dim3((unsigned)((n_users_blk + 31) / 32)), dim3(256), 0, s, users, hist_indptr, hist_indices,
+                           hist_row_mode, n_users_blk, const_cast<uint32_t*>(g.bloom), g.prep_hdr, pop_head ? 1 : 0);
+        PDA_CHECK_LAUNCH();
     }
-#define PDA_V4_(DD, BFV) (head == PDA_HEAD_POP ? launch4<DD, PDA_HEAD_POP, BFV>(g, phase, s, geometry) : launch4<DD, PDA_HEAD_RAW, BFV>(g, phase, s, geometry))
+#define PDA_V4_(DD, BFV) (pop_head ? launch4<DD, PDA_HEAD_POP, BFV>(g, c, s) : launch4<DD, PDA_HEAD_RAW, BFV>(g, c, s))
     switch (d) {
         case 64: return bf16 ? PDA_V4_(64, true) : PDA_V4_(64, false);
         case 128: return bf16 ? PDA_V4_(128, true) : PDA_V4_(128, false);
@@ -2806,14 +2725,6 @@ extern "C" int pda_topk_seed_pick(const float* bounds, const int32_t* counts, in
     return PDA_OK;
 }
 
-#ifdef PDA_V5_LOG
-
-extern "C" int pda_debug_v5_log(unsigned* out, int n_words, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pda_v5_log), (size_t)n_words * 4) != hipSuccess) return PDA_ERR_LAUNCH;
-    if (reset) { unsigned z = 0; if (hipMemcpyToSymbol(HIP_SYMBOL(pda_v5_log), &z, 4) != hipSuccess) return PDA_ERR_LAUNCH; }
-    return PDA_OK;
-}
-#endif
 #ifdef PDA_V5_EXITPROF
 extern "C" int pda_debug_v5_exitprof(unsigned long long* out, int n_workgroups) {     /* [n_workgroups][4 waves][8] of the LAST sweep5_kernel launch */
     if (!out || n_workgroups < 1 || n_workgroups > kXpMaxWg) return PDA_ERR_ARG;

@@ -40,13 +40,6 @@
 #endif
 #include "pda_v6_free_asm.h"           // its test-free bodies (tools/gen_v6_loop_asm.py --free: made by the Makefile, not kept in the repository)
 
-#ifdef PDA_V5_LOG
-__device__ unsigned pda_v5_log[1 << 18];      // debug build: [0] = entries used; then (block << 8 | wave, kind, a, b) per event
-#define V5LOG(kind, a, b) do { if (lane == 0) { const unsigned i_ = atomicAdd(&pda_v5_log[0], 1u); if (i_ < (1u << 16) - 1u) { \
-    pda_v5_log[4 * i_ + 4] = ((unsigned)blockIdx.x << 8) | (unsigned)wave; pda_v5_log[4 * i_ + 5] = (kind); pda_v5_log[4 * i_ + 6] = (a); pda_v5_log[4 * i_ + 7] = (b); } } } while (0)
-#else
-#define V5LOG(kind, a, b) do {} while (0)
-#endif
 #ifdef PDA_V5_EXITPROF
 // profiling build (tools/build_variant.sh exitprof -DPDA_V5_EXITPROF; read by tools/time_huge_exits.py): what a wave spends OUTSIDE its asm loops,
 // in ticks of the constant 100 MHz wall clock -- per (workgroup, wave): [0] in extract, [1] in rescore_ring behind the extracts, [2] from the end
@@ -70,7 +63,6 @@ constexpr int kRing5 = 192;           // candidate ring entries per wave (u64 ea
 // MFMA cost more clock than the overlap buys (8.38 vs 8.18 ms) -- and the loop on v_mfma_f32_32x32x16_bf16 (9.16 ms).
 template <int D, bool BF, bool S16, int UPW>
 __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
-    [[maybe_unused]] constexpr int HB = half_bytes5(D);
     static_assert(slot_bytes5(D) == Loop6<D, 8>::kSlotBytes, "one LDS image for all loops");
     static_assert(S16, "the loop on v_mfma_f32_32x32x16_bf16 (round 4's first form: 9.16 against 8.07 ms, profiles/README.md) left with round 5; the parameter keeps the kernel's name");
     static_assert((D <= 128 && UPW == 256) || (D == 256 && UPW == 128), "users per wave: 256, or (d = 256) 128 -- 8 blocks x 8 k-steps = 256 AGPRs, one 512-user workgroup per CU");
@@ -345,64 +337,6 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             n_cand += ring_n;
             ring_n = 0;
         };
-#ifdef PDA_V5_EXTRACT_OLD
-        // (A/B build, tools/build_variant.sh extractold -DPDA_V5_EXTRACT_OLD: the exit path before the fused extract -- one call per half-tile,
-        // one user block at a time, the user fragments loaded twice)
-        // ---- a half-tile that raised a flag, scored again with compiler-visible MFMAs: every pair whose bound reaches the user's
-        // threshold -> the ring
-        auto extract = [&](unsigned ft) __attribute__((always_inline)) {
-            const unsigned T = t0 + (ft >> 1) * (unsigned)g.n_splits;                   // its 64-item tile
-            const unsigned pos0 = T * 64u + (ft & 1u) * 32u;                            // visiting position of its first item
-            const float2 mt = *reinterpret_cast<const float2*>(g.meta5 + 4 * (size_t)(2u * T + (ft & 1u)));
-            const float ct = __builtin_fmaf(eu, mt.y, mt.x);
-            const unsigned char* tb = tiles + (ft & (kNSlot5 - 1)) * SS + j * (2 * D);
-            // accumulator register r of the lane <-> item of the half-tile (r = 4 ib + register of chain ib)
-            auto item_of = [&](int r) __attribute__((always_inline)) -> unsigned {
-                return 16u * (r >> 2) + 4u * hh + (r & 3);
-            };
-            constexpr int NR = 8;
-            u32x4 af[2 * NK];
-#pragma unroll
-            for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                for (int k = 0; k < NK; ++k) af[ib * NK + k] = *reinterpret_cast<const u32x4*>(tb + ib * 16 * (2 * D) + (((4 * k + hh) ^ swz5<D>(j)) << 4));
-            for (int u = 0; u < NU; ++u) {
-                const float tl = thr_of(u);
-                const bool clampy = mt.x > tl;
-                uint32_t m = 0;
-#pragma unroll
-                for (int ib = 0; ib < 2; ++ib) {
-                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) {
-                        const u32x4 bf = *reinterpret_cast<const u32x4*>(my_ufrag + (((size_t)u * NK + k) * 64 + lane) * 16);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[ib * NK + k]), __builtin_bit_cast(bf16x8, bf), acc, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) m |= (acc[r] + ct > tl) ? (1u << (4 * ib + r)) : 0u;
-                }
-                if (__any(clampy)) {
-                    // (rare: a user whose threshold lies below a popularity of this half-tile -- a head pop x exp(s), s <= 0, may qualify)
-#pragma unroll
-                    for (int r = 0; r < NR; ++r) {
-                        const unsigned pp = pos0 + item_of(r);
-                        const float pi = clampy ? *reinterpret_cast<const float*>(g.rows + (size_t)pp * RB4 + 2 * D + 32) : 0.f;
-                        m |= (clampy && pi > tl) ? (1u << r) : 0u;
-                    }
-                }
-                while (__any(m != 0u)) {
-                    if (ring_n + 64u > (unsigned)kRing5) rescore_ring();
-                    const bool act = m != 0u;
-                    const int r = __builtin_ctz(m | 0x10000u);
-                    m &= ~(1u << r);
-                    const uint64_t pm = __ballot(act);
-                    const unsigned slot = ring_n + (unsigned)__builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0));
-                    if (act) my_ring[slot] = ((uint64_t)(unsigned)(UBW * u + j) << 32) | (uint64_t)(pos0 + item_of(r));
-                    ring_n += (unsigned)__popcll(pm);
-                }
-            }
-        };
-#else
         // ---- the two half-tiles behind an exit at half-tile hx (hx - 2 raised the flag, the flags of hx - 1 were still being worked out), scored
         // again with compiler-visible MFMAs in ONE pass over the user blocks: every pair whose bound reaches the user's threshold -> the ring.
         // With one wave per SIMD nothing hides a round trip to the user image (the rows cannot stay in AGPRs across the asm statements), and a pass
@@ -536,7 +470,6 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
                 }
             }
         };
-#endif
 
         // ---- the workgroup's DECIDED half-tile: the first local half-tile from which no pair of the rest of the split can reach ANY row's
         // threshold -- the criterion that ends generation 4's early-terminating sweeps (stop_predict4_kernel, the votes of sweep4_kernel),
@@ -593,7 +526,6 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
                     n_free = hend - h;
                     XP(if (xp_out != 0) { const unsigned long long t_ = wall_clock64(); xp[3] += t_ - xp_out; xp[2] += t_ - xp_re; xp_out = 0; } else xp[6] = wall_clock64() - xp_k0;)
                     Loop6Free<D, NU>::run(h, issued, hend, ring_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits, (unsigned)img, (unsigned)(img >> 32), my_ufrag, lane16);
-                    V5LOG(14u, h, n_free);
                 }
                 break;
             }
@@ -603,39 +535,18 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             Loop6<D, NU>::run(h, issued, reason, hlim, ring_lds, flags_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits,
                               (unsigned)img, (unsigned)(img >> 32), (unsigned)meta, (unsigned)(meta >> 32), eu, tmin, my_ufrag, thr, lane16);
             XP(xp_out = wall_clock64(); xp_re = xp_out;)
-            V5LOG(reason, h, issued);
             if (reason == 0u) {
                 if (hlim == hend) break;
                 continue;                                                // (the flags of every half-tile below hlim have been looked at: test-free from hlim on)
             }
             if (reason != 1u) { if (lane == 0) g.stats[0] = 5u; break; }
-#ifdef PDA_V5_LOG
-            // LDS integrity: the half-tiles about to be scored again and the one in progress, in their slots, against the image
-            for (unsigned tq = (h >= 2u ? h - 2u : 0u); tq <= h && tq < hlim; ++tq) {
-                const unsigned Tq = t0 + (tq >> 1) * (unsigned)g.n_splits;
-                const unsigned char* gsrc = g.rows5 + ((size_t)(2u * Tq + (tq & 1u))) * HB;
-                const unsigned char* lsrc = tiles + (tq & (kNSlot5 - 1)) * SS;
-                unsigned pieces = 0;
-                for (int i = 0; i < HB / 1024; ++i) {
-                    const u32x4 a4 = *reinterpret_cast<const u32x4*>(gsrc + i * 1024 + lane * 16);
-                    const u32x4 b4 = *reinterpret_cast<const u32x4*>(lsrc + i * 1024 + lane * 16);
-                    if (__ballot(((a4[0] ^ b4[0]) | (a4[1] ^ b4[1]) | (a4[2] ^ b4[2]) | (a4[3] ^ b4[3])) != 0u) != 0ull) pieces |= 1u << i;
-                }
-                if (pieces != 0u) V5LOG(13u, (tq << 8) | (h - tq), pieces);
-            }
-#endif
             // every wave of the workgroup left at half-tile h because SOME wave's lanes flagged h - 2; the flags of h - 1 were still being
             // worked out: both are scored again here (a half-tile without a candidate of this wave costs its 8 NK MFMAs)
+            // (`before` has had no reader since the debug log left.  It stays for now: without this dead local hipcc allocates the kernel's
+            // scalar registers differently -- a change of this kernel's code, which wants its own measurement: DESIGN 7)
             [[maybe_unused]] const unsigned before = ring_n + n_cand;
-#ifdef PDA_V5_EXTRACT_OLD
-            // (below hlim: what the tested body scored behind its end are copies of half-tile hlim - 1)
-            if (h >= 2u && h - 2u < hlim) extract(h - 2u);
-            if (h >= 1u && h - 1u < hlim) extract(h - 1u);
-#else
             extract2(h, hlim);
-#endif
             XP(const unsigned long long xp_a = wall_clock64(); xp[0] += xp_a - xp_out; xp[4] += 1;)
-            V5LOG(10u, h, ring_n + n_cand - before);
             // (thresholds rise only through the lists: rescoring a ring that holds a pass's worth keeps them fresh enough)
             if (ring_n >= (unsigned)CPP) rescore_ring();
             XP(xp_re = wall_clock64(); xp[1] += xp_re - xp_a;)
@@ -724,19 +635,15 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
 }
 
 template <int D, bool BF, bool S16, int UPW>
-int launch_sweep5(const Args4& g, hipStream_t stream) {
+int launch_sweep5(const Args4& g, const Call4& c, hipStream_t stream) {
     constexpr int UT = 4 * UPW;
     constexpr size_t lds = (size_t)kNSlot5 * slot_bytes5(D) + (size_t)UT * 8 + 4 * kRing5 * 8 + 80 * 4 + 64;
     static_assert(UPW == 256 || D == 256 || 2 * lds <= 160 * 1024, "two workgroups per CU");
     static_assert(lds <= 160 * 1024, "LDS per workgroup");
-    static int attr_set = 0;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep5_kernel<D, BF, S16, UPW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return PDA_ERR_LAUNCH;
-        attr_set = 1;
-    }
+    static char attr_done[kMaxDev4] = {};
+    if (const int rc = dynamic_lds_once(reinterpret_cast<const void*>(&sweep5_kernel<D, BF, S16, UPW>), lds, attr_done)) return rc;
     const int utiles = (g.n_users_blk + UT - 1) / UT, n_pad = utiles * UT;
-    if (g.ufrag_out == nullptr) {        // (else: the warm-up of this call has written the user image and the norms -- warm4_kernel)
+    if (c.uprep5) {                      // (else: the warm-up of this call has written the user image and the norms -- Args4::ufrag_out)
         hipLaunchKernelGGL((uprep5_kernel<D, BF, S16, UPW>), dim3((unsigned)(((size_t)n_pad * (D / 8) + 255) / 256)), dim3(256), 0, stream, g.U, g.users, g.n_users_blk, n_pad,
                            const_cast<unsigned char*>(g.ufrag), const_cast<float*>(g.unorm));
         PDA_CHECK_LAUNCH();

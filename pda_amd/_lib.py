@@ -1,5 +1,5 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
-pda_hip_deep.h, pda_hip_xquad.h and pda_hip_dice.h).
+pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h and pda_hip_ips.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -200,6 +200,13 @@ DICE_SIGNATURES = {
     "pda_dice_sample_dev": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_ips.h (IPS, IPS-C, IPS-CN: `--train ips`)
+IPS_SIGNATURES = {
+    "pda_ips_weight_sum": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pda_ips_step_f32": (_i, [_vp, _vp, _sz, _sz] + [_vp] * 5 + [_i, _i, _f, _f] + [_vp] * 4 + [_i, _i, _vp, _vp]),
+    "pda_ips_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 5 + [_i, _i, _f, _f, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -218,7 +225,8 @@ def load():
             "or `make -C pda_amd/csrc`.  pda_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
-            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()):
+            list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
+            list(IPS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

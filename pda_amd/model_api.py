@@ -4,6 +4,7 @@
     BPRMFTempPop       BPRMF(t)-pop        MF/model_api.py:300-416   (temporal popularity bias; Adam sweep only)
     BPRMF              plain BPR-MF        MF/model_api.py:419-757   (only :419-471, :521-536, :695-706 are live)
     DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
+    IPSBPRMF           IPS / IPS-C / IPS-CN (no reference code: DESIGN.md 5g)  a BPRMF trained with inverse propensity weights; Adam sweep only
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
 trainer passes to `sess.run`.  Here they are light handle objects understood by `pda_amd.train_new_api.Session`,
@@ -633,3 +634,83 @@ class DICE(_MFBase):
             st = self._dice_state()
             for k in ("mU", "vU", "mI", "vI"):
                 getattr(st, k).copy_(sd[k])
+
+
+def ips_item_counts(train_user_list, n_items: int):
+    """The train interactions of every item, int64 numpy [n_items], from the loader's {user: [items]} lists: what the propensities are built from."""
+    import numpy as np
+    counts = np.zeros(int(n_items), dtype=np.int64)
+    for items in train_user_list.values():
+        if len(items):
+            counts += np.bincount(np.asarray(items, dtype=np.int64), minlength=int(n_items))
+    return counts
+
+
+def check_ips(args):
+    """--train ips: refuse, before anything is built, what the IPS step has no kernel for.  Every message names its flag."""
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train ips sums its gradients with float atomics (no planned gradient)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train ips runs fp32 tables only" % args.table_dtype)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train ips runs the reference's dense-decay Adam only (--optimizer adam)" % args.optimizer)
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("--adam_sweep %s: --train ips runs the dense Adam sweep only (auto | sweep)" % getattr(args, "adam_sweep", "auto"))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train ips trains on one GPU" % args.gpus)
+    if not float(getattr(args, "ips_clip", 0.0)) >= 0.0:
+        raise ValueError("--ips_clip must be >= 0 (0: no clip), got %s" % args.ips_clip)
+    if getattr(args, "ips_norm", 0) not in (0, 1):
+        raise ValueError("--ips_norm must be 0 or 1, got %s" % args.ips_norm)
+
+
+class IPSBPRMF(BPRMF):
+    """BPR-MF trained with inverse propensity scoring: IPS, IPS-C (--ips_clip C) and IPS-CN (--ips_clip C --ips_norm 1).
+    Fetchables, tables, evaluation and checkpoint are those of BPRMF -- the two differ only in how they were trained; a step is
+    pda_ips_adam_step_f32.  data_config["ips_item_counts"] (or set_item_counts): the train interactions per item the weights are built from;
+    a model that is only restored and evaluated needs none."""
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_ips(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.ips_clip = float(getattr(args, "ips_clip", 0.0))
+        self.ips_norm = int(getattr(args, "ips_norm", 0))
+        self.ips = None
+        self._wsum = None
+        if data_config.get("ips_item_counts") is not None:
+            self.set_item_counts(data_config["ips_item_counts"])
+
+    def set_item_counts(self, counts):
+        if len(counts) != self.n_items:
+            raise ValueError("ips_item_counts holds one number per item (%d), got %d" % (self.n_items, len(counts)))
+        self.ips = ops.IpsWeights.from_counts(counts, self.ips_clip, self.device)
+
+    def train_step(self, users, pos, neg, pos_pop=None, neg_pop=None, plan=None) -> torch.Tensor:
+        """One IPS step; returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this step, as BPRMF.train_step does."""
+        if self.ips is None:
+            raise ValueError("IPSBPRMF needs the train interactions per item before it trains (data_config['ips_item_counts'] or set_item_counts)")
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._opt_state()
+        if "tagU" not in st:
+            st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
+        if self.ips_norm and self._wsum is None:
+            self._wsum = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._t += 1
+        ops.ips_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, neg, self.ips.ipw,
+                          wsum=self._wsum if self.ips_norm else None, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                          lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+        return self._loss
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd.update(ips_clip=self.ips_clip, ips_norm=self.ips_norm)
+        return sd

@@ -2182,3 +2182,126 @@ def dice_sample_into(out, train_indptr, train_indices, dp: DicePop, *, margin_de
                                           ptr(dp.pop), ptr(margin_dev), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(out[1]), ptr(out[2]),
                                           ptr(out[3]), stream_ptr()), "pda_dice_sample_dev")
     return out
+
+
+# ---- IPS, IPS-C, IPS-CN (include/pda_hip_ips.h) ---------------------------------------------------------------------------------------------
+IPS_EMBED_SIZES = (32, 64, 128, 256)
+
+
+class IpsWeights:
+    """The inverse propensity weight of every item as a positive, built once per data set on the host: with n_i the train interactions of item i,
+    p_i = max(n_i, 1) / max_j n_j and w_i = 1 / p_i in float64, w_i = min(w_i, clip) when clip > 0, then cast: ipw float32 [n_items] on the
+    device of train_indices.  counts: the int64 numpy vector n_i."""
+
+    def __init__(self, train_indices: torch.Tensor, n_items: int, clip: float = 0.0):
+        import numpy as np
+        idx = train_indices.detach().cpu().numpy().astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_items):
+            raise ValueError("a train item id lies outside the catalogue")
+        self._build(np.bincount(idx, minlength=int(n_items)), clip, train_indices.device)
+
+    @classmethod
+    def from_counts(cls, counts, clip: float = 0.0, device="cpu"):
+        """The same from the vector of train interactions per item."""
+        import numpy as np
+        counts = np.asarray(counts)
+        if counts.ndim != 1 or counts.size == 0 or (counts < 0).any():
+            raise ValueError("counts: one non-negative number of train interactions per item")
+        self = cls.__new__(cls)
+        self._build(counts.astype(np.int64), clip, device)
+        return self
+
+    def _build(self, counts, clip, device):
+        import numpy as np
+        clip = float(clip)
+        if not clip >= 0.0:
+            raise ValueError("--ips_clip must be >= 0 (0: no clip)")
+        n = np.maximum(counts, 1).astype(np.float64)
+        w = 1.0 / (n / float(max(int(counts.max()) if counts.size else 1, 1)))
+        if clip > 0.0:
+            w = np.minimum(w, clip)
+        self.n_items, self.clip, self.counts = int(counts.size), clip, counts
+        self.ipw = torch.from_numpy(w.astype(np.float32)).to(device)
+
+
+def _ips_check(U, I, users, pos, neg, ipw, tagU, tagI, wsum, loss_acc, check_ids: bool):
+    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
+    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1]:
+        raise ValueError("IPS tables: U [n_users, d] and I [n_items, d]")
+    d = U.shape[1]
+    if d not in IPS_EMBED_SIZES:
+        raise ValueError(f"IPS: the embedding width d must be one of {IPS_EMBED_SIZES}, got {d}")
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    B = users.numel()
+    if B < 1 or pos.numel() != B or neg.numel() != B:
+        raise ValueError("users/pos/neg must have the same, non-zero length")
+    if _need(ipw, torch.float32, "ipw").numel() != I.shape[0]:
+        raise ValueError("ipw holds one float32 per item")
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(wsum, torch.float32, "wsum", optional=True) is not None and wsum.numel() < 1:
+        raise ValueError("wsum holds one float32")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("IPS loss_acc holds three float32")
+    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
+        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
+        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
+            raise ValueError("IPS batch: a user or item id lies outside the tables")
+    return d, B
+
+
+def _ips_flags(grouped: bool, users_distinct: bool) -> int:
+    return (0 if grouped else UPD_ANY_ORDER) | (UPD_USERS_DISTINCT if users_distinct else 0)
+
+
+def ips_weight_sum(ipw, users, pos, neg, n_users: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_ips_weight_sum -> float32 [1] on the device: the sum of ipw[pos] over the batch's valid triplets (one workgroup, a fixed order)."""
+    ipw = _need(ipw, torch.float32, "ipw")
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    B = users.numel()
+    if B < 1 or pos.numel() != B or neg.numel() != B:
+        raise ValueError("users/pos/neg must have the same, non-zero length")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=ipw.device)
+    if _need(out, torch.float32, "out").numel() < 1:
+        raise ValueError("out holds one float32")
+    check(_lib.load().pda_ips_weight_sum(ptr(ipw), int(n_users), ipw.numel(), ptr(users), ptr(pos), ptr(neg), B, ptr(out), stream_ptr()),
+          "pda_ips_weight_sum")
+    return out
+
+
+def ips_grads(U, I, users, pos, neg, ipw, gU, gI, tagU, tagI, *, wsum: Optional[torch.Tensor] = None, regs: float, reg_div: float, step: int,
+              grouped: bool = False, users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """[pda_ips_weight_sum +] pda_ips_step_f32: the batch's gradient summed into gU / gI (rows tagged `step`), no update.  wsum float32 [1]: the
+    self-normalised form (IPS-CN) -- the batch's weight sum is written there first and the triplets are scaled by w_t / wsum; None: by w_t / B.
+    loss_acc float32 [3] += (loss, mf_loss, reg_loss)."""
+    d, B = _ips_check(U, I, users, pos, neg, ipw, tagU, tagI, wsum, loss_acc, check_ids)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    lib = _lib.load()
+    if wsum is not None:
+        check(lib.pda_ips_weight_sum(ptr(ipw), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), B, ptr(wsum), stream_ptr()),
+              "pda_ips_weight_sum")
+    check(lib.pda_ips_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(ipw), ptr(wsum), B, d, float(regs),
+                               float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step), _ips_flags(grouped, users_distinct), ptr(loss_acc),
+                               stream_ptr()), "pda_ips_step_f32")
+
+
+def ips_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, neg, ipw, *, wsum: Optional[torch.Tensor] = None, regs: float,
+                  reg_div: float, step: int, lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False,
+                  users_distinct: bool = False, cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None,
+                  check_ids: bool = False):
+    """pda_ips_adam_step_f32: one IPS train step ([the weight sum,] the weighted gradients, TF-1.14 dense-decay Adam over both tables) in two or
+    three launches; graph-capturable.  The arguments of adam_step with ipw float32 [n_items] in place of the popularities; wsum float32 [1]
+    (workspace) selects the self-normalised form."""
+    d, B = _ips_check(U, I, users, pos, neg, ipw, tagU, tagI, wsum, loss_acc, check_ids)
+    for t in (mU, vU, gU, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_ips_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI),
+                                            I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(ipw), ptr(wsum), B, d, float(regs), float(reg_div),
+                                            int(step), float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy),
+                                            ptr(loss_acc), stream_ptr()), "pda_ips_adam_step_f32")
+    mark_modified(U, I)

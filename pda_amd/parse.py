@@ -79,6 +79,8 @@ _EXTENSION_FLAGS = [
     ("xq_candidates", int, 1000, "xQuAD: candidates per user the re-ranking selects from, max(Ks) .. 1024 (above 54 they come from the deep path)"),
     ("xq_head_share", float, 0.8, "xQuAD: the short head is the most popular items that hold this share of the train interactions, strictly inside 0 .. 1"),
     ("xq_variant", str, "smooth", "xQuAD: smooth | binary"),
+    ("ips_clip", float, 0.0, "IPS (--train ips): clip the inverse propensity weights at this value (IPS-C); 0: no clip"),
+    ("ips_norm", int, 0, "IPS: 1 divides a batch's weighted loss by the sum of its weights instead of the batch size (IPS-CN, with --ips_clip); 0 | 1"),
     ("dice_int_weight", float, 0.1, "DICE (--train dice): weight of the interest loss L_int"),
     ("dice_con_weight", float, 0.1, "DICE: weight of the conformity loss L_con"),
     ("dice_dis_pen", float, 0.01, "DICE: weight of the discrepancy term (the loss takes -dice_dis_pen * L_dis)"),

@@ -28,7 +28,7 @@ import torch
 
 from . import ops
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import BPRMF, DICE, BPRMFTempPop, ConditionalBPRMF, Fetch, check_dice
+from .model_api import BPRMF, DICE, IPSBPRMF, BPRMFTempPop, ConditionalBPRMF, Fetch, check_dice, check_ips, ips_item_counts
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -132,6 +132,11 @@ class DatasetApi_Model:
             self.input_type = "without_pop"
             print("dataset api without pop")
             self.Recommender = DICE(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train == "ips":
+            # IPS / IPS-C / IPS-CN: a BPRMF whose step weighs every triplet by the inverse propensity of its positive
+            self.input_type = "without_pop"
+            print("dataset api without pop")
+            self.Recommender = IPSBPRMF(args, data_config, use_dataset_api=True, device=self.device)
         else:
             raise NotImplementedError("not implement this model: " + args.train)   # :590
         # the device sampler draws a batch's users without replacement (like the reference, :380-381): the fused SGD step may
@@ -443,6 +448,11 @@ def main(argv=None):
         check_dice(args)
         if args.test not in ("normal", "dice"):
             raise NotImplementedError("--train dice goes with --test normal (DICE and DICE-A) or --test dice, not --test " + str(args.test))
+    if args.train == "ips":
+        check_ips(args)
+        if args.test not in ("normal", "ips"):
+            raise NotImplementedError("--train ips goes with --test normal (the raw head and the gamma search of a BPRMF) or --test ips, not --test "
+                                      + str(args.test))
     random.seed(2020)                      # :934-936
     np.random.seed(2020)
     torch.manual_seed(2021)
@@ -462,9 +472,12 @@ def main(argv=None):
     linear_predict_popularity = np.power(linear_predict_popularity, popularity_exp)
 
     with_pop = False
-    if args.model == "mf" and args.train in ("normal", "dice"):                  # :963-970 (DICE is evaluated like a BPRMF: --test normal = DICE-A)
+    if args.model == "mf" and args.train in ("normal", "dice", "ips"):           # :963-970 (DICE and IPS are evaluated like a BPRMF: --test normal)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
-        print("normal MF... " if args.train == "normal" else "-------    running DICE  ----------------")
+        print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
+        if args.train == "ips":
+            args.saveID += "ips"
+            config["ips_item_counts"] = ips_item_counts(data.train_user_list, data.n_items)
         last_stage_popualarity_ori = pop_item_all[:, -2]
         linear_predict_popularity_ori = pop_item_all[:, -2] + 0.5 * (pop_item_all[:, -2] - pop_item_all[:, -3])
         # the reference masks with the already-powered array (a quirk): kept
@@ -588,7 +601,7 @@ def main(argv=None):
             print("||------------PDA/PDGA injecting linear predicted popularity testing : time: ", int(time() - ttt1))
             _print_result(ret2)
             ret = ret1
-        elif args.test in ("temp_pop", "dice"):                                  # :1192-1200 (--test dice: the main_branch head alone)
+        elif args.test in ("temp_pop", "dice", "ips"):                           # :1192-1200 (--test dice / ips: the main_branch head alone)
             print(perf_str)
             ttt1 = time()
             evaluation_model.set_testing_popularity(None)
@@ -686,10 +699,11 @@ def main(argv=None):
             print("|||---BPRMF-A with injecting %s:" % name)
             _print_result(r)
         print("----------------------------")
-    elif args.test in ("temp_pop", "dice"):                                      # :1310-1314
+    elif args.test in ("temp_pop", "dice", "ips"):                               # :1310-1314
         evaluation_model.set_testing_popularity(None)
         ret = evaluation_model.eval(model, sess, rec_type="main_branch")
-        print("---- result with last pop bias for temp_pop model:" if args.test == "temp_pop" else "---- DICE result (interest + conformity):")
+        print({"temp_pop": "---- result with last pop bias for temp_pop model:", "dice": "---- DICE result (interest + conformity):"}
+              .get(args.test, "---- IPS result:"))
         _print_result(ret)
     print("training and testing end!!!!")
     print("|||  ------------------------ best performance for model selected by PD/PDG/BPRMF ------------------- |||")

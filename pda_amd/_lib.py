@@ -1,5 +1,5 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
-pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h and pda_hip_ips.h).
+pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h and pda_hip_macr.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -207,6 +207,14 @@ IPS_SIGNATURES = {
     "pda_ips_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 5 + [_i, _i, _f, _f, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_macr.h (MACR: `--train macr`)
+MACR_SIGNATURES = {
+    "pda_macr_step_f32": (_i, [_vp] * 4 + [_sz, _sz] + [_vp] * 3 + [_i, _i, _f, _f, _f, _f] + [_vp] * 5 + [_i, _i, _vp, _vp]),
+    "pda_macr_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 8 + [_i, _i, _f, _f, _f, _f, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
+    "pda_macr_item_prep_f32": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pda_macr_item_bias_f32": (_i, [_vp, _f, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -226,7 +234,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
-            list(IPS_SIGNATURES.items()):
+            list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -5,6 +5,7 @@
     BPRMF              plain BPR-MF        MF/model_api.py:419-757   (only :419-471, :521-536, :695-706 are live)
     DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
     IPSBPRMF           IPS / IPS-C / IPS-CN (no reference code: DESIGN.md 5g)  a BPRMF trained with inverse propensity weights; Adam sweep only
+    MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
 trainer passes to `sess.run`.  Here they are light handle objects understood by `pda_amd.train_new_api.Session`,
@@ -714,3 +715,160 @@ class IPSBPRMF(BPRMF):
         sd = super().state_dict()
         sd.update(ips_clip=self.ips_clip, ips_norm=self.ips_norm)
         return sd
+
+
+MACR_EMBED_SIZES = ops.MACR_EVAL_EMBED_SIZES   # --embed_size of a MACR model: what its lists (the bias head) can rank
+
+
+def macr_c_grid(args):
+    """The values of c an evaluation tries after c = 0: np.linspace(--start, --end, --step) with --check_c 1, the single --c with --check_c 0."""
+    import numpy as np
+    if int(getattr(args, "check_c", 1)):
+        return [float(c) for c in np.linspace(float(args.start), float(args.end), int(args.step))]
+    return [float(args.c)]
+
+
+def check_macr(args):
+    """--train macr: refuse, before anything is built, what MACR has no kernel for.  Every message names its flag."""
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train macr sums its gradients with float atomics (no planned gradient)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train macr runs fp32 tables only" % args.table_dtype)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train macr runs the reference's dense-decay Adam only (--optimizer adam)" % args.optimizer)
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("--adam_sweep %s: --train macr runs the dense Adam sweep only (auto | sweep)" % getattr(args, "adam_sweep", "auto"))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train macr trains and evaluates on one GPU" % args.gpus)
+    k = getattr(args, "topk_max", None)
+    if k is not None and int(k) > ops.TOPK_K_V4:
+        raise NotImplementedError("--topk_max %d: MACR ranks by the bias head (u . s_i I_i - c s_i), which has no lists deeper than %d"
+                                  % (int(k), ops.TOPK_K_V4))
+    if int(args.embed_size) not in MACR_EMBED_SIZES:
+        raise NotImplementedError("--embed_size %s: --train macr ranks by the bias-head score kernels, which take one of %s"
+                                  % (args.embed_size, MACR_EMBED_SIZES))
+    for flag in ("alpha", "beta", "c", "start", "end"):
+        if not math.isfinite(float(getattr(args, flag, 0.0))):
+            raise ValueError("--%s must be finite, got %s" % (flag, getattr(args, flag)))
+    if int(getattr(args, "check_c", 1)) not in (0, 1):
+        raise ValueError("--check_c must be 0 or 1, got %s" % args.check_c)
+    if int(getattr(args, "check_c", 1)) and int(getattr(args, "step", 20)) < 1:
+        raise ValueError("--step must be >= 1 (the number of values of c between --start and --end), got %s" % args.step)
+
+
+class MACRBPRMF(BPRMF):
+    """MACR on BPR-MF (Wei et al., KDD'21): the three-branch loss of MF/model_api.py:613-651 and its counterfactual inference.
+    Fetchables: those of BPRMF.  weights: user_embedding, item_embedding, and the two branch vectors w_item / w_user [d, 1] (the reference's
+    `item_branch` / `user_branch`), Xavier-uniform like every [fan_in, fan_out] table: U(-l, l), l = sqrt(6 / (d + 1)).  A step is
+    pda_macr_adam_step_f32 with --alpha / --beta as the loss weights.  c: the constant of (y - c) s_i s_u the lists are ranked with (update_c);
+    best_c: the value the last evaluation chose, kept in the checkpoint."""
+    LOSS_TERMS = ops.MACR_LOSS_TERMS       # a step's loss row: loss, L_O, L_I, L_U, reg
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_macr(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.alpha, self.beta = float(args.alpha), float(args.beta)          # self.alpha = args.alpha in the reference's class
+        self.c = self.best_c = 0.0
+        self._macr = None
+        self._prep = None                    # (MacrItemPrep, item table version, w_item version)
+        self._loss_ring = torch.zeros((16, self.LOSS_TERMS), dtype=torch.float32, device=self.device)
+        self._loss = self._loss_ring[0]
+        self.epoch_terms = None              # float64 [5]: the sums of the last finished epoch's loss rows
+
+    def init_weights(self, gen):
+        w = super().init_weights(gen)
+        w["w_item"] = xavier_uniform_(torch.empty(self.emb_dim, 1, device=self.device), gen)
+        w["w_user"] = xavier_uniform_(torch.empty(self.emb_dim, 1, device=self.device), gen)
+        return w
+
+    def _macr_state(self):
+        if self._macr is None:
+            self._macr = ops.MacrState(self.weights["user_embedding"], self.weights["item_embedding"])
+        return self._macr
+
+    def update_c(self, c):
+        """MF/model_api.py:744: the constant the next lists are ranked with."""
+        c = float(c)
+        if not math.isfinite(c):
+            raise ValueError("c must be finite, got %s" % c)
+        self.c = c
+
+    def item_prep(self):
+        """sig and J = fl(sig_i I_i) of the current weights (ops.macr_item_prep), rebuilt when a step or a checkpoint moved them: once per
+        evaluation, whatever the number of user blocks and of values of c."""
+        I, w = self.weights["item_embedding"], self.weights["w_item"]
+        if self._prep is None or self._prep[1:] != (I._version, w._version):
+            prep = ops.macr_item_prep(I, w, self._prep[0] if self._prep is not None else None)
+            self._prep = (prep, I._version, w._version)
+        return self._prep[0]
+
+    @staticmethod
+    def trainer_terms(row):
+        """(loss, mf_loss, reg_loss) of a loss row or of a sum of rows: mf_loss = L_O + alpha L_I + beta L_U, everything except reg_loss."""
+        return torch.stack([row[0], row[0] - row[4], row[4]])
+
+    def start_loss_rows(self, n_steps: int):
+        self._loss_rows = torch.zeros((max(1, int(n_steps)), self.LOSS_TERMS), dtype=torch.float32, device=self.device)
+        self._loss_row_i = 0
+
+    def finish_loss_rows(self) -> torch.Tensor:
+        """The trainer's (loss, mf_loss, reg_loss) sums; all five terms of the epoch stay in epoch_terms."""
+        rows, n = self._loss_rows, self._loss_row_i
+        self._loss_rows = None
+        self.epoch_terms = rows[:n].double().sum(0)
+        return self.trainer_terms(self.epoch_terms)
+
+    def train_step(self, users, pos, neg, pos_pop=None, neg_pop=None, plan=None) -> torch.Tensor:
+        """One MACR step; returns the float32 [5] device tensor (loss, L_O, L_I, L_U, reg_loss) of this step (trainer_terms: the trainer's three)."""
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._macr_state()
+        w = self.weights
+        self._t += 1
+        ops.macr_adam_step(w["user_embedding"], w["item_embedding"], w["w_item"], w["w_user"], users, pos, neg, st, alpha=self.alpha, beta=self.beta,
+                           regs=self.decay, reg_div=self.batch_size, step=self._t, lr_t=ops.adam_lr_t(self.lr, self._t),
+                           users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+        return self._loss
+
+    CKPT_MOMENTS = ("mU", "vU", "mI", "vI", "mW", "vW")
+
+    def state_dict(self):
+        w = self.weights
+        sd = {"format": self.CKPT_FORMAT, "model": "macr", "embed_size": self.emb_dim, "n_users": self.n_users, "n_items": self.n_items,
+              "optimizer": self.optimizer, "table_dtype": self.table_dtype, "user_embedding": w["user_embedding"],
+              "item_embedding": w["item_embedding"], "w_item": w["w_item"], "w_user": w["w_user"], "adam_t": self._t, "macr_alpha": self.alpha,
+              "macr_beta": self.beta, "macr_c": self.best_c}
+        if self._macr is not None:
+            sd.update({k: getattr(self._macr, k) for k in self.CKPT_MOMENTS})
+        return sd
+
+    def load_state_dict(self, sd):
+        if not isinstance(sd, dict) or "user_embedding" not in sd:
+            raise ValueError("not a pda_amd checkpoint (a tf.train.Saver checkpoint of the reference cannot be loaded)")
+        if sd.get("format") != self.CKPT_FORMAT:
+            raise ValueError("checkpoint format %r, MACRBPRMF reads %s" % (sd.get("format"), self.CKPT_FORMAT))
+        if sd.get("model", "mf") != "macr":
+            raise ValueError("checkpoint of a %s model cannot be loaded into MACRBPRMF (no branch vectors)" % sd.get("model", "mf"))
+        for key, mine in (("embed_size", self.emb_dim), ("n_users", self.n_users), ("n_items", self.n_items)):
+            if int(sd[key]) != int(mine):
+                raise ValueError("checkpoint %s = %s, model has %s" % (key, sd[key], mine))
+        names = ("user_embedding", "item_embedding", "w_item", "w_user")
+        for k in names:
+            if tuple(sd[k].shape) != tuple(self.weights[k].shape):
+                raise ValueError("checkpoint table %s does not have the model's shape" % k)
+        for k in names:
+            self.weights[k].copy_(sd[k])
+        self._t = int(sd.get("adam_t", 0))
+        self.c = self.best_c = float(sd.get("macr_c", 0.0))
+        self._macr = None                     # (fresh tags and zero gradient accumulators: as after DICE's restore)
+        if "mU" in sd:
+            st = self._macr_state()
+            for k in self.CKPT_MOMENTS:
+                getattr(st, k).copy_(sd[k])

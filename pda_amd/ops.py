@@ -2305,3 +2305,140 @@ def ips_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, neg, ipw
                                             int(step), float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy),
                                             ptr(loss_acc), stream_ptr()), "pda_ips_adam_step_f32")
     mark_modified(U, I)
+
+
+# ---- MACR (include/pda_hip_macr.h) ----------------------------------------------------------------------------------------------------------
+MACR_EMBED_SIZES = (32, 64, 128, 256)         # the step and the item prep
+MACR_EVAL_EMBED_SIZES = (64, 128, 256)        # the lists: the bias head of include/pda_hip_temp_pop.h
+MACR_LOSS_TERMS = 5                           # a step's loss row: loss, L_O, L_I, L_U, reg
+
+
+class MacrState:
+    """What a MACR step writes besides the parameters: the Adam moments of both tables and of the two branch vectors (mW / vW float32 [2, d]:
+    w_item, w_user), the dense gradient accumulators gU / gI / gW and the per-row step tags."""
+
+    def __init__(self, U, I):
+        z = torch.zeros_like
+        self.mU, self.vU, self.gU, self.mI, self.vI, self.gI = z(U), z(U), z(U), z(I), z(I), z(I)
+        self.tagU, self.tagI = adam_row_tags(U.shape[0], I.shape[0], U.device)
+        self.mW, self.vW, self.gW = (torch.zeros((2, U.shape[1]), dtype=torch.float32, device=U.device) for _ in range(3))
+
+
+def _macr_check(U, I, w_item, w_user, users, pos, neg, st, loss_acc, check_ids: bool):
+    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
+    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1]:
+        raise ValueError("MACR tables: U [n_users, d] and I [n_items, d]")
+    d = U.shape[1]
+    if d not in MACR_EMBED_SIZES:
+        raise ValueError(f"MACR: the embedding width d must be one of {MACR_EMBED_SIZES}, got {d}")
+    if _need(w_item, torch.float32, "w_item").numel() != d or _need(w_user, torch.float32, "w_user").numel() != d:
+        raise ValueError("w_item / w_user hold d float32 each")
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    B = users.numel()
+    if B < 1 or pos.numel() != B or neg.numel() != B:
+        raise ValueError("users/pos/neg must have the same, non-zero length")
+    if not isinstance(st, MacrState) or st.gU.shape != U.shape or st.gI.shape != I.shape:
+        raise ValueError("st: the MacrState of these tables")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < MACR_LOSS_TERMS:
+        raise ValueError("MACR loss_acc holds five float32")
+    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
+        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
+        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
+            raise ValueError("MACR batch: a user or item id lies outside the tables")
+    return d, B
+
+
+def macr_grads(U, I, w_item, w_user, users, pos, neg, st: MacrState, *, alpha: float, beta: float, regs: float, reg_div: float, step: int,
+               grouped: bool = False, users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_macr_step_f32: the batch's gradients summed into st.gU / st.gI (rows tagged `step`) and st.gW (row 0: w_item, row 1: w_user), no
+    update.  loss_acc float32 [5] += (loss, L_O, L_I, L_U, reg)."""
+    d, B = _macr_check(U, I, w_item, w_user, users, pos, neg, st, loss_acc, check_ids)
+    check(_lib.load().pda_macr_step_f32(ptr(U), ptr(I), ptr(w_item), ptr(w_user), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), B, d,
+                                        float(alpha), float(beta), float(regs), float(reg_div), ptr(st.gU), ptr(st.gI), ptr(st.gW), ptr(st.tagU),
+                                        ptr(st.tagI), int(step), (0 if grouped else UPD_ANY_ORDER) | (UPD_USERS_DISTINCT if users_distinct else 0),
+                                        ptr(loss_acc), stream_ptr()), "pda_macr_step_f32")
+
+
+def macr_adam_step(U, I, w_item, w_user, users, pos, neg, st: MacrState, *, alpha: float, beta: float, regs: float, reg_div: float, step: int,
+                   lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False, users_distinct: bool = False,
+                   cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_macr_adam_step_f32: one MACR train step (the gradients, TF-1.14 dense-decay Adam over both tables, the same Adam over the two branch
+    vectors) in three launches; graph-capturable."""
+    d, B = _macr_check(U, I, w_item, w_user, users, pos, neg, st, loss_acc, check_ids)
+    check(_lib.load().pda_macr_adam_step_f32(ptr(U), ptr(st.mU), ptr(st.vU), ptr(st.gU), ptr(st.tagU), U.shape[0], ptr(I), ptr(st.mI), ptr(st.vI),
+                                             ptr(st.gI), ptr(st.tagI), I.shape[0], ptr(w_item), ptr(w_user), ptr(st.mW), ptr(st.vW), ptr(st.gW),
+                                             ptr(users), ptr(pos), ptr(neg), B, d, float(alpha), float(beta), float(regs), float(reg_div), int(step),
+                                             float(lr_t), beta1, beta2, eps, (0 if grouped else UPD_ANY_ORDER) | (UPD_USERS_DISTINCT if users_distinct else 0),
+                                             int(cache_policy), ptr(loss_acc), stream_ptr()), "pda_macr_adam_step_f32")
+    mark_modified(U, I, w_item, w_user)
+
+
+class MacrItemPrep:
+    """What MACR's lists read in place of the item table, built once per evaluation: sig float32 [n_items] = sigmoid(I_i . w_item),
+    J float32 [n_items, d] = fl(sig_i I_i), and beta float32 [n_items], the bias of the value of c asked for last."""
+
+    def __init__(self, n_items: int, d: int, device):
+        self.sig = torch.empty(n_items, dtype=torch.float32, device=device)
+        self.J = torch.empty((n_items, d), dtype=torch.float32, device=device)
+        self.beta = torch.empty(n_items, dtype=torch.float32, device=device)
+        self.c = None
+
+    def bias(self, c: float) -> torch.Tensor:
+        if self.c is None or float(c) != self.c:
+            macr_item_bias(self.sig, c, self.beta)
+            self.c = float(c)
+        return self.beta
+
+
+def macr_item_prep(I, w_item, out: Optional[MacrItemPrep] = None) -> MacrItemPrep:
+    """pda_macr_item_prep_f32 -> MacrItemPrep (sig, J): one launch over the item table, the same bits run after run."""
+    I, w_item = _need(I, torch.float32, "I"), _need(w_item, torch.float32, "w_item")
+    if I.dim() != 2 or I.shape[1] not in MACR_EMBED_SIZES or w_item.numel() != I.shape[1]:
+        raise ValueError(f"MACR item prep: I [n_items, d], d one of {MACR_EMBED_SIZES}, and w_item of d float32")
+    n, d = I.shape
+    if out is None:
+        out = MacrItemPrep(n, d, I.device)
+    if out.J.shape != I.shape or out.J.device != I.device:
+        raise ValueError("out: the MacrItemPrep of a table of this shape")
+    check(_lib.load().pda_macr_item_prep_f32(ptr(I), ptr(w_item), n, d, ptr(out.sig), ptr(out.J), stream_ptr()), "pda_macr_item_prep_f32")
+    out.c = None
+    mark_modified(out.J, out.sig)
+    return out
+
+
+def macr_item_bias(sig, c: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_macr_item_bias_f32 -> beta float32 [n]: beta_i = fl(-c sig_i)."""
+    sig = _need(sig, torch.float32, "sig")
+    if not math.isfinite(float(c)):
+        raise ValueError(f"c must be finite, got {c}")
+    if out is None:
+        out = torch.empty_like(sig)
+    if _need(out, torch.float32, "beta").numel() != sig.numel():
+        raise ValueError("beta holds one float32 per item")
+    check(_lib.load().pda_macr_item_bias_f32(ptr(sig), float(c), ptr(out), sig.numel(), stream_ptr()), "pda_macr_item_bias_f32")
+    mark_modified(out)
+    return out
+
+
+def check_macr_lists(d: int, K: int):
+    """MACR's lists come from the bias head: d in {64, 128, 256} and K <= 54, like BPRMF(t)-pop's."""
+    if int(d) not in MACR_EVAL_EMBED_SIZES:
+        raise ValueError(f"MACR lists: the embedding width must be one of {MACR_EVAL_EMBED_SIZES} (the bias-head score kernels), got {d}")
+    if not 1 <= int(K) <= TOPK_K_V4:
+        raise ValueError(f"MACR lists: K must lie in 1 .. {TOPK_K_V4} (the bias head has no deep lists), got {K}")
+
+
+def recommend_topk_macr(U, I, w_item, users, c: float, K=50, hist: Optional[HistoryCSR] = None, prep: Optional[MacrItemPrep] = None,
+                        stats: Optional[dict] = None):
+    """MACR's counterfactual ranking by (y_ui - c) s_i -> (int32 [Bu, K] item ids, float32 [Bu, K] values): the bias head on J = fl(s_i I_i)
+    with alpha = 1 and beta_i = fl(-c s_i), so the values are fl(chain(u . J_i) + beta_i).  prep: macr_item_prep(I, w_item) of the evaluation
+    (built here when missing); every value of c costs one bias launch and one sweep."""
+    U = _need(U, torch.float32, "U")
+    users = _need(users, torch.int32, "users")
+    check_macr_lists(U.shape[1], K)
+    if prep is None:
+        prep = macr_item_prep(I, w_item)
+    if prep.J.shape[1] != U.shape[1]:
+        raise ValueError("U and the item prep share the embed dim")
+    ones = torch.ones(users.numel(), dtype=torch.float32, device=U.device)
+    return recommend_topk_bias(U, prep.J, users, ones, prep.bias(c), K, hist, stats=stats)

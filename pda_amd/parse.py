@@ -17,8 +17,8 @@ _REFERENCE_FLAGS = [
     ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA)"),
     ("valid_set", None, "test", "test | valid"),
     ("save_dir", None, "/data/zyang/save_model/", "checkpoint root"),
-    ("alpha", float, 1e-3, "(unused; appears in the checkpoint directory name)"),
-    ("beta", float, 1e-3, "(unused)"),
+    ("alpha", float, 1e-3, "MACR (--train macr): weight of the item-branch loss L_I; otherwise unused (appears in the checkpoint directory name)"),
+    ("beta", float, 1e-3, "MACR: weight of the user-branch loss L_U; otherwise unused"),
     ("pc_alpha", float, 0.1, "BPR-PC (python -m pda_amd.bpr_pc): weight alpha of the popularity compensation"),
     ("pc_beta", float, 0.1, "BPR-PC: beta of the compensation C = (beta s + 1 - beta) / pop"),
     ("exp_init_values", float, 0.1, "(unused)"),
@@ -35,7 +35,7 @@ _REFERENCE_FLAGS = [
     ("epochs", None, "[]", "(unused)"),
     ("regs", float, 1e-5, "L2 coefficient"),
     ("fregs", float, 1e-5, "(unused)"),
-    ("c", float, 10.0, "(unused)"),
+    ("c", float, 10.0, "MACR: the counterfactual constant c of (y - c) s_i s_u when --check_c 0; otherwise unused"),
     ("train_c", str, "val", "(unused)"),
     ("lr", float, 1e-3, "learning rate"),
     ("wd", float, 1e-5, "(overwritten by --regs, MF/train_new_api.py:1020)"),
@@ -47,7 +47,7 @@ _REFERENCE_FLAGS = [
     ("pop_used", int, -2, "(unused)"),
     ("cuda", str, "1", "visible GPU id (HIP_VISIBLE_DEVICES)"),
     ("pretrain", int, 0, "only 0 is implemented"),
-    ("check_c", int, 1, "(unused)"),
+    ("check_c", int, 1, "MACR: 1 searches c over linspace(--start, --end, --step) at every evaluation, 0 uses --c; otherwise unused"),
     ("log_interval", int, 10, "evaluate every this many epochs"),
     ("pop_wd", float, 0.0, "(unused)"),
     ("base", float, -1.0, "(unused)"),
@@ -60,9 +60,9 @@ _REFERENCE_FLAGS = [
     ("top_ratio", float, 0.1, "(unused)"),
     ("lam", float, 1.0, "(unused)"),
     ("check_epoch", None, "all", "(unused)"),
-    ("start", float, -1.0, "(unused)"),
-    ("end", float, 1.0, "(unused)"),
-    ("step", int, 20, "(unused)"),
+    ("start", float, -1.0, "MACR: first value of the search over c; otherwise unused"),
+    ("end", float, 1.0, "MACR: last value of the search over c; otherwise unused"),
+    ("step", int, 20, "MACR: number of values of the search over c; otherwise unused"),
     ("out", int, 0, "(unused)"),
 ]
 

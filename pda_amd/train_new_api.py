@@ -28,7 +28,8 @@ import torch
 
 from . import ops
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import BPRMF, DICE, IPSBPRMF, BPRMFTempPop, ConditionalBPRMF, Fetch, check_dice, check_ips, ips_item_counts
+from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, BPRMFTempPop, ConditionalBPRMF, Fetch, check_dice, check_ips, check_macr, ips_item_counts,
+                        macr_c_grid)
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -60,6 +61,7 @@ class Session:
         if not any(f.name == "opt" for f in fetches):
             raise NotImplementedError("fetching %s without the optimiser op" % [f.name for f in fetches])
         b = self.model.next_batch()
+        self._rec = rec
         return rec.train_step(*b, plan=self.model.batch_plan)
 
     def run_async(self, fetches):
@@ -70,7 +72,8 @@ class Session:
             return None
         if isinstance(fetches, Fetch):
             fetches = [fetches]
-        loss = self._step(fetches).tolist()
+        loss = self._step(fetches)
+        loss = (self._rec.trainer_terms(loss) if hasattr(self._rec, "trainer_terms") else loss).tolist()      # (MACR: a row of five terms)
         pick = {"opt": None, "loss": loss[0], "mf_loss": loss[1], "reg_loss": loss[2]}
         return [pick[f.name] for f in fetches]
 
@@ -137,6 +140,11 @@ class DatasetApi_Model:
             self.input_type = "without_pop"
             print("dataset api without pop")
             self.Recommender = IPSBPRMF(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train == "macr":
+            # MACR: the tables of a BPRMF plus two branch vectors; lists ranked by (y - c) s_i through the bias head
+            self.input_type = "without_pop"
+            print("dataset api without pop")
+            self.Recommender = MACRBPRMF(args, data_config, use_dataset_api=True, device=self.device)
         else:
             raise NotImplementedError("not implement this model: " + args.train)   # :590
         # the device sampler draws a batch's users without replacement (like the reference, :380-381): the fused SGD step may
@@ -237,6 +245,10 @@ class DatasetApi_Model:
         if self.input_type == "with_temp":
             if rec_type != "main_branch":
                 raise NotImplementedError("temp_pop evaluates the main_branch head only (--test temp_pop)")
+        elif rec_type == "macr":
+            if not isinstance(self.Recommender, MACRBPRMF):
+                raise NotImplementedError("the macr head needs a MACR model (--train macr)")
+            head, pos_pop = None, None
         elif rec_type == "main_branch":
             head, pos_pop = ops.HEAD_RAW, None
         elif rec_type in ("main_with_pop", "condition"):
@@ -246,7 +258,7 @@ class DatasetApi_Model:
             if pos_pop is None:
                 raise ValueError("rec_type %s needs pos_pop" % rec_type)
         else:
-            raise NotImplementedError("we have only implement recommendation method: main main+pop condition")   # :639
+            raise NotImplementedError("we have only implement recommendation method: main main+pop condition macr")   # :639
         users = batch_users if torch.is_tensor(batch_users) else torch.as_tensor(np.asarray(batch_users, dtype=np.int32), device=self.device)
         hist = mask
         if mask is not None and not isinstance(mask, ops.HistoryCSR):
@@ -263,6 +275,16 @@ class DatasetApi_Model:
                 beta = beta.index_select(0, _sel).contiguous()
             alpha = self.temp_pop_alpha(users, eval_pos, eval_users)
             return ops.recommend_topk_bias(self.Recommender.score_tables()[0], I, users, alpha, beta, K, hist)
+        if rec_type == "macr":
+            # (y - c) s_i = u . (s_i I_i) - c s_i: the bias head on the model's item prep (built once per evaluation), alpha = 1, beta = -c s_i
+            rec = self.Recommender
+            ops.check_macr_lists(rec.emb_dim, K)
+            prep = rec.item_prep()
+            if _sel is None:
+                return ops.recommend_topk_macr(rec.score_tables()[0], I, rec.weights["w_item"], users, rec.c, K, hist, prep=prep)
+            ones = torch.ones(users.numel(), dtype=torch.float32, device=self.device)
+            return ops.recommend_topk_bias(rec.score_tables()[0], prep.J.index_select(0, _sel).contiguous(), users, ones,
+                                           prep.bias(rec.c).index_select(0, _sel).contiguous(), K, hist)
         if self._shard is not None and _sel is None:
             self._shard.set_popularity(pop_t)
             return self._shard.topk(users, K, head, hist)
@@ -274,7 +296,7 @@ class DatasetApi_Model:
         """Dense scores f32 [B, len(items)] (:642-669): batch_ratings / condition_ratings as the NeuRec evaluators' protocol fetches them (the
         reference imports that protocol and never calls it).  pda_score_dense_f32: every entry is the exact fmaf chain of the top-K kernels, so
         these scores equal the values do_recommendation ranks by, bit for bit (bf16 tables: widened first, as their scores are defined)."""
-        if model_type not in ("main_branch", "condition"):
+        if model_type not in ("main_branch", "condition", "macr"):
             raise NotImplementedError("error -- not implement this type testing method...")      # :664
         U, I = self.Recommender.score_tables()
         users = torch.as_tensor(np.asarray(batch_users, dtype=np.int32), device=self.device)
@@ -283,6 +305,16 @@ class DatasetApi_Model:
         it_t = None if whole else torch.as_tensor(it.astype(np.int32), device=self.device)
         if U.dtype != torch.float32:
             U, I = U.float(), I.float()
+        if model_type == "macr":
+            # rubi_ratings_both (:628) of a MACR model: (y - c) s_i s_u, y the exact chain, the rest element-wise torch (not a hot path)
+            rec = self.Recommender
+            if not isinstance(rec, MACRBPRMF):
+                raise NotImplementedError("the macr ratings need a MACR model (--train macr)")
+            y = ops.score_dense(U, I, users, ops.HEAD_RAW, None, it_t)
+            Isel = I if it_t is None else I.index_select(0, it_t.long())
+            s_i = torch.sigmoid(Isel @ rec.weights["w_item"]).view(1, -1)
+            s_u = torch.sigmoid(U.index_select(0, users.long()) @ rec.weights["w_user"]).view(-1, 1)
+            return ((y - rec.c) * s_i * s_u).cpu().numpy()
         pop = None
         if model_type == "condition":
             pop = torch.as_tensor(np.asarray(pos_pop, dtype=np.float32).reshape(-1), device=self.device)
@@ -311,6 +343,8 @@ class DatasetApi_Model:
     def predict(self, user_batch, item_batch):                                              # :683-696
         if item_batch is None:
             item_batch = list(range(self.n_items))
+        if isinstance(self.Recommender, MACRBPRMF):
+            return self.testing(self.sess, user_batch, item_batch, "macr")
         if self.testing_model_type == "o":
             return self.testing(self.sess, user_batch, item_batch, "main_branch")
         if self.testing_model_type == "condition":
@@ -453,6 +487,12 @@ def main(argv=None):
         if args.test not in ("normal", "ips"):
             raise NotImplementedError("--train ips goes with --test normal (the raw head and the gamma search of a BPRMF) or --test ips, not --test "
                                       + str(args.test))
+    if args.train == "macr":
+        check_macr(args)
+        if args.test != "macr":
+            raise NotImplementedError("--train macr goes with --test macr (the counterfactual head and the search over c), not --test " + str(args.test))
+    elif args.test == "macr":
+        raise NotImplementedError("--test macr needs a MACR model (--train macr), not --train " + str(args.train))
     random.seed(2020)                      # :934-936
     np.random.seed(2020)
     torch.manual_seed(2021)
@@ -472,9 +512,12 @@ def main(argv=None):
     linear_predict_popularity = np.power(linear_predict_popularity, popularity_exp)
 
     with_pop = False
-    if args.model == "mf" and args.train in ("normal", "dice", "ips"):           # :963-970 (DICE and IPS are evaluated like a BPRMF: --test normal)
+    if args.model == "mf" and args.train in ("normal", "dice", "ips", "macr"):   # :963-970 (DICE and IPS are evaluated like a BPRMF: --test normal)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
-        print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
+        print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------", "macr": "-------    running MACR  ----------------"}
+              .get(args.train, "-------    running IPS  ----------------"))
+        if args.train == "macr":
+            args.saveID += "macr"
         if args.train == "ips":
             args.saveID += "ips"
             config["ips_item_counts"] = ips_item_counts(data.train_user_list, data.n_items)
@@ -568,7 +611,7 @@ def main(argv=None):
                 before = rec._loss_row_i
                 row = sess.run_async(fetches)
                 if rec._loss_row_i == before:           # (a generator longer than n_batch + 1 steps: the step fell back to the ring's rows)
-                    extra += row[:3]
+                    extra += rec.trainer_terms(row) if hasattr(rec, "trainer_terms") else row[:3]
         except OutOfRangeError:
             pass
         acc = rec.finish_loss_rows() + extra
@@ -609,6 +652,29 @@ def main(argv=None):
             print("test: time:", time() - ttt1)
             _print_result(ret_main)
             ret = ret_main
+        elif args.test == "macr":
+            # MACR: c = 0 (rubi_ratings_both_nonc) first, then the search over c; the best c by recall@Ks[0] on the validation objective
+            # drives the early stop and best_ckpt.ckpt, c = 0 the main ones
+            print(perf_str)
+            ttt1 = time()
+            evaluation_model.set_testing_popularity(None)
+            rec.update_c(0.0)
+            ret_main = evaluation_model.eval(model, sess, rec_type="macr")
+            print("MACR without c")
+            _print_result(ret_main)
+            best_ret, best_c = ret_main, 0.0
+            for c in macr_c_grid(args):
+                rec.update_c(c)
+                ret_c = evaluation_model.eval(model, sess, rec_type="macr")
+                if ret_c["recall"][0] > best_ret["recall"][0]:
+                    best_ret, best_c = ret_c, c
+                print("c: {:.4f} best c: {:.4f}".format(c, best_c))
+                _print_result(ret_c)
+            rec.best_c = best_c
+            rec.update_c(best_c)
+            print("MACR best c: {:.6f}  test: time: {:.3f}".format(best_c, time() - ttt1))
+            _print_result(best_ret)
+            ret = best_ret
         elif args.test == "normal":                                              # :1159-1191
             print(perf_str)
             ttt1 = time()
@@ -699,6 +765,16 @@ def main(argv=None):
             print("|||---BPRMF-A with injecting %s:" % name)
             _print_result(r)
         print("----------------------------")
+    elif args.test == "macr":
+        evaluation_model.set_testing_popularity(None)
+        rec.update_c(0.0)
+        ret = evaluation_model.eval(model, sess, rec_type="macr")
+        print("---- MACR without c:")
+        _print_result(ret)
+        rec.update_c(rec.best_c)
+        ret = evaluation_model.eval(model, sess, rec_type="macr")
+        print("---- MACR result with the best c of the validation (c = {:.6f}):".format(rec.best_c))
+        _print_result(ret)
     elif args.test in ("temp_pop", "dice", "ips"):                               # :1310-1314
         evaluation_model.set_testing_popularity(None)
         ret = evaluation_model.eval(model, sess, rec_type="main_branch")

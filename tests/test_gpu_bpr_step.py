@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import train_ref
 from oracle import c_oracle
 from oracle import pda_oracle as po
 
@@ -169,6 +170,14 @@ def test_reference_faithful_adam_three_steps(dev):
         ops.adam_dense_sweep(It, st["mI"], st["vI"], st["gI"], lr_t)
         np.testing.assert_allclose(loss.cpu().numpy(), ref_loss, atol=TOL, rtol=TOL)
         assert float(st["gU"].abs().max()) == 0.0 and float(st["gI"].abs().max()) == 0.0   # accumulator reset
+        if t == 1:
+            # the step read the oracle's inputs bit for bit: all four moment tables within train_ref's propagated rounding bound (it scales with
+            # the gradient; max |v| is 1e-9 here, which atol = 1e-5 below cannot see)
+            bnd = train_ref.bound(train_ref.Case(U, I, users, pos, neg, pp, pn, regs), True)
+            for k in ("mU", "vU", "mI", "vI"):
+                err = np.abs(st[k].cpu().numpy() - state[k])
+                print(k, "first step: largest err / bound", (err / np.where(bnd[k] > 0, bnd[k], 1.0)).max())
+                assert (err <= bnd[k]).all(), k
     for got, ref in ((Ut, Ur), (It, Ir)):
         adam_close(got.cpu().numpy(), ref)
     np.testing.assert_allclose(st["mI"].cpu().numpy(), state["mI"], atol=TOL)

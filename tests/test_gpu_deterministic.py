@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import train_ref
 from oracle import pda_oracle as po
 
 pytestmark = pytest.mark.gpu
@@ -94,6 +95,15 @@ def test_planned_gradient_matches_the_float64_oracle(dev, d, with_pop, shape, B)
     np.testing.assert_allclose(got_loss, ref_loss, atol=TOL, rtol=TOL)
     np.testing.assert_allclose(got_gU, rgU, atol=TOL)
     np.testing.assert_allclose(got_gI, rgI, atol=TOL)
+    # the same arrays within train_ref's a-priori rounding bound, which scales with 1 / B like the gradients (the median |gU| at B = 32768 is
+    # 3e-6: atol = 1e-5 accepts zeros there)
+    one = np.ones(B, np.float32)
+    bnd = train_ref.bound(train_ref.Case(U, I, users, pos, neg, pp if with_pop else one, pn if with_pop else one, regs), with_pop, tables=False)
+    for name, got, ref in (("gU", got_gU, rgU), ("gI", got_gI, rgI)):
+        err = np.abs(got - ref)
+        print(name, "largest err / bound", (err / np.where(bnd[name] > 0, bnd[name], 1.0)).max())
+        assert (err <= bnd[name]).all(), name
+    assert np.abs(got_loss - ref_loss).max() <= bnd["loss"].max() and (np.abs(got_loss - ref_loss) <= bnd["loss"]).all()
     in_u = np.zeros(nU, bool)
     in_u[users] = True
     in_i = cnt > 0
@@ -125,6 +135,18 @@ def _small_case():
         check_batch(users, pos, neg, nI, B)
         batches.append((users, pos, neg) + pops(seed, B))
     return nU, nI, d, B, regs, lr, U, I, batches
+
+
+def _check_first_step(st, U, I, batch, regs):
+    """After step 1 the tables the step read still equal the oracle's inputs bit for bit: all four moment tables against one oracle step, within
+    train_ref's propagated rounding bound (max |v| is 1e-9 here: the atol = 1e-5 of _check_against_oracle cannot fail on it)."""
+    users, pos, neg, pp, pn = batch
+    c = train_ref.Case(U, I, users, pos, neg, pp, pn, regs)
+    ref, bnd = train_ref.reference(c, True), train_ref.bound(c, True)
+    for k in ("mU", "vU", "mI", "vI"):
+        err = np.abs(st[k].cpu().numpy() - ref[k])
+        print(k, "first step: largest err / bound", (err / np.where(bnd[k] > 0, bnd[k], 1.0)).max())
+        assert (err <= bnd[k]).all(), k
 
 
 def _check_against_oracle(got, ref, losses, ref_losses):
@@ -166,6 +188,8 @@ def test_three_adam_steps_match_the_oracle(dev, path):
             ops.adam_step(Ut, st["mU"], st["vU"], st["gU"], tagU, It, st["mI"], st["vI"], st["gI"], tagI, ut, pt, nt, ppt, pnt, **common)
         losses.append(loss.cpu().numpy())
         assert float(st["gU"].abs().max()) == 0.0 and float(st["gI"].abs().max()) == 0.0   # accumulators reset by the sweep
+        if t == 1:
+            _check_first_step(st, U, I, b, regs)
     _check_against_oracle((Ut, It, st), ref[:3], losses, ref[3])
 
 
@@ -190,7 +214,11 @@ def test_three_model_steps_with_the_flag_match_the_oracle(dev, optimizer):
     assert m.deterministic and not m.adam_exact_lazy
     if optimizer == "adam":
         ref = _three_steps_oracle(U, I, batches, regs, B, lr)
-        losses = [m.train_step(*to(dev, *b)).cpu().numpy().copy() for b in batches]      # (no plan given: train_step makes it)
+        losses = []
+        for t, b in enumerate(batches, 1):
+            losses.append(m.train_step(*to(dev, *b)).cpu().numpy().copy())             # (no plan given: train_step makes it)
+            if t == 1:
+                _check_first_step(m._state, U, I, b, regs)
         _check_against_oracle((m.weights["user_embedding"], m.weights["item_embedding"], m._state), ref[:3], losses, ref[3])
         return
 

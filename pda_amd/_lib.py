@@ -1,5 +1,5 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
-pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h and pda_hip_macr.h).
+pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h and pda_hip_gcn.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -215,6 +215,14 @@ MACR_SIGNATURES = {
     "pda_macr_item_bias_f32": (_i, [_vp, _f, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_gcn.h (the LightGCN backbone: `--model lightgcn`)
+GCN_CHUNK = 512
+GCN_SIGNATURES = {
+    "pda_gcn_spmm_workspace_bytes": (_sz, [_sz, _i]),
+    "pda_gcn_spmm_f32": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _sz, _vp]),
+    "pda_gcn_reg_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -234,7 +242,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
-            list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()):
+            list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

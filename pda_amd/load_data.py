@@ -46,7 +46,7 @@ class _Base:
         self.expo_popularity = None
         if getattr(args, "data_type", "ori") != "ori":
             raise NotImplementedError("only --data_type ori is implemented")
-        if getattr(args, "model", "mf") not in ("mf", "biasmf"):
+        if getattr(args, "model", "mf") not in ("mf", "biasmf", "lightgcn"):
             raise NotImplementedError("only can sampling for mf-type model")   # MF/load_data.py:708
         self._load(args)
         self.n_users += 1                                   # ids are 0-based: MF/load_data.py:93-94

@@ -6,6 +6,7 @@
     DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
     IPSBPRMF           IPS / IPS-C / IPS-CN (no reference code: DESIGN.md 5g)  a BPRMF trained with inverse propensity weights; Adam sweep only
     MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
+    LightGCN           the LightGCN backbone (no reference code: DESIGN.md 5j)  ego tables propagated over the train graph; ConditionalLightGCN: PD/PDA on it
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
 trainer passes to `sess.run`.  Here they are light handle objects understood by `pda_amd.train_new_api.Session`,
@@ -872,3 +873,180 @@ class MACRBPRMF(BPRMF):
             st = self._macr_state()
             for k in self.CKPT_MOMENTS:
                 getattr(st, k).copy_(sd[k])
+
+
+GCN_EMBED_SIZES = ops.GCN_EMBED_SIZES       # --embed_size of a LightGCN model: the row widths of pda_gcn_spmm_f32
+
+
+def gcn_train_pairs(train_user_list):
+    """The train pairs (users int64 [n], items int64 [n]) from the loader's {user: [items]} lists: what the graph is built from (a pair that
+    occurs twice is one edge: ops.gcn_graph_arrays)."""
+    import numpy as np
+    us = [u for u, items in train_user_list.items() if len(items)]
+    if not us:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    lens = [len(train_user_list[u]) for u in us]
+    return np.repeat(np.asarray(us, dtype=np.int64), lens), np.concatenate([np.asarray(train_user_list[u], dtype=np.int64) for u in us])
+
+
+def check_lightgcn(args):
+    """--model lightgcn: refuse, before anything is built, what the LightGCN backbone has no kernel for.  Every message names the combination."""
+    train = getattr(args, "train", "normal")
+    if train in ("temp_pop", "dice", "ips", "macr"):
+        raise NotImplementedError("--model lightgcn --train %s: the LightGCN backbone trains with --train normal (BPR) or s_condition (PD/PDA) only" % train)
+    if train not in ("normal", "s_condition"):
+        raise NotImplementedError("--model lightgcn --train %s: normal | s_condition" % train)
+    test = getattr(args, "test", "normal")
+    if test not in (("normal",) if train == "normal" else ("s_condition", "normal")):
+        raise NotImplementedError("--model lightgcn --train %s --test %s: --train normal goes with --test normal, --train s_condition with "
+                                  "--test s_condition | normal" % (train, test))
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--model lightgcn --optimizer %s: the gradient of a graph model is dense, it runs the reference's Adam only "
+                                  "(--optimizer adam)" % args.optimizer)
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--model lightgcn --table_dtype %s: the LightGCN backbone runs fp32 tables only" % args.table_dtype)
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--model lightgcn --deterministic 1: the propagation is bit-reproducible, the triplet gradient under it is summed "
+                                  "with float atomics (no planned gradient on the final tables)")
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--model lightgcn --gpus %s: no item-parallel training (the graph is not sharded); train on one GPU" % args.gpus)
+    L = getattr(args, "gcn_layers", 3)
+    if int(L) != L or not 0 <= int(L) <= ops.GCN_MAX_LAYERS:
+        raise ValueError("--gcn_layers must be an integer in 0 .. %d, got %s" % (ops.GCN_MAX_LAYERS, L))
+    if int(args.embed_size) not in GCN_EMBED_SIZES:
+        raise NotImplementedError("--model lightgcn --embed_size %s: the product kernel takes one of %s" % (args.embed_size, GCN_EMBED_SIZES))
+
+
+class LightGCN(_MFBase):
+    """LightGCN (He et al., SIGIR'20; DESIGN.md 5j, include/pda_hip_gcn.h) under the BPR loss.  Fetchables: those of BPRMF.
+    weights: the EGO tables user_embedding / item_embedding, Xavier-uniform from the same seed as every other model, kept as the two row
+    slices of one [n_users + n_items, d] buffer so that one launch per layer serves both directions.  score_tables() returns the FINAL tables
+    (the layer mean over --gcn_layers propagations): everything that ranks reads those.  data_config["gcn_train_pairs"] = (users, items), or
+    set_train_pairs: the train pairs the graph is built from -- rebuilt from the data, never stored in a checkpoint."""
+    with_pop = False
+    MODEL_NAME = "lightgcn"
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, pos_pop_api=None,
+                 neg_pop_api=None, **kw):
+        check_lightgcn(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, pos_pop_api, neg_pop_api, **kw)
+        self.adam_exact_lazy = False
+        self.gcn_layers = int(getattr(args, "gcn_layers", 3))
+        self.graph = None
+        self._final = None                   # ((F_U, F_I), version of the ego buffer they were computed from)
+        self._G = None
+        if data_config.get("gcn_train_pairs") is not None:
+            self.set_train_pairs(*data_config["gcn_train_pairs"])
+        self.opt, self.loss = Fetch(self, "opt"), Fetch(self, "loss")
+        self.mf_loss, self.reg_loss = Fetch(self, "mf_loss"), Fetch(self, "reg_loss")
+        self.batch_ratings = Fetch(self, "batch_ratings")
+
+    def init_weights(self, gen):
+        w = super().init_weights(gen)        # (the draws of _MFBase, then moved into one buffer: the same values from the same seed)
+        self._E0 = torch.cat([w["user_embedding"], w["item_embedding"]], dim=0)
+        return {"user_embedding": self._E0[:self.n_users], "item_embedding": self._E0[self.n_users:]}
+
+    def set_train_pairs(self, users, items):
+        self.graph = ops.GcnGraph(users, items, self.n_users, self.n_items, self.device)
+        self._final = None
+
+    def _opt_state(self):
+        if self._state is None:
+            z = lambda: torch.zeros_like(self._E0)      # noqa: E731
+            m, v = z(), z()
+            nu = self.n_users
+            self._state = {"mU": m[:nu], "vU": v[:nu], "mI": m[nu:], "vI": v[nu:]}
+        return self._state
+
+    def _need_graph(self):
+        if self.graph is None:
+            raise ValueError("LightGCN needs the train pairs before it propagates (data_config['gcn_train_pairs'] or set_train_pairs)")
+        return self.graph
+
+    def score_tables(self):
+        """The final tables of the current ego tables: recomputed when a step (or a restore) has moved them since, cached otherwise."""
+        U0, I0 = self.weights["user_embedding"], self.weights["item_embedding"]
+        if self.gcn_layers == 0:
+            return U0, I0
+        if self._final is None or self._final[1] != self._E0._version:
+            F = ops.gcn_propagate(self._need_graph(), U0, I0, self.gcn_layers)
+            self._final = (F, self._E0._version)
+        return self._final[0]
+
+    def train_step(self, users, pos, neg, pos_pop=None, neg_pop=None, plan=None) -> torch.Tensor:
+        """One LightGCN step: propagate, the triplet gradient on the final tables (regs = 0), the backward pass, the ego-row regulariser, Adam
+        over both ego tables.  No host read; returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this step."""
+        if not self.with_pop:
+            pos_pop = neg_pop = None
+        elif pos_pop is None or neg_pop is None:
+            raise ValueError("PD/PDA needs pos_pop and neg_pop")
+        g = self._need_graph()
+        U0, I0 = self.weights["user_embedding"], self.weights["item_embedding"]
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._opt_state()
+        if self._G is None:
+            self._G = torch.zeros_like(self._E0)
+        L = self.gcn_layers
+        F_U, F_I = ops.gcn_propagate(g, U0, I0, L)
+        self._final = None                   # (the graph's buffer now holds the tables of BEFORE this step's update)
+        self._G.zero_()
+        G_U, G_I = self._G[:self.n_users], self._G[self.n_users:]
+        ops.bpr_step(F_U, F_I, users, pos, neg, pos_pop, neg_pop, regs=0.0, reg_div=self.batch_size, mode=ops.UPD_DENSE_GRAD, gU=G_U, gI=G_I,
+                     loss_acc=self._loss)
+        H_U, H_I = ops.gcn_backward(g, G_U, G_I, L)
+        ops.gcn_reg(U0, I0, users, pos, neg, H_U, H_I, regs=self.decay, reg_div=self.batch_size, loss_acc=self._loss)
+        self._t += 1
+        ops.adam_dense_sweep2(U0, st["mU"], st["vU"], H_U, I0, st["mI"], st["vI"], H_I, ops.adam_lr_t(self.lr, self._t))
+        return self._loss
+
+    def state_dict(self):
+        sd = {"format": self.CKPT_FORMAT, "model": self.MODEL_NAME, "gcn_layers": self.gcn_layers, "embed_size": self.emb_dim, "n_users": self.n_users,
+              "n_items": self.n_items, "optimizer": self.optimizer, "table_dtype": self.table_dtype,
+              "user_embedding": self.weights["user_embedding"], "item_embedding": self.weights["item_embedding"], "adam_t": self._t}
+        if self._state is not None:
+            sd.update(self._state)
+        return sd
+
+    def load_state_dict(self, sd):
+        name = type(self).__name__
+        if not isinstance(sd, dict) or "user_embedding" not in sd:
+            raise ValueError("not a pda_amd checkpoint (a tf.train.Saver checkpoint of the reference cannot be loaded)")
+        if sd.get("format") != self.CKPT_FORMAT:
+            raise ValueError("checkpoint format %r, %s reads %s" % (sd.get("format"), name, self.CKPT_FORMAT))
+        if sd.get("model", "mf") != self.MODEL_NAME:
+            raise ValueError("checkpoint of a %s model cannot be loaded into %s (its tables are not ego tables)" % (sd.get("model", "mf"), name))
+        for key, mine in (("embed_size", self.emb_dim), ("n_users", self.n_users), ("n_items", self.n_items), ("gcn_layers", self.gcn_layers)):
+            if int(sd[key]) != int(mine):
+                raise ValueError("checkpoint %s = %s, model has %s" % (key, sd[key], mine))
+        for k in ("user_embedding", "item_embedding"):
+            if tuple(sd[k].shape) != tuple(self.weights[k].shape):
+                raise ValueError("checkpoint table %s does not have the model's shape" % k)
+        for k in ("user_embedding", "item_embedding"):
+            self.weights[k].copy_(sd[k])
+        self._final = None
+        self._t = int(sd.get("adam_t", 0))
+        if "mU" in sd:
+            st = self._opt_state()
+            for k in ("mU", "vU", "mI", "vI"):
+                st[k].copy_(sd[k])
+        else:
+            self._state = None
+
+
+class ConditionalLightGCN(LightGCN):
+    """PD / PDA on the LightGCN backbone: the matching term is the popularity head (ELU + 1) x pop^gamma of ConditionalBPRMF on the final tables.
+    Fetchables: those of ConditionalBPRMF."""
+    with_pop = True
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.opt_pop_global, self.loss_pop_global = Fetch(self, "opt"), Fetch(self, "loss")
+        self.mf_loss_pop_global, self.reg_loss_pop_global = Fetch(self, "mf_loss"), Fetch(self, "reg_loss")
+        self.condition_ratings = Fetch(self, "condition_ratings")

@@ -2442,3 +2442,191 @@ def recommend_topk_macr(U, I, w_item, users, c: float, K=50, hist: Optional[Hist
         raise ValueError("U and the item prep share the embed dim")
     ones = torch.ones(users.numel(), dtype=torch.float32, device=U.device)
     return recommend_topk_bias(U, prep.J, users, ones, prep.bias(c), K, hist, stats=stats)
+
+
+# ---- LightGCN (include/pda_hip_gcn.h) -------------------------------------------------------------------------------------------------------
+GCN_EMBED_SIZES = (32, 64, 128, 256)
+GCN_CHUNK = _lib.GCN_CHUNK                    # PDA_GCN_CHUNK: a row with more edges is cut into chunks of this many
+GCN_MAX_LAYERS = 4
+
+
+def gcn_graph_arrays(users, items, n_users: int, n_items: int, chunk: int = GCN_CHUNK) -> dict:
+    """The train graph of include/pda_hip_gcn.h from the train pairs, on the host (numpy; no GPU needed): the distinct (u, i) edges sorted by
+    (u, i), deg_u / deg_i, w = fl32(1 / sqrt(float64(deg_u deg_i))), the symmetric CSR over the n_users + n_items stacked rows (a user row
+    lists n_users + i ascending, an item row lists u ascending) and the work list (`work` int64 [n_work, 4] = row, first edge, end edge, slot;
+    `long_rows` int64 [n_long, 3] = row, first slot, chunks; `n_slots`).  The entries of `work` are sorted by falling length (stable: rows and
+    chunks in rising order among equals), so the lane groups of a wave run about equally long; every sum's order stays that of the CSR.
+    Ids outside the tables are an error here, once: the kernels trust the graph."""
+    import numpy as np
+    n_users, n_items, chunk = int(n_users), int(n_items), int(chunk)
+    if n_users < 1 or n_items < 1 or n_users + n_items > 0x7FFFFFFF or chunk < 1:
+        raise ValueError("gcn graph: n_users, n_items >= 1 with n_users + n_items < 2^31, chunk >= 1")
+    u, i = np.asarray(users, dtype=np.int64).reshape(-1), np.asarray(items, dtype=np.int64).reshape(-1)
+    if u.shape != i.shape:
+        raise ValueError("gcn graph: users and items hold one id per train pair each")
+    if u.size and (u.min() < 0 or u.max() >= n_users or i.min() < 0 or i.max() >= n_items):
+        raise ValueError("gcn graph: a train pair has a user or item id outside the tables")
+    key = np.unique(u * n_items + i)
+    eu, ei = key // n_items, key % n_items
+    deg_u, deg_i = np.bincount(eu, minlength=n_users).astype(np.int64), np.bincount(ei, minlength=n_items).astype(np.int64)
+    w = (1.0 / np.sqrt((deg_u[eu] * deg_i[ei]).astype(np.float64))).astype(np.float32)
+    N = n_users + n_items
+    o = np.lexsort((eu, ei))                       # the same edges by (i, u): the item rows
+    deg = np.concatenate([deg_u, deg_i])
+    indptr = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(deg, out=indptr[1:])
+    indices = np.concatenate([n_users + ei, eu[o]]).astype(np.int32)
+    weights = np.concatenate([w, w[o]])
+    nch = np.maximum(1, -(-deg // chunk))
+    first = np.cumsum(nch) - nch
+    row = np.repeat(np.arange(N, dtype=np.int64), nch)
+    j = np.arange(int(nch.sum()), dtype=np.int64) - np.repeat(first, nch)
+    e0 = indptr[row] + j * chunk
+    e1 = np.minimum(e0 + chunk, indptr[row + 1])
+    is_long = nch > 1
+    slot0 = np.cumsum(np.where(is_long, nch, 0)) - np.where(is_long, nch, 0)
+    slot = np.where(is_long[row], slot0[row] + j, -1)
+    order = np.argsort(-(e1 - e0), kind="stable")
+    work = np.ascontiguousarray(np.stack([row, e0, e1, slot], axis=1)[order])
+    lr = np.flatnonzero(is_long)
+    long_rows = np.ascontiguousarray(np.stack([lr, slot0[lr], nch[lr]], axis=1).astype(np.int64))
+    return dict(n_users=n_users, n_items=n_items, chunk=chunk, edge_users=eu, edge_items=ei, edge_w=w, deg_u=deg_u, deg_i=deg_i, indptr=indptr,
+                indices=indices, w=weights, work=work, long_rows=long_rows, n_slots=int(np.where(is_long, nch, 0).sum()))
+
+
+class GcnGraph:
+    """The train graph on the device, built once per graph (gcn_graph_arrays): the deduplicated edges, the degrees and weights, the symmetric
+    CSR and the work list; `host` keeps the numpy arrays.  It also owns what the passes write: the partial-sum workspace, two layer buffers,
+    the final tables and the propagated gradient, one set per row width.  What gcn_propagate / gcn_backward return are views of those
+    buffers: valid until the next call of the same function on this graph."""
+
+    def __init__(self, users, items, n_users: int, n_items: int, device, chunk: int = GCN_CHUNK):
+        if int(chunk) != GCN_CHUNK:
+            raise ValueError(f"the kernels are built for chunks of {GCN_CHUNK} edges")
+        h = self.host = gcn_graph_arrays(users, items, n_users, n_items, chunk)
+        self.n_users, self.n_items, self.n_rows = h["n_users"], h["n_items"], h["n_users"] + h["n_items"]
+        self.device = torch.device(device)
+        dev = lambda a: torch.from_numpy(a).to(self.device)      # noqa: E731
+        self.indptr, self.indices, self.w = dev(h["indptr"]), dev(h["indices"]), dev(h["w"])
+        self.work, self.long_rows, self.n_slots = dev(h["work"]), dev(h["long_rows"]), h["n_slots"]
+        self.n_edges = int(h["edge_w"].shape[0])
+        self._bufs = {}
+
+    @staticmethod
+    def from_csr(indptr, indices, n_items: int, device) -> "GcnGraph":
+        """From the train CSR (rows: users; int64 indptr, item ids), e.g. Data.train_csr."""
+        import numpy as np
+        ip = indptr.cpu().numpy() if torch.is_tensor(indptr) else np.asarray(indptr)
+        ix = indices.cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
+        users = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip))
+        return GcnGraph(users, ix, len(ip) - 1, n_items, device)
+
+    def buffers(self, d: int) -> dict:
+        if d not in self._bufs:
+            mk = lambda: torch.zeros((self.n_rows, d), dtype=torch.float32, device=self.device)      # noqa: E731
+            nbytes = _lib.load().pda_gcn_spmm_workspace_bytes(self.n_slots, d)
+            b = dict(A=mk(), B=mk(), F=mk(), H=mk(), ws=torch.empty(max(1, nbytes), dtype=torch.uint8, device=self.device))
+            b["Fv"], b["Hv"] = self.split(b["F"]), self.split(b["H"])      # (the same view objects call after call: what ops caches per table stays keyed)
+            self._bufs[d] = b
+        return self._bufs[d]
+
+    def split(self, t):
+        return t[:self.n_users], t[self.n_users:]
+
+
+def _gcn_stacked(graph: GcnGraph, a, b, what: str):
+    """(a [n_users, d]; b [n_items, d]) as ONE [n_users + n_items, d] tensor: the storage itself where b starts where a ends (the model's
+    tables), a copy otherwise."""
+    a, b = _need(a, torch.float32, what + " (users)"), _need(b, torch.float32, what + " (items)")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.shape[0] != graph.n_users or b.shape[0] != graph.n_items:
+        raise ValueError(f"{what}: [n_users, d] and [n_items, d] tables of the graph's {graph.n_users} users and {graph.n_items} items")
+    if a.shape[1] not in GCN_EMBED_SIZES:
+        raise ValueError(f"LightGCN: the embedding width d must be one of {GCN_EMBED_SIZES}, got {a.shape[1]}")
+    if a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr() and a.data_ptr() + a.numel() * 4 == b.data_ptr():
+        return a.as_strided((graph.n_rows, a.shape[1]), (a.shape[1], 1), a.storage_offset())
+    return torch.cat([a, b], dim=0)
+
+
+def gcn_spmm(graph: GcnGraph, X, *, add=None, Y=None, sum_in=None, sum_out=None, scale: float = 1.0):
+    """pda_gcn_spmm_f32 on stacked [n_users + n_items, d] tensors: y = add + A X;  Y = scale y, or with a running sum Y = y (optional) and
+    sum_out = scale (sum_in + y).  Y is allocated when neither Y nor sum_out is given.  Returns (Y, sum_out)."""
+    X = _need(X, torch.float32, "X")
+    if X.dim() != 2 or X.shape[0] != graph.n_rows or X.shape[1] not in GCN_EMBED_SIZES:
+        raise ValueError(f"X: float32 [{graph.n_rows}, d], d one of {GCN_EMBED_SIZES}")
+    if (sum_in is None) != (sum_out is None):
+        raise ValueError("sum_in and sum_out come together")
+    if Y is None and sum_out is None:
+        Y = torch.empty_like(X)
+    for t, n in ((add, "add"), (Y, "Y"), (sum_in, "sum_in"), (sum_out, "sum_out")):
+        if _need(t, torch.float32, n, optional=True) is not None and t.shape != X.shape:
+            raise ValueError(f"{n} has the shape of X")
+    if not math.isfinite(float(scale)):
+        raise ValueError("scale must be finite")
+    d = X.shape[1]
+    ws = graph.buffers(d)["ws"]
+    check(_lib.load().pda_gcn_spmm_f32(ptr(graph.indptr), ptr(graph.indices), ptr(graph.w), graph.n_rows, ptr(graph.work), graph.work.shape[0],
+                                       ptr(graph.long_rows) if graph.long_rows.shape[0] else None, graph.long_rows.shape[0], graph.n_slots,
+                                       ptr(X), d, ptr(add), ptr(Y), ptr(sum_in), ptr(sum_out), float(scale),
+                                       ptr(ws) if graph.n_slots else None, ws.numel() if graph.n_slots else 0, stream_ptr()), "pda_gcn_spmm_f32")
+    mark_modified(*(t for t in (Y, sum_out) if t is not None))
+    return Y, sum_out
+
+
+def _gcn_layers(L) -> int:
+    L = int(L)
+    if not 0 <= L <= GCN_MAX_LAYERS:
+        raise ValueError(f"gcn layers must lie in 0 .. {GCN_MAX_LAYERS}, got {L}")
+    return L
+
+
+def gcn_propagate(graph: GcnGraph, U0, I0, L: int):
+    """The final tables (F_U, F_I) = (1 / (L + 1)) sum_k A^k (U0; I0): L launches (plus one per layer for cut rows), the layer mean kept as a
+    running sum by each row's owner and scaled in the last one.  L = 0: the ego tables themselves.  The result is a pair of views of the
+    graph's own buffer."""
+    L = _gcn_layers(L)
+    E0 = _gcn_stacked(graph, U0, I0, "ego tables")
+    if L == 0:
+        return U0, I0
+    b = graph.buffers(E0.shape[1])
+    X, F = E0, b["F"]
+    for k in range(1, L + 1):
+        last = k == L
+        Y = None if last else b["AB"[(k - 1) & 1]]
+        gcn_spmm(graph, X, Y=Y, sum_in=E0 if k == 1 else F, sum_out=F, scale=1.0 / (L + 1) if last else 1.0)
+        X = Y
+    return b["Fv"]
+
+
+def gcn_backward(graph: GcnGraph, G_U, G_I, L: int):
+    """(1 / (L + 1)) sum_{k = 0 .. L} A^k (G_U; G_I) in Horner form: H <- G + A H, L times from H = G, the last one scaled.  L = 0: G itself.
+    The result is a pair of views of the graph's own buffer."""
+    L = _gcn_layers(L)
+    G = _gcn_stacked(graph, G_U, G_I, "gradient tables")
+    if L == 0:
+        return G_U, G_I
+    b = graph.buffers(G.shape[1])
+    X = G
+    for j in range(1, L + 1):
+        last = j == L
+        Y = b["H"] if last else b["AB"[(j - 1) & 1]]
+        gcn_spmm(graph, X, add=G, Y=Y, scale=1.0 / (L + 1) if last else 1.0)
+        X = Y
+    return b["Hv"]
+
+
+def gcn_reg(U0, I0, users, pos, neg, gU, gI, *, regs: float, reg_div: float, loss_acc: Optional[torch.Tensor] = None):
+    """pda_gcn_reg_f32: gU / gI += (regs / reg_div) x the batch's ego rows, per occurrence; loss_acc float32 [3]: [0] and [2] += the regulariser."""
+    U0, I0, gU, gI = (_need(t, torch.float32, n) for t, n in ((U0, "U0"), (I0, "I0"), (gU, "gU"), (gI, "gI")))
+    if U0.dim() != 2 or I0.dim() != 2 or U0.shape[1] != I0.shape[1] or gU.shape != U0.shape or gI.shape != I0.shape:
+        raise ValueError("gcn_reg: U0 [n_users, d], I0 [n_items, d] and gradient tables of the same shapes")
+    if U0.shape[1] not in GCN_EMBED_SIZES:
+        raise ValueError(f"LightGCN: the embedding width d must be one of {GCN_EMBED_SIZES}, got {U0.shape[1]}")
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    B = users.numel()
+    if B < 1 or pos.numel() != B or neg.numel() != B:
+        raise ValueError("users/pos/neg must have the same, non-zero length")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("loss_acc holds three float32")
+    check(_lib.load().pda_gcn_reg_f32(ptr(U0), ptr(I0), U0.shape[0], I0.shape[0], ptr(users), ptr(pos), ptr(neg), B, U0.shape[1], float(regs),
+                                      float(reg_div), ptr(gU), ptr(gI), ptr(loss_acc), stream_ptr()), "pda_gcn_reg_f32")
+    mark_modified(gU, gI)

@@ -39,7 +39,7 @@ _REFERENCE_FLAGS = [
     ("train_c", str, "val", "(unused)"),
     ("lr", float, 1e-3, "learning rate"),
     ("wd", float, 1e-5, "(overwritten by --regs, MF/train_new_api.py:1020)"),
-    ("model", None, "mf", "only 'mf' is implemented"),
+    ("model", None, "mf", "mf (matrix factorisation) | lightgcn (the LightGCN backbone, --gcn_layers; --train normal | s_condition)"),
     ("skew", int, 0, "(unused)"),
     ("model_type", None, "o", "(unused)"),
     ("devide_ratio", float, 0.8, "(unused)"),
@@ -79,6 +79,7 @@ _EXTENSION_FLAGS = [
     ("xq_candidates", int, 1000, "xQuAD: candidates per user the re-ranking selects from, max(Ks) .. 1024 (above 54 they come from the deep path)"),
     ("xq_head_share", float, 0.8, "xQuAD: the short head is the most popular items that hold this share of the train interactions, strictly inside 0 .. 1"),
     ("xq_variant", str, "smooth", "xQuAD: smooth | binary"),
+    ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
     ("ips_clip", float, 0.0, "IPS (--train ips): clip the inverse propensity weights at this value (IPS-C); 0: no clip"),
     ("ips_norm", int, 0, "IPS: 1 divides a batch's weighted loss by the sum of its weights instead of the batch size (IPS-CN, with --ips_clip); 0 | 1"),
     ("dice_int_weight", float, 0.1, "DICE (--train dice): weight of the interest loss L_int"),

@@ -28,8 +28,8 @@ import torch
 
 from . import ops
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, BPRMFTempPop, ConditionalBPRMF, Fetch, check_dice, check_ips, check_macr, ips_item_counts,
-                        macr_c_grid)
+from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice, check_ips,
+                        check_lightgcn, check_macr, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -118,7 +118,16 @@ class DatasetApi_Model:
             generator_sampler.with_plan = True
         self.sess = None
         self.testing_model_type, self.testing_popularity = "o", None
-        if args.train in ("s_condition", "condition"):
+        if getattr(args, "model", "mf") == "lightgcn":
+            # the LightGCN backbone: the same two heads on the final tables of the propagated ego tables
+            check_lightgcn(args)
+            if topk_shard is not None:
+                raise NotImplementedError("--model lightgcn with item shards: no item-parallel training or evaluation (the graph is not sharded)")
+            self.input_type = "with_pop" if args.train == "s_condition" else "without_pop"
+            print("dataset api with pop or temp" if args.train == "s_condition" else "dataset api without pop")
+            cls = ConditionalLightGCN if args.train == "s_condition" else LightGCN
+            self.Recommender = cls(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train in ("s_condition", "condition"):
             self.input_type = "with_pop"                                     # :547-549
             print("dataset api with pop or temp")
             self.Recommender = ConditionalBPRMF(args, data_config, use_dataset_api=True, device=self.device)
@@ -478,6 +487,10 @@ def main(argv=None):
     print(os.getcwd())
     configure(argv)
     check_topk_max(args)                   # (refusals before anything is built)
+    if args.model == "lightgcn":
+        check_lightgcn(args)
+    elif args.model != "mf":
+        raise NotImplementedError("--model %s: mf | lightgcn" % args.model)
     if args.train == "dice":
         check_dice(args)
         if args.test not in ("normal", "dice"):
@@ -512,7 +525,10 @@ def main(argv=None):
     linear_predict_popularity = np.power(linear_predict_popularity, popularity_exp)
 
     with_pop = False
-    if args.model == "mf" and args.train in ("normal", "dice", "ips", "macr"):   # :963-970 (DICE and IPS are evaluated like a BPRMF: --test normal)
+    if args.model == "lightgcn":           # the graph's edges reach the model the way ips_item_counts does
+        config["gcn_train_pairs"] = gcn_train_pairs(data.train_user_list)
+        args.saveID += "gcn_layers-{}".format(args.gcn_layers)
+    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr"):   # :963-970 (DICE and IPS are evaluated like a BPRMF: --test normal)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
         print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------", "macr": "-------    running MACR  ----------------"}
               .get(args.train, "-------    running IPS  ----------------"))
@@ -526,7 +542,7 @@ def main(argv=None):
         # the reference masks with the already-powered array (a quirk): kept
         linear_predict_popularity_ori[np.where(linear_predict_popularity <= 0)] = 1e-9
         linear_predict_popularity_ori[np.where(linear_predict_popularity > 1.0)] = 1.0
-    elif args.model == "mf" and args.train == "s_condition":                     # :984-997
+    elif args.model in ("mf", "lightgcn") and args.train == "s_condition":       # :984-997
         print("-------    running PD & PDA model  ----------------")
         args.saveID += "pop_exp-{:.2f} (gamma)".format(popularity_exp)
         print("save_ID", args.saveID)
@@ -538,6 +554,11 @@ def main(argv=None):
         print("   each stage min:", popularity_matrix.min(axis=0))
         data.add_expo_popularity(popularity_matrix)
         with_pop = True
+        if args.test == "normal":          # (--model lightgcn --train s_condition --test normal: the gamma search of the normal branch reads these)
+            last_stage_popualarity_ori = pop_item_all[:, -2]
+            linear_predict_popularity_ori = pop_item_all[:, -2] + 0.5 * (pop_item_all[:, -2] - pop_item_all[:, -3])
+            linear_predict_popularity_ori[np.where(linear_predict_popularity <= 0)] = 1e-9
+            linear_predict_popularity_ori[np.where(linear_predict_popularity > 1.0)] = 1.0
     elif args.model == "mf" and args.train == "temp_pop":                        # :999-1005
         print("-------    running temproal pop MF  ----------------")
         config["temp_num"] = pop_item_all.shape[1] - 1

@@ -421,7 +421,9 @@ int pda_adam_dense_sweep2_f32(float* var_a, float* m_a, float* v_a, float* g_a, 
  *     PRECONDITION (both functions): gU / gI are ZERO on every row whose tag differs from step_tag (true when they are only ever written by
  *     this function: the sweep zeroes what the step wrote).  A caller that accumulates gradients of other rows must tag them, too.
  *     PDA_UPD_USERS_DISTINCT stores the user gradient instead of adding it, so it requires gU to be EXACTLY zero on the batch's rows (and no
- *     user id twice in the batch).  A non-OK return from the step or from the sweep leaves gU / gI dirty: the caller zeroes them before going on.
+ *     user id twice in the batch): the plain store is the row's gradient only then.  A non-OK return from the step or from the sweep -- anything
+ *     between the step's launch and the end of the sweep -- leaves gU / gI and the tags dirty: the caller zeroes them before going on.  (The
+ *     kernels' side of this: pda_amd/csrc/pda_train_common.h.)
  *     The bit-reproducible variant of this step is pda_adam_step_plan_f32 (pda_hip_det.h).
  *   cache_policy: PDA_ADAM_CACHE_AUTO = plain loads / stores while x, m, v of both tables (3 (rows_a + rows_b) d 4 bytes) fit
  *     PDA_ADAM_RESIDENT_BYTES -- they then stay in the 256 MiB Infinity Cache from step to step (C1 / C2: 54 MB) --, non-temporal streams above

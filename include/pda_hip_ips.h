@@ -36,7 +36,10 @@ int pda_ips_weight_sum(const float* ipw, size_t n_users, size_t n_items, const i
  * scales by 0).  The gradients are SUMMED into gU [n_users, d] / gI [n_items, d] (duplicates add up; equal positives inside a workgroup are
  * combined on chip first); the rows touched get tagU[user] = tagI[pos] = tagI[neg] = step_tag, exactly as pda_adam_step_f32 tags them.
  * flags: PDA_UPD_ANY_ORDER (the batch is not grouped by positive) | PDA_UPD_USERS_DISTINCT (no user id occurs twice: its gU row, zero before the
- * call, takes a plain store).  loss_acc (optional) f32 [3] += (loss, mf, reg). */
+ * call, takes a plain store).  loss_acc (optional) f32 [3] += (loss, mf, reg).
+ * PRECONDITION of PDA_UPD_USERS_DISTINCT, as for pda_adam_step_f32 (pda_hip.h): the plain store is the row's gradient only if gU is zero on every
+ * row the batch touches and no user occurs twice.  The sweep of pda_ips_adam_step_f32 zeroes what the step wrote; a non-OK return between the
+ * step and the sweep leaves gU / gI and the tags dirty, and the caller zeroes them before going on. */
 int pda_ips_step_f32(const float* U, const float* I, size_t n_users, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* neg,
                      const float* ipw, const float* wsum, int B, int d, float regs, float reg_div, float* gU, float* gI, int32_t* tagU,
                      int32_t* tagI, int step_tag, int flags, float* loss_acc, void* stream);

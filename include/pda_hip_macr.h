@@ -40,7 +40,10 @@ extern "C" {
  * tagU[user] = tagI[pos] = tagI[neg] = step_tag, exactly as pda_adam_step_f32 tags them.  The gradients of the branch vectors are SUMMED into
  * gW f32 [2, d] (row 0: w_item, row 1: w_user): every workgroup reduces its triplets on chip and adds 2 d values.
  * flags: PDA_UPD_ANY_ORDER (the batch is not grouped by positive) | PDA_UPD_USERS_DISTINCT (no user id occurs twice: its gU row, zero before the
- * call, takes a plain store).  loss_acc (optional) f32 [5] += (loss, L_O, L_I, L_U, reg): L_I and L_U unweighted. */
+ * call, takes a plain store).  loss_acc (optional) f32 [5] += (loss, L_O, L_I, L_U, reg): L_I and L_U unweighted.
+ * PRECONDITION of PDA_UPD_USERS_DISTINCT, as for pda_adam_step_f32 (pda_hip.h): the plain store is the row's gradient only if gU is zero on every
+ * row the batch touches and no user occurs twice.  The sweeps of pda_macr_adam_step_f32 zero what the step wrote; a non-OK return between the
+ * step and the sweeps leaves gU / gI / gW and the tags dirty, and the caller zeroes them before going on. */
 int pda_macr_step_f32(const float* U, const float* I, const float* w_item, const float* w_user, size_t n_users, size_t n_items,
                       const int32_t* users, const int32_t* pos, const int32_t* neg, int B, int d, float alpha, float beta, float regs, float reg_div,
                       float* gU, float* gI, float* gW, int32_t* tagU, int32_t* tagI, int step_tag, int flags, float* loss_acc, void* stream);

@@ -330,17 +330,7 @@ __global__ void __launch_bounds__(512) plan_triplets_kernel(Args a) {
     if (!a.exact) {
         if (e == 0) s_pos[g] = shared_pos ? p : -1 - g;       // (distinct dummies: never equal to each other or to an item)
         __syncthreads();
-        if (shared_pos) {
-            // the first triplet of the workgroup with this positive sums all the workgroup's contributions to it
-            bool leader = true;
-            for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
-            if (leader) {
-                f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-                for (int k = g + 1; k < TPB; ++k)
-                    if (s_pos[k] == p) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-                atomic_add4(ptarget, sum);
-            }
-        }
+        if (shared_pos) pos_scatter_any<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);
     }
     block_loss_reduce(maxi, sq, red);
     if (tid == 0 && (a.loss_acc || a.exact)) {

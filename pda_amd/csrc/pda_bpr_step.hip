@@ -120,7 +120,8 @@ __device__ __forceinline__ void bpr_step_body(const StepArgs& a, const int bid) 
             atomic_add4(a.gI + (size_t)n * D + 4 * e, dne);
             ptarget = a.gI + (size_t)p * D + 4 * e;
         } else if (a.mode == PDA_UPD_DENSE_GRAD) {
-            // (tagged step + distinct users: gU is zero off the rows the sweep clears behind itself, the row has one writer -- a plain store)
+            // (the dense-gradient writes of a tagged step, here with a tag that may be absent: pda_train_common.h has the precondition of the
+            // plain store)
             if (a.tag_u && a.users_distinct && !COH) *reinterpret_cast<f32x4*>(a.gU + (size_t)u * D + 4 * e) = due;
             else atomic_add4(a.gU + (size_t)u * D + 4 * e, due);
             atomic_add4(a.gI + (size_t)n * D + 4 * e, dne);
@@ -140,23 +141,10 @@ __device__ __forceinline__ void bpr_step_body(const StepArgs& a, const int bid) 
     }
     if (e == 0) s_pos[g] = p;
     __syncthreads();
-    if (scatter && active && a.any_order) {
-        // batch in sampling order: the first triplet of the workgroup with this positive sums ALL the workgroup's
-        // contributions to it -- adjacent or not -- and leaves as one atomic per element (hot item: one atomic per
-        // workgroup instead of one per occurrence; 24.8 -> 12.9 us per 2048-triplet step at C2 without any sort)
-        bool leader = true;
-        for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
-        if (leader) {
-            f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-            for (int k = g + 1; k < TPB; ++k)
-                if (s_pos[k] == p) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-            atomic_add4(ptarget, sum);
-        }
-    } else if (scatter && active && (g == 0 || s_pos[g - 1] != p)) {   // grouped batch: first triplet of a run of equal positives
-        f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-        for (int k = g + 1; k < TPB && s_pos[k] == p; ++k) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-        atomic_add4(ptarget, sum);
-    }
+    // batch in sampling order: one atomic per element, workgroup and positive, adjacent or not (hot item: 24.8 -> 12.9 us per 2048-triplet step
+    // at C2 without any sort); grouped batch: one per run of equal positives
+    if (scatter && active && a.any_order) pos_scatter_any<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);
+    else if (scatter && active && pos_run_head(s_pos, g, p)) pos_scatter_run<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);
     block_loss_reduce(maxi, sq, red);
     if (tid == 0 && a.loss_acc) block_loss_add(red, a.inv_B, a.reg_c, a.loss_acc);
 }

@@ -12,6 +12,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
         if (hipGetLastError() != hipSuccess) return PDA_ERR_LAUNCH; \
     } while (0)
 
+// (host) the embedding widths the "d/4 lanes per row" kernels are instantiated for, and table sizes whose row ids fit an int32
+inline bool pda_d_ok(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
+inline bool pda_tables_ok(size_t n_users, size_t n_items) { return n_users != 0 && n_items != 0 && n_users <= 0x7FFFFFFFu && n_items <= 0x7FFFFFFFu; }
+
+// (host) the launch of a training step kernel KERNEL<W>, W the row width in floats: 512 threads, W/4 lanes per triplet, so 512 / (W/4) triplets per
+// workgroup and grid = ceil(B / that).  PDA_STEP_LAUNCH dispatches on a width the caller has checked with pda_d_ok.
+#define PDA_STEP_LAUNCH_W(KERNEL, WW, B, STREAM, ARGS) \
+    hipLaunchKernelGGL(KERNEL<WW>, dim3((unsigned)(((B) + 512 / (WW / 4) - 1) / (512 / (WW / 4)))), dim3(512), 0, STREAM, ARGS)
+#define PDA_STEP_LAUNCH(KERNEL, W, B, STREAM, ARGS)                       \
+    switch (W) {                                                          \
+        case 32: PDA_STEP_LAUNCH_W(KERNEL, 32, B, STREAM, ARGS); break;   \
+        case 64: PDA_STEP_LAUNCH_W(KERNEL, 64, B, STREAM, ARGS); break;   \
+        case 128: PDA_STEP_LAUNCH_W(KERNEL, 128, B, STREAM, ARGS); break; \
+        default: PDA_STEP_LAUNCH_W(KERNEL, 256, B, STREAM, ARGS); break;  \
+    }
+
 // Monotone float -> uint32 map (larger float => larger uint); -0.0 is canonicalised by the caller.
 __device__ __forceinline__ uint32_t pda_ordf(float v) {
     uint32_t u = __float_as_uint(v);

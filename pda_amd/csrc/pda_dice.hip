@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(512) dice_step_kernel(DiceStepArgs a) {
     bool active = t < a.B;
     if (active) {
         u = a.users[t], p = a.pos[t], n = a.neg[t];
-        active = (unsigned)u < a.n_users && (unsigned)p < a.n_items && (unsigned)n < a.n_items;
+        active = triplet_ids_ok(u, p, n, a.n_users, a.n_items);
         if (!active) p = -1;
     }
     if (active) {
@@ -100,17 +100,7 @@ __global__ void __launch_bounds__(512) dice_step_kernel(DiceStepArgs a) {
     if (e == 0) s_pos[g] = p;
     __syncthreads();
     if (tid < 2) s_base[tid] = s_n[tid] > 0 ? atomicAdd(&a.ws[tid], s_n[tid]) : 0;
-    if (active) {
-        // the first triplet of the workgroup with this positive sums all the workgroup's contributions to its row
-        bool leader = true;
-        for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
-        if (leader) {
-            f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * W + 4 * e);
-            for (int k = g + 1; k < TPB; ++k)
-                if (s_pos[k] == p) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * W + 4 * e);
-            atomic_add4(a.gI + (size_t)p * W + 4 * e, sum);
-        }
-    }
+    if (active) pos_scatter_any<W, TPB>(s_pos, s_dpe, g, e, p, a.gI + (size_t)p * W + 4 * e);
     block_loss_reduce(l_click, sq, red);
     block_loss_reduce(l_int, l_con, red2);      // (its barrier also publishes s_base)
     // distinct users <= B and distinct items <= 2 B: the lists cannot overflow (the counters start at zero in every call)
@@ -280,7 +270,7 @@ __global__ void __launch_bounds__(64) dice_sample_kernel(DiceSampleArgs a) {
     a.mask[r] = whole ? (uint8_t)(a.pop[n] > a.pop[p]) : (uint8_t)fromH;
 }
 
-bool d_ok(int d) { return d == 32 || d == 64 || d == 128; }
+bool dice_d_ok(int d) { return d == 32 || d == 64 || d == 128; }       // (the width of ONE embedding: rows of 2 d floats)
 
 int launch_sample(const DiceSampleArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(dice_sample_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
@@ -297,22 +287,16 @@ extern "C" int pda_dice_step_f32(const float* U, const float* I, size_t n_users,
                                  float* gU, float* gI, int32_t* tagU, int32_t* tagI, int step_tag, int32_t* rows_ws, float* loss_acc,
                                  void* stream) {
     if (!U || !I || !users || !pos || !neg || !mask || !gU || !gI || !tagU || !tagI || !rows_ws) return PDA_ERR_ARG;
-    if (B <= 0 || B > (1 << 28) || reg_div <= 0.f || step_tag <= 0 || n_users == 0 || n_items == 0 || n_users > 0x7FFFFFFFu ||
-        n_items > 0x7FFFFFFFu)
-        return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (B <= 0 || B > (1 << 28) || reg_div <= 0.f || step_tag <= 0 || !pda_tables_ok(n_users, n_items)) return PDA_ERR_ARG;
+    if (!dice_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (hipMemsetAsync(rows_ws, 0, kWsHead * sizeof(int32_t), s) != hipSuccess) return PDA_ERR_LAUNCH;
     DiceStepArgs a{U, I, users, pos, neg, mask, gU, gI, tagU, tagI, rows_ws, loss_acc, (unsigned)n_users, (unsigned)n_items, step_tag, B,
                    1.0f / (float)B, regs / reg_div, w_int, w_con};
-    switch (d) {
-#define PDA_DICE_STEP(WW)                                                                                                        \
-    hipLaunchKernelGGL(dice_step_kernel<WW>, dim3((unsigned)((B + 512 / (WW / 4) - 1) / (512 / (WW / 4)))), dim3(512), 0, s, a); \
-    break;
-        case 32: PDA_DICE_STEP(64)
-        case 64: PDA_DICE_STEP(128)
-        default: PDA_DICE_STEP(256)
-#undef PDA_DICE_STEP
+    switch (d) {        // (rows of 2 d floats; no width 32)
+        case 32: PDA_STEP_LAUNCH_W(dice_step_kernel, 64, B, s, a); break;
+        case 64: PDA_STEP_LAUNCH_W(dice_step_kernel, 128, B, s, a); break;
+        default: PDA_STEP_LAUNCH_W(dice_step_kernel, 256, B, s, a); break;
     }
     PDA_CHECK_LAUNCH();
     return PDA_OK;
@@ -321,9 +305,9 @@ extern "C" int pda_dice_step_f32(const float* U, const float* I, size_t n_users,
 extern "C" int pda_dice_dis_f32(const float* U, const float* I, size_t n_users, size_t n_items, int B, int d, int dis_kind, float dis_pen,
                                 float* gU, float* gI, const int32_t* rows_ws, float* loss_acc, void* stream) {
     if (!U || !I || !gU || !gI || !rows_ws || B <= 0 || B > (1 << 28)) return PDA_ERR_ARG;
-    if (n_users == 0 || n_items == 0 || n_users > 0x7FFFFFFFu || n_items > 0x7FFFFFFFu) return PDA_ERR_ARG;
+    if (!pda_tables_ok(n_users, n_items)) return PDA_ERR_ARG;
     if (dis_kind != PDA_DICE_DIS_L1 && dis_kind != PDA_DICE_DIS_L2) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!dice_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DiceDisArgs a{U, I, gU, gI, rows_ws, loss_acc, (unsigned)n_users, (unsigned)n_items, B, dis_kind == PDA_DICE_DIS_L2 ? 1 : 0, dis_pen};
     // a thread per float4 pair of the 3 B rows the lists can hold, at most 2 048 workgroups (grid-stride beyond)

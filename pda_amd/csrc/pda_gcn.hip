@@ -137,12 +137,10 @@ __global__ __launch_bounds__(512) void gcn_reg_kernel(GcnRegArgs a) {
     }
 }
 
-bool d_ok(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
-
 }  // namespace
 
 extern "C" size_t pda_gcn_spmm_workspace_bytes(size_t n_slots, int d) {
-    if (!d_ok(d)) return 0;
+    if (!pda_d_ok(d)) return 0;
     return n_slots * (size_t)d * sizeof(float);
 }
 
@@ -157,7 +155,7 @@ extern "C" int pda_gcn_spmm_f32(const int64_t* indptr, const int32_t* indices, c
     if (!std::isfinite(scale)) return PDA_ERR_ARG;
     if (n_long > n_rows || (n_long != 0 && (!long_rows || n_slots < 2 * n_long)) || (n_long == 0 && n_slots != 0)) return PDA_ERR_ARG;
     if (n_work != n_rows - n_long + n_slots) return PDA_ERR_ARG;      // one entry per whole row, one per chunk of a cut row
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     if (n_slots != 0 && (!workspace || workspace_bytes < pda_gcn_spmm_workspace_bytes(n_slots, d))) return PDA_ERR_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const GcnSpmmArgs a{indptr, indices, w, work, long_rows, X, add, Y, sum_in, sum_out, reinterpret_cast<float*>(workspace), n_work, n_long, scale};
@@ -181,8 +179,8 @@ extern "C" int pda_gcn_reg_f32(const float* U0, const float* I0, size_t n_users,
                                const int32_t* neg, int B, int d, float regs, float reg_div, float* gU, float* gI, float* loss_acc, void* stream) {
     if (!U0 || !I0 || !users || !pos || !neg || !gU || !gI) return PDA_ERR_ARG;
     if (B <= 0 || B > (1 << 28) || !(reg_div > 0.f) || !std::isfinite(regs)) return PDA_ERR_ARG;
-    if (n_users == 0 || n_items == 0 || n_users > 0x7FFFFFFFu || n_items > 0x7FFFFFFFu) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_tables_ok(n_users, n_items)) return PDA_ERR_ARG;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const GcnRegArgs a{U0, I0, users, pos, neg, gU, gI, loss_acc, (unsigned)n_users, (unsigned)n_items, B, regs / reg_div};
     switch (d) {

@@ -5,7 +5,7 @@
 // Step layout: the one of pda_bpr_step.hip -- d/4 lanes per triplet, each lane owns one float4 of the three gathered rows, the dots by the
 // xor-shuffle ladder of triplet_dots.  The only new traffic is one 4-byte gather per triplet (ipw[pos]) and, self-normalised, one uniform load
 // of S.  Equal positives inside a workgroup are summed by their first triplet through LDS, as there (they carry the same weight: a hot item is
-// still one atomic per element and workgroup).  A kernel of its own: the step kernels of pda_bpr_step.hip are not touched.
+// still one atomic per element and workgroup).  A kernel of its own, on the helpers every step kernel shares (pda_train_common.h).
 #include <cmath>
 #include <cstdlib>
 #include "pda_common.h"
@@ -36,10 +36,6 @@ struct IpsStepArgs {
     int users_distinct;     // PDA_UPD_USERS_DISTINCT
 };
 
-__device__ __forceinline__ bool ips_valid(int u, int p, int n, unsigned n_users, unsigned n_items) {
-    return (unsigned)u < n_users && (unsigned)p < n_items && (unsigned)n < n_items;
-}
-
 // One workgroup of 1 024 threads.  float64 partial sums: the one rounding to fp32 at the end keeps the result within an ulp of the exact sum
 // whatever the weights, and a fixed order (thread: t = tid, tid + 1024, ...; wave: xor ladder; workgroup: waves 0 .. 15) keeps its bits.
 __global__ void __launch_bounds__(1024) ips_weight_sum_kernel(const float* __restrict__ ipw, const int32_t* __restrict__ users,
@@ -49,7 +45,7 @@ __global__ void __launch_bounds__(1024) ips_weight_sum_kernel(const float* __res
     double acc = 0.0;
     for (int t = (int)threadIdx.x; t < B; t += 1024) {
         const int u = users[t], p = pos[t], n = neg[t];
-        if (ips_valid(u, p, n, n_users, n_items)) acc += (double)ipw[p];
+        if (triplet_ids_ok(u, p, n, n_users, n_items)) acc += (double)ipw[p];
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
@@ -85,7 +81,7 @@ __global__ void __launch_bounds__(512) ips_step_kernel(IpsStepArgs a) {
     bool active = t < a.B;
     if (active) {
         u = a.users[t], p = a.pos[t], n = a.neg[t];
-        active = ips_valid(u, p, n, a.n_users, a.n_items);
+        active = triplet_ids_ok(u, p, n, a.n_users, a.n_items);
         if (!active) p = -1;
     }
     float* ptarget = nullptr;
@@ -101,7 +97,7 @@ __global__ void __launch_bounds__(512) ips_step_kernel(IpsStepArgs a) {
         sq = triplet_sq(ue, pe, ne);
         f32x4 due, dpe, dne;
         triplet_row_grads(ue, pe, ne, gg, gg, a.reg_c, due, dpe, dne);
-        // (distinct users: gU is zero off the rows the sweep clears behind itself, the row has one writer -- a plain store)
+        // (the dense-gradient writes of a tagged step: pda_train_common.h has the precondition of the plain store)
         if (a.users_distinct) *reinterpret_cast<f32x4*>(a.gU + (size_t)u * D + 4 * e) = due;
         else atomic_add4(a.gU + (size_t)u * D + 4 * e, due);
         atomic_add4(a.gI + (size_t)n * D + 4 * e, dne);
@@ -115,28 +111,11 @@ __global__ void __launch_bounds__(512) ips_step_kernel(IpsStepArgs a) {
     }
     if (e == 0) s_pos[g] = p;
     __syncthreads();
-    if (active && a.any_order) {
-        // the first triplet of the workgroup with this positive sums all the workgroup's contributions to its row
-        bool leader = true;
-        for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
-        if (leader) {
-            f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-            for (int k = g + 1; k < TPB; ++k)
-                if (s_pos[k] == p) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-            atomic_add4(ptarget, sum);
-        }
-    } else if (active && (g == 0 || s_pos[g - 1] != p)) {       // grouped batch: the first triplet of a run of equal positives
-        f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-        for (int k = g + 1; k < TPB && s_pos[k] == p; ++k) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-        atomic_add4(ptarget, sum);
-    }
+    if (active && a.any_order) pos_scatter_any<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);
+    else if (active && pos_run_head(s_pos, g, p)) pos_scatter_run<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);     // (grouped batch)
     block_loss_reduce(maxi, sq, red);
     if (tid == 0 && a.loss_acc) block_loss_add(red, 1.f, a.reg_c, a.loss_acc);     // (maxi carries its weight and scale already)
 }
-
-bool d_ok(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
-
-bool tables_ok(size_t n_users, size_t n_items) { return n_users != 0 && n_items != 0 && n_users <= 0x7FFFFFFFu && n_items <= 0x7FFFFFFFu; }
 
 // (arguments checked by the callers)
 int launch_weight_sum(const float* ipw, size_t n_users, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* neg, int B,
@@ -147,16 +126,7 @@ int launch_weight_sum(const float* ipw, size_t n_users, size_t n_items, const in
 }
 
 int launch_step(const IpsStepArgs& a, int d, hipStream_t s) {
-    switch (d) {
-#define PDA_IPS_STEP(DD)                                                                                                              \
-    hipLaunchKernelGGL(ips_step_kernel<DD>, dim3((unsigned)((a.B + 512 / (DD / 4) - 1) / (512 / (DD / 4)))), dim3(512), 0, s, a); \
-    break;
-        case 32: PDA_IPS_STEP(32)
-        case 64: PDA_IPS_STEP(64)
-        case 128: PDA_IPS_STEP(128)
-        default: PDA_IPS_STEP(256)
-#undef PDA_IPS_STEP
-    }
+    PDA_STEP_LAUNCH(ips_step_kernel, d, a.B, s, a)
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
@@ -165,9 +135,9 @@ int check_step(const float* U, const float* I, size_t n_users, size_t n_items, c
                const float* ipw, int B, int d, float reg_div, const float* gU, const float* gI, const int32_t* tagU, const int32_t* tagI,
                int step_tag, int flags) {
     if (!U || !I || !users || !pos || !neg || !ipw || !gU || !gI || !tagU || !tagI) return PDA_ERR_ARG;
-    if (B <= 0 || B > (1 << 28) || !(reg_div > 0.f) || step_tag <= 0 || !tables_ok(n_users, n_items)) return PDA_ERR_ARG;
+    if (B <= 0 || B > (1 << 28) || !(reg_div > 0.f) || step_tag <= 0 || !pda_tables_ok(n_users, n_items)) return PDA_ERR_ARG;
     if (flags & ~(PDA_UPD_ANY_ORDER | PDA_UPD_USERS_DISTINCT)) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     return PDA_OK;
 }
 
@@ -182,7 +152,7 @@ IpsStepArgs step_args(const float* U, const float* I, size_t n_users, size_t n_i
 
 extern "C" int pda_ips_weight_sum(const float* ipw, size_t n_users, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* neg,
                                   int B, float* wsum, void* stream) {
-    if (!ipw || !users || !pos || !neg || !wsum || B <= 0 || B > (1 << 28) || !tables_ok(n_users, n_items)) return PDA_ERR_ARG;
+    if (!ipw || !users || !pos || !neg || !wsum || B <= 0 || B > (1 << 28) || !pda_tables_ok(n_users, n_items)) return PDA_ERR_ARG;
     return launch_weight_sum(ipw, n_users, n_items, users, pos, neg, B, wsum, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -6,7 +6,7 @@
 // branch vectors (two 16-byte loads per thread, the same 2 d floats for every triplet: they stay in the caches and then in registers).  The
 // three branch dots ride the xor-shuffle ladder beside triplet_dots.  Equal positives inside a workgroup are summed by their first triplet
 // through LDS, as there.  The branch gradients are reduced inside the workgroup -- the triplets of a wave by shuffles, the eight waves through
-// LDS -- and leave it as 2 d atomics.  A kernel of its own: the step kernels of pda_bpr_step.hip are not touched.
+// LDS -- and leave it as 2 d atomics.  A kernel of its own, on the helpers every step kernel shares (pda_train_common.h).
 #include <cmath>
 #include <cstdlib>
 #include "pda_common.h"
@@ -39,10 +39,6 @@ struct MacrStepArgs {
     int any_order;          // PDA_UPD_ANY_ORDER
     int users_distinct;     // PDA_UPD_USERS_DISTINCT
 };
-
-__device__ __forceinline__ bool macr_valid(int u, int p, int n, unsigned n_users, unsigned n_items) {
-    return (unsigned)u < n_users && (unsigned)p < n_items && (unsigned)n < n_items;
-}
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -84,7 +80,7 @@ __global__ void __launch_bounds__(512) macr_step_kernel(MacrStepArgs a) {
     bool active = t < a.B;
     if (active) {
         u = a.users[t], p = a.pos[t], n = a.neg[t];
-        active = macr_valid(u, p, n, a.n_users, a.n_items);
+        active = triplet_ids_ok(u, p, n, a.n_users, a.n_items);
         if (!active) p = -1;
     }
     float* ptarget = nullptr;
@@ -121,7 +117,7 @@ __global__ void __launch_bounds__(512) macr_step_kernel(MacrStepArgs a) {
         dne += hn * wi;
         gwi = hp * pe + hn * ne;
         gwu = hu * ue;
-        // (distinct users: gU is zero off the rows the sweep clears behind itself, the row has one writer -- a plain store)
+        // (the dense-gradient writes of a tagged step: pda_train_common.h has the precondition of the plain store)
         if (a.users_distinct) *reinterpret_cast<f32x4*>(a.gU + (size_t)u * D + 4 * e) = due;
         else atomic_add4(a.gU + (size_t)u * D + 4 * e, due);
         atomic_add4(a.gI + (size_t)n * D + 4 * e, dne);
@@ -148,21 +144,8 @@ __global__ void __launch_bounds__(512) macr_step_kernel(MacrStepArgs a) {
         *reinterpret_cast<f32x4*>(&s_gw[tid >> 6][D + 4 * e]) = gwu;
     }
     __syncthreads();
-    if (active && a.any_order) {
-        // the first triplet of the workgroup with this positive sums all the workgroup's contributions to its row
-        bool leader = true;
-        for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
-        if (leader) {
-            f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-            for (int k = g + 1; k < TPB; ++k)
-                if (s_pos[k] == p) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-            atomic_add4(ptarget, sum);
-        }
-    } else if (active && (g == 0 || s_pos[g - 1] != p)) {       // grouped batch: the first triplet of a run of equal positives
-        f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * D + 4 * e);
-        for (int k = g + 1; k < TPB && s_pos[k] == p; ++k) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * D + 4 * e);
-        atomic_add4(ptarget, sum);
-    }
+    if (active && a.any_order) pos_scatter_any<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);
+    else if (active && pos_run_head(s_pos, g, p)) pos_scatter_run<D, TPB>(s_pos, s_dpe, g, e, p, ptarget);     // (grouped batch)
     // the workgroup's 2 d branch gradients: waves 0 .. 7 in order, one atomic per element (a wave of L == 64 lanes holds one triplet, so
     // with D == 256 every wave wrote its row; below, too -- every wave has lanes < L)
     if (tid < 2 * D) {
@@ -218,21 +201,8 @@ __global__ void __launch_bounds__(256) macr_item_bias_kernel(const float* __rest
     if (i < n) beta[i] = neg_c * sig[i];
 }
 
-bool d_ok(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
-
-bool tables_ok(size_t n_users, size_t n_items) { return n_users != 0 && n_items != 0 && n_users <= 0x7FFFFFFFu && n_items <= 0x7FFFFFFFu; }
-
 int launch_step(const MacrStepArgs& a, int d, hipStream_t s) {
-    switch (d) {
-#define PDA_MACR_STEP(DD)                                                                                                              \
-    hipLaunchKernelGGL(macr_step_kernel<DD>, dim3((unsigned)((a.B + 512 / (DD / 4) - 1) / (512 / (DD / 4)))), dim3(512), 0, s, a); \
-    break;
-        case 32: PDA_MACR_STEP(32)
-        case 64: PDA_MACR_STEP(64)
-        case 128: PDA_MACR_STEP(128)
-        default: PDA_MACR_STEP(256)
-#undef PDA_MACR_STEP
-    }
+    PDA_STEP_LAUNCH(macr_step_kernel, d, a.B, s, a)
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
@@ -241,10 +211,10 @@ int check_step(const float* U, const float* I, const float* w_item, const float*
                const int32_t* pos, const int32_t* neg, int B, int d, float alpha, float beta, float reg_div, const float* gU, const float* gI,
                const float* gW, const int32_t* tagU, const int32_t* tagI, int step_tag, int flags) {
     if (!U || !I || !w_item || !w_user || !users || !pos || !neg || !gU || !gI || !gW || !tagU || !tagI) return PDA_ERR_ARG;
-    if (B <= 0 || B > (1 << 28) || !(reg_div > 0.f) || step_tag <= 0 || !tables_ok(n_users, n_items)) return PDA_ERR_ARG;
+    if (B <= 0 || B > (1 << 28) || !(reg_div > 0.f) || step_tag <= 0 || !pda_tables_ok(n_users, n_items)) return PDA_ERR_ARG;
     if (!std::isfinite(alpha) || !std::isfinite(beta)) return PDA_ERR_ARG;
     if (flags & ~(PDA_UPD_ANY_ORDER | PDA_UPD_USERS_DISTINCT)) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     return PDA_OK;
 }
 
@@ -292,7 +262,7 @@ extern "C" int pda_macr_adam_step_f32(float* U, float* mU, float* vU, float* gU,
 
 extern "C" int pda_macr_item_prep_f32(const float* I, const float* w_item, size_t n_items, int d, float* sig, float* J, void* stream) {
     if (!I || !w_item || !sig || !J || n_items == 0 || n_items > 0x7FFFFFFFu) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (d) {
 #define PDA_MACR_PREP(DD)                                                                                                                   \

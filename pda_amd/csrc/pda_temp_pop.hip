@@ -96,7 +96,8 @@ __global__ void __launch_bounds__(512) temp_pop_step_kernel(TPStepArgs a) {
     if (e == 0) s_pos[g] = p;
     __syncthreads();
     if (active) {
-        // the first triplet of the workgroup with this positive sums all the workgroup's contributions to its row and to C[p, T]
+        // the first triplet of the workgroup with this positive sums all the workgroup's contributions to its row and to C[p, T]: pos_scatter_any
+        // (pda_train_common.h) with the second LDS array summed in the same loop
         bool leader = true;
         for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
         if (leader) {
@@ -169,19 +170,8 @@ __global__ void __launch_bounds__(256) temp_pop_sweep_kernel(TPSweepArgs a) {
 }
 
 int launch_temp_pop_step(const TPStepArgs& a, int d, hipStream_t s) {
-    switch (d) {
-#define PDA_TP_STEP(DD)                                                                                                       \
-    case DD:                                                                                                                  \
-        hipLaunchKernelGGL(temp_pop_step_kernel<DD>, dim3((unsigned)((a.B + 512 / (DD / 4) - 1) / (512 / (DD / 4)))), dim3(512), 0, s, a); \
-        break;
-        PDA_TP_STEP(32)
-        PDA_TP_STEP(64)
-        PDA_TP_STEP(128)
-        PDA_TP_STEP(256)
-#undef PDA_TP_STEP
-        default:
-            return PDA_ERR_UNSUPPORTED;
-    }
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    PDA_STEP_LAUNCH(temp_pop_step_kernel, d, a.B, s, a)
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
@@ -207,8 +197,6 @@ int launch_temp_pop_sweep(TPSweepArgs& a, hipStream_t s) {
     return PDA_OK;
 }
 
-bool d_ok(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
-
 }  // namespace
 
 extern "C" int pda_temp_pop_step_f32(const float* U, const float* I, const float* bu, const float* C, const int32_t* users, const int32_t* pos,
@@ -216,7 +204,7 @@ extern "C" int pda_temp_pop_step_f32(const float* U, const float* I, const float
                                      float* gbu, float* gC, int32_t* tagU, int32_t* tagI, int step_tag, float* loss_acc, void* stream) {
     if (!U || !I || !bu || !C || !users || !pos || !neg || !temps || !gU || !gI || !gbu || !gC || !tagU || !tagI) return PDA_ERR_ARG;
     if (B <= 0 || T < 1 || reg_div <= 0.f || step_tag <= 0) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     TPStepArgs a{U, I, bu, C, users, pos, neg, temps, gU, gI, gbu, gC, tagU, tagI, loss_acc, step_tag, B, T, 1.0f / (float)B, regs / reg_div};
     return launch_temp_pop_step(a, d, reinterpret_cast<hipStream_t>(stream));
 }
@@ -227,7 +215,7 @@ extern "C" int pda_temp_pop_sweep_f32(float* U, float* mU, float* vU, float* gU,
     if (!U || !mU || !vU || !gU || !tagU || !I || !mI || !vI || !gI || !tagI || !bu || !mbu || !vbu || !gbu || !C || !mC || !vC || !gC)
         return PDA_ERR_ARG;
     if (n_users == 0 || n_items == 0 || T < 1 || step_tag <= 0) return PDA_ERR_ARG;
-    if (!d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (!pda_d_ok(d)) return PDA_ERR_UNSUPPORTED;
     TPSweepArgs a{{U, I, bu, C}, {mU, mI, mbu, mC}, {vU, vI, vbu, vC}, {gU, gI, gbu, gC}, {tagU, tagI, tagU, tagI},
                   {n_users * (size_t)(d / 4), n_items * (size_t)(d / 4), n_users, n_items * (size_t)(T + 1)}, {d / 4, d / 4, 1, T + 1},
                   {0u, 0u, 0u, 0u}, step_tag, lr_t, beta1, beta2, eps};

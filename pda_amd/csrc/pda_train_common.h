@@ -1,7 +1,9 @@
-// The arithmetic every training kernel shares (pda_bpr_step.hip, pda_bpr_plan.hip, pda_temp_pop.hip): the triplet forward / backward of the
-// reference model, the block reduction of the loss, and the TF-1.14 Adam element update.  One definition each: the bit-identity of the sweeps,
-// the lazy replay, --deterministic and the checkpoints (tests/test_gpu_bpr_step.py, test_gpu_deterministic.py, test_gpu_temp_pop.py) holds
-// because every kernel compiles THESE expressions, in this order, under -ffp-contract=off.
+// What every training step kernel shares (pda_bpr_step.hip, pda_bpr_plan.hip, pda_temp_pop.hip, pda_dice.hip, pda_ips.hip, pda_macr.hip; pda_gcn.hip
+// takes the loss reduction).  The arithmetic: the triplet forward / backward of the reference model, the block reduction of the loss, and the TF-1.14
+// Adam element update.  Around it: the id test of a triplet, the precondition of the dense-gradient writes of a tagged step, and the scatter of the
+// positives' gradients through LDS.  One definition each: the bit-identity of the sweeps, the lazy replay, --deterministic and the checkpoints
+// (tests/test_gpu_bpr_step.py, test_gpu_deterministic.py, test_gpu_temp_pop.py) holds because every kernel compiles THESE expressions, in this
+// order, under -ffp-contract=off.
 #pragma once
 #include "pda_common.h"
 
@@ -87,6 +89,50 @@ __device__ __forceinline__ void bpr_triplet(f32x4 ue, f32x4 pe, f32x4 ne, const 
     sq = triplet_sq(ue, pe, ne);      // (behind the score chain: nothing waits for it before the block reduction)
     gp = gg * ap, gn = gg * an;
     triplet_row_grads(ue, pe, ne, gp, gn, reg_c, due, dpe, dne);
+}
+
+// ---- around the arithmetic: which triplets count, and where their gradients go -------------------------------------------------------------------
+// a triplet whose ids lie outside the tables is skipped (memory safety when the host check is off): it reads and writes nothing
+__device__ __forceinline__ bool triplet_ids_ok(int u, int p, int n, unsigned n_users, unsigned n_items) {
+    return (unsigned)u < n_users && (unsigned)p < n_items && (unsigned)n < n_items;
+}
+
+// The dense-gradient writes of a tagged step (pda_ips.hip, pda_macr.hip, the PDA_UPD_DENSE_GRAD branch of pda_bpr_step.hip): the user row of gU by
+// a plain store under users_distinct and by atomics otherwise, the negative's row of gI by atomics, and the step's tag on the three rows by lane 0
+// (the same value from every writer of a row: plain stores).  The three kernels keep these ten lines: as a helper -- one of W, the pointers and
+// the flag, one of the argument block, or split in two -- the IPS and MACR kernels kept three more addresses in registers (43 -> 46, 60 -> 64
+// VGPRs, five instructions fewer) and ran 0.3 us per step slower (profiles/step_scatter_timing.txt).
+// PRECONDITION of users_distinct (PDA_UPD_USERS_DISTINCT): the PLAIN STORE is the row's gradient only if gU is zero on every row the batch touches
+// and no user occurs twice in the batch.  The sweep behind the step clears the tagged rows of g, so the condition holds from one whole step to
+// the next; a call that returns anything but PDA_OK between the step and the sweep leaves g and the tags dirty, and the caller has to zero them
+// before the next step (include/pda_hip.h, pda_adam_step_f32).  Without the flag the row takes atomics and needs neither.
+
+// The positives' gradients go through LDS first: positive items are popularity-skewed, one batch holds the hottest item ~170 times, and that many
+// float atomics on the same cache lines serialise in L2 (24.8 -> 12.9 us per 2048-triplet step, pda_bpr_step.hip).  The caller has written, for
+// every triplet g of the workgroup (TPB of them, W/4 lanes each, lane e owns floats [4 e, 4 e + 4) of a row of W), s_pos[g] -- the positive, -1 for a
+// refused or inactive triplet, a distinct dummy where the row does not take part -- and s_dpe[g W ..] for the triplets that do, and passed its own
+// barrier.  A triplet that takes part calls ONE of the two with its own p (never a dummy) and the address of its float4 in the target row.  The
+// order of the sum -- the triplet's own contribution, then ascending k -- is part of the bit-identity contract.
+// Any batch order: the first triplet of the workgroup with this positive sums ALL the workgroup's contributions, adjacent or not: one atomic_add4.
+template <int W, int TPB>
+__device__ __forceinline__ void pos_scatter_any(const int* s_pos, const float* s_dpe, int g, int e, int p, float* target) {
+    bool leader = true;
+    for (int k = 0; k < g; ++k) leader = leader && (s_pos[k] != p);
+    if (leader) {
+        f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * W + 4 * e);
+        for (int k = g + 1; k < TPB; ++k)
+            if (s_pos[k] == p) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * W + 4 * e);
+        atomic_add4(target, sum);
+    }
+}
+// Grouped batch (equal positives adjacent): is triplet g the first of a run of equal positives? ...
+__device__ __forceinline__ bool pos_run_head(const int* s_pos, int g, int p) { return g == 0 || s_pos[g - 1] != p; }
+// ... then it sums the run: a refused triplet (-1) inside a run ends it, and the triplet behind it heads the next one.
+template <int W, int TPB>
+__device__ __forceinline__ void pos_scatter_run(const int* s_pos, const float* s_dpe, int g, int e, int p, float* target) {
+    f32x4 sum = *reinterpret_cast<const f32x4*>(s_dpe + g * W + 4 * e);
+    for (int k = g + 1; k < TPB && s_pos[k] == p; ++k) sum += *reinterpret_cast<const f32x4*>(s_dpe + k * W + 4 * e);
+    atomic_add4(target, sum);
 }
 
 // ---- block reduction of sum(log(.)) and of the squared norms (512 threads = 8 waves; red: a __shared__ float[2][8] of the calling kernel) -----

@@ -2040,6 +2040,33 @@ def xquad_rerank(cand_idx, cand_val, item_is_head, lam, K=50, variant="smooth", 
     return idx, val
 
 
+# ---- what the checks of the tagged step kernels (DICE, IPS, MACR) repeat ---------------------------------------------------------------------
+def _triplet_shapes(method: str, tables: str, sizes, U, I, users, pos, neg, *, halves: int = 1, width_note: str = "", mask=None):
+    """fp32 2-D tables of equal width (rows of `halves` embeddings of d floats), d in `sizes`, int32 users/pos/neg (and a uint8 mask, where given)
+    of one non-zero length -> (d, B).  `method` stands in front of the messages, `tables` describes the tables."""
+    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
+    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1] or U.shape[1] % halves:
+        raise ValueError(f"{method} tables: {tables}")
+    d = U.shape[1] // halves
+    if d not in sizes:
+        raise ValueError(f"{method}: the embedding width d must be one of {sizes}{width_note}, got {d}")
+    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
+    names, lens = "users/pos/neg", (pos.numel(), neg.numel())
+    if mask is not None:
+        names, lens = names + "/mask", lens + (_need(mask, torch.uint8, "mask").numel(),)
+    B = users.numel()
+    if B < 1 or any(n != B for n in lens):
+        raise ValueError(f"{names} must have the same, non-zero length")
+    return d, B
+
+
+def _triplet_ids(method: str, U, I, users, pos, neg, check_ids: bool):
+    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
+        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
+        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
+            raise ValueError(f"{method} batch: a user or item id lies outside the tables")
+
+
 # ---- DICE (include/pda_hip_dice.h) ------------------------------------------------------------------------------------------------------
 DICE_EMBED_SIZES = (32, 64, 128)          # d, the width of ONE embedding: the tables' rows are 2 d wide
 DICE_DIS_KINDS = {"l1": _lib.DICE_DIS_L1, "l2": _lib.DICE_DIS_L2}
@@ -2067,21 +2094,9 @@ class DiceState:
 
 
 def _dice_check(U, I, users, pos, neg, mask, check_ids: bool):
-    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
-    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1] or U.shape[1] % 2:
-        raise ValueError("DICE tables: U [n_users, 2d] and I [n_items, 2d] (interest columns, then conformity columns)")
-    d = U.shape[1] // 2
-    if d not in DICE_EMBED_SIZES:
-        raise ValueError(f"DICE: the embedding width d must be one of {DICE_EMBED_SIZES} (rows of 2d floats), got {d}")
-    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
-    mask = _need(mask, torch.uint8, "mask")
-    B = users.numel()
-    if B < 1 or pos.numel() != B or neg.numel() != B or mask.numel() != B:
-        raise ValueError("users/pos/neg/mask must have the same, non-zero length")
-    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
-        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
-        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
-            raise ValueError("DICE batch: a user or item id lies outside the tables")
+    d, B = _triplet_shapes("DICE", "U [n_users, 2d] and I [n_items, 2d] (interest columns, then conformity columns)", DICE_EMBED_SIZES, U, I, users,
+                           pos, neg, halves=2, width_note=" (rows of 2d floats)", mask=mask)
+    _triplet_ids("DICE", U, I, users, pos, neg, check_ids)
     return d, B
 
 
@@ -2225,16 +2240,7 @@ class IpsWeights:
 
 
 def _ips_check(U, I, users, pos, neg, ipw, tagU, tagI, wsum, loss_acc, check_ids: bool):
-    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
-    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1]:
-        raise ValueError("IPS tables: U [n_users, d] and I [n_items, d]")
-    d = U.shape[1]
-    if d not in IPS_EMBED_SIZES:
-        raise ValueError(f"IPS: the embedding width d must be one of {IPS_EMBED_SIZES}, got {d}")
-    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
-    B = users.numel()
-    if B < 1 or pos.numel() != B or neg.numel() != B:
-        raise ValueError("users/pos/neg must have the same, non-zero length")
+    d, B = _triplet_shapes("IPS", "U [n_users, d] and I [n_items, d]", IPS_EMBED_SIZES, U, I, users, pos, neg)
     if _need(ipw, torch.float32, "ipw").numel() != I.shape[0]:
         raise ValueError("ipw holds one float32 per item")
     if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
@@ -2243,10 +2249,7 @@ def _ips_check(U, I, users, pos, neg, ipw, tagU, tagI, wsum, loss_acc, check_ids
         raise ValueError("wsum holds one float32")
     if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
         raise ValueError("IPS loss_acc holds three float32")
-    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
-        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
-        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
-            raise ValueError("IPS batch: a user or item id lies outside the tables")
+    _triplet_ids("IPS", U, I, users, pos, neg, check_ids)
     return d, B
 
 
@@ -2325,26 +2328,14 @@ class MacrState:
 
 
 def _macr_check(U, I, w_item, w_user, users, pos, neg, st, loss_acc, check_ids: bool):
-    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
-    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1]:
-        raise ValueError("MACR tables: U [n_users, d] and I [n_items, d]")
-    d = U.shape[1]
-    if d not in MACR_EMBED_SIZES:
-        raise ValueError(f"MACR: the embedding width d must be one of {MACR_EMBED_SIZES}, got {d}")
+    d, B = _triplet_shapes("MACR", "U [n_users, d] and I [n_items, d]", MACR_EMBED_SIZES, U, I, users, pos, neg)
     if _need(w_item, torch.float32, "w_item").numel() != d or _need(w_user, torch.float32, "w_user").numel() != d:
         raise ValueError("w_item / w_user hold d float32 each")
-    users, pos, neg = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg")))
-    B = users.numel()
-    if B < 1 or pos.numel() != B or neg.numel() != B:
-        raise ValueError("users/pos/neg must have the same, non-zero length")
     if not isinstance(st, MacrState) or st.gU.shape != U.shape or st.gI.shape != I.shape:
         raise ValueError("st: the MacrState of these tables")
     if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < MACR_LOSS_TERMS:
         raise ValueError("MACR loss_acc holds five float32")
-    if check_ids:          # (a host synchronisation: the debugging entry points ask for it, the training loop does not)
-        lo = min(int(users.min()), int(pos.min()), int(neg.min()))
-        if lo < 0 or int(users.max()) >= U.shape[0] or max(int(pos.max()), int(neg.max())) >= I.shape[0]:
-            raise ValueError("MACR batch: a user or item id lies outside the tables")
+    _triplet_ids("MACR", U, I, users, pos, neg, check_ids)
     return d, B
 
 

@@ -150,6 +150,39 @@ def test_ops_checks_ids_and_the_kernel_skips_a_triplet_outside_the_tables(dev):
         assert float(st.wsum) == 0.0 and float(loss.abs().max()) == 0.0 and float(st.gU.abs().max()) == 0.0 and float(st.gI.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("d", [32, 256])
+def test_a_refused_triplet_inside_a_run_of_equal_positives(dev, d):
+    """The contract of the shared scatter of the positives' gradients (pos_scatter_any / pos_run_head / pos_scatter_run, pda_train_common.h) where
+    its callers differ: a workgroup holds TPB = 512 / (d / 4) triplets, the batch TPB + 3 (the run crosses a workgroup boundary, the last workgroup
+    is mostly empty), every positive is the same item, and two triplets are refused by the kernel -- triplet 2 (pos = n_items) inside the run of
+    the first workgroup, triplet TPB (users = -1) at the head of the second.  Under either rule the batch equals the kept triplets with the
+    means over the whole B, and the tags are set on exactly the kept triplets' rows."""
+    from pda_amd import ops
+    TPB = 512 // (d // 4)
+    B = TPB + 3
+    rng = np.random.default_rng(11 * d)
+    U, I = tables(rng, d)
+    ipw = ips_weights(COUNTS, 4.0)[1]
+    users, pos, neg = batch(rng, B)
+    pos[:] = 7
+    pos[2], users[TPB] = NI, -1
+    keep = ~np.isin(np.arange(B), [2, TPB])
+    kept = [x[keep] for x in (users, pos, neg)]
+    Ut, It, ut, pt, nt, wt = to(dev, U, I, users, pos, neg, ipw)
+    for norm in (False, True):
+        ref = ips_grads(U, I, *kept, ipw, norm=norm, regs=REGS, reg_div=B, B=B)
+        for grouped in (False, True):
+            st = State(Ut, It)
+            loss = torch.zeros(3, device=dev)
+            ops.ips_grads(Ut, It, ut, pt, nt, wt, st.gU, st.gI, st.tagU, st.tagI, wsum=st.wsum if norm else None, regs=REGS, reg_div=B, step=5,
+                          grouped=grouped, loss_acc=loss, check_ids=False)
+            check((loss.cpu().numpy(), st.gU.cpu().numpy(), st.gI.cpu().numpy()), ref, tolerance(ipw, kept[1], norm),
+                  "refused inside a run d=%d norm=%d grouped=%d" % (d, norm, grouped))
+            S_u, S_i = np.unique(kept[0]), np.unique(np.concatenate(kept[1:]))
+            tagU, tagI = st.tagU.cpu().numpy(), st.tagI.cpu().numpy()
+            assert (np.nonzero(tagU)[0] == S_u).all() and (np.nonzero(tagI)[0] == S_i).all() and set(tagU[S_u]) == {5} and set(tagI[S_i]) == {5}
+
+
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_three_whole_steps_against_the_restatement(dev, variant):
     from pda_amd import ops

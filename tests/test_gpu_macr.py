@@ -157,6 +157,32 @@ def test_ops_checks_ids_and_the_kernel_skips_a_triplet_outside_the_tables(dev):
     assert float(loss.abs().max()) == 0.0 and float(st.gU.abs().max()) == 0.0 and float(st.gI.abs().max()) == 0.0 and float(st.gW.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("d", [32, 256])
+def test_a_refused_triplet_inside_a_run_of_equal_positives(dev, d):
+    """The contract of the shared scatter of the positives' gradients (pos_scatter_any / pos_run_head / pos_scatter_run, pda_train_common.h) where
+    its callers differ: a workgroup holds TPB = 512 / (d / 4) triplets, the batch TPB + 3 (the run crosses a workgroup boundary, the last workgroup
+    is mostly empty), every positive is the same item, and two triplets are refused by the kernel -- triplet 2 (pos = n_items) inside the run of
+    the first workgroup, triplet TPB (users = -1) at the head of the second.  Under either rule the batch equals the kept triplets with the
+    means over the whole B, and the tags are set on exactly the kept triplets' rows."""
+    TPB = 512 // (d // 4)
+    B = TPB + 3
+    rng = np.random.default_rng(11 * d)
+    U, I = tables(rng, d)
+    wi, wu = (3 * w for w in branches(rng, d))
+    users, pos, neg = batch(rng, B)
+    pos[:] = 7
+    pos[2], users[TPB] = NI, -1
+    keep = ~np.isin(np.arange(B), [2, TPB])
+    kept = [x[keep] for x in (users, pos, neg)]
+    ref = macr_grads(U, I, wi, wu, *kept, alpha=0.5, beta=0.25, regs=REGS, reg_div=B, B=B)
+    for grouped in (False, True):
+        got, st = run_grads(dev, U, I, wi, wu, (users, pos, neg), 0.5, 0.25, B, step=5, grouped=grouped, check_ids=False)
+        check(got, ref, "refused inside a run d=%d grouped=%d" % (d, grouped), 0.5, 0.25)
+        S_u, S_i = np.unique(kept[0]), np.unique(np.concatenate(kept[1:]))
+        tagU, tagI = st.tagU.cpu().numpy(), st.tagI.cpu().numpy()
+        assert (np.nonzero(tagU)[0] == S_u).all() and (np.nonzero(tagI)[0] == S_i).all() and set(tagU[S_u]) == {5} and set(tagI[S_i]) == {5}
+
+
 @pytest.mark.parametrize("d", [32, 128])
 def test_three_whole_steps_against_the_restatement(dev, d):
     """Tables, branch vectors and all moments after three steps, within 1e-5; the gradient accumulators are zero behind every step."""

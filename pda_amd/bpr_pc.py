@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .exposure import BiasReport
 from .load_data import load_popularity
 from .sampler import host_generator
 
@@ -162,6 +163,7 @@ def main(argv=None):
     if t.check_topk_max(args) > ops.TOPK_K_V4:
         raise NotImplementedError("--topk_max %d: BPR-PC ranks at most %d items per user (its sweep keeps K + 8 candidates on chip and there is "
                                   "no PC head on the deep path)" % (args.topk_max, ops.PC_MAX_K))
+    bias = BiasReport.from_args(args, data, t.Ks)
     random.seed(2020)
     np.random.seed(2020)
     torch.manual_seed(2021)
@@ -190,6 +192,7 @@ def main(argv=None):
     model.set_sess(None)
 
     evaluation_model = t.evaluation(data, t.Ks, device, block=pc_eval_block(args.eval_block))
+    evaluation_model.set_bias_report(bias)
     if args.valid_set == "test":
         evaluation_model.set_evaluate_obj_pre("test")
         print("valid in test set")

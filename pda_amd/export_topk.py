@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from .bpr_pc import checkpoint_dir
+from .exposure import BiasReport
 from .load_data import get_popularity_from_load, load_popularity
 from .sampler import host_generator
 
@@ -72,9 +73,14 @@ def main(argv=None):
         raise ValueError("export_topk needs --export_out FILE.npz")
     pop = None if popularity is None else ev._pop_dev
     idx_parts, val_parts = [], []
+    from . import train_new_api as t
+    bias = BiasReport.from_args(args, t.data, t.Ks)            # --bias_report 1: the report of the lists written, without targets (no hit columns)
+    acc = None if bias is None else bias.accumulator(ev.device, with_hits=False)
     for i in range(0, ev.tot_user, ev.batch_size):
         ub = ev.users_dev[i:i + ev.batch_size]
         idx, val = model.recommend_device(ub, None, rec_type, pop, ev._hist, eval_pos=i, eval_users=ev.users_dev)
+        if acc is not None:
+            acc.add(idx)
         idx_parts.append(idx.cpu().numpy())
         val_parts.append(val.cpu().numpy())
     out = {"users": ev.users_dev.cpu().numpy().astype(np.int32), "idx": np.concatenate(idx_parts), "val": np.concatenate(val_parts)}
@@ -83,6 +89,9 @@ def main(argv=None):
     with open(args.export_out, "wb") as f:            # (a file object: np.savez would append .npz to a name without it)
         np.savez(f, **out)
     print("export_topk: %d users x %d items (%s) -> %s" % (out["idx"].shape[0], out["idx"].shape[1], rec_type, args.export_out))
+    if acc is not None:
+        for line in bias.header() + bias.report(acc).lines():
+            print(line)
     return out
 
 

@@ -2040,6 +2040,70 @@ def xquad_rerank(cand_idx, cand_val, item_is_head, lam, K=50, variant="smooth", 
     return idx, val
 
 
+# ---- item exposure of the lists (include/pda_hip_exposure.h) ------------------------------------------------------------------------------
+EXPOSURE_MAX_KS = _lib.EXPOSURE_MAX_KS
+EXPOSURE_MAX_COLS = _lib.EXPOSURE_MAX_COLS
+_EXPOSURE_KS = {}                        # (Ks, device) -> the cut-offs on the device: one copy per list of cut-offs, not one per block
+
+
+def exposure_ks(Ks) -> Tuple[int, ...]:
+    """The cut-offs of pda_list_exposure, checked: 1 .. EXPOSURE_MAX_KS integers, strictly ascending, the first >= 1."""
+    ks = tuple(int(k) for k in Ks)
+    if any(k != k0 for k, k0 in zip(ks, Ks)):
+        raise ValueError("Ks must be integers, got %r" % (list(Ks),))
+    if not 1 <= len(ks) <= EXPOSURE_MAX_KS:
+        raise ValueError("pda_list_exposure takes 1 .. %d cut-offs, got %d" % (EXPOSURE_MAX_KS, len(ks)))
+    if ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])) or ks[-1] > 0x7FFFFFFF:
+        raise ValueError("Ks must be strictly ascending and >= 1, got %r" % (list(ks),))
+    return ks
+
+
+def list_exposure(topk, Ks, n_items, tgt_indptr=None, tgt_indices=None, shown=None, hit=None, plain: bool = False):
+    """pda_list_exposure: shown[b][i] += the entries of topk int32 [n, k] in the columns Ks[b-1] <= j < Ks[b] that hold item i, hit[b][i] += those
+    that are also in the row's targets (CSR tgt_indptr int64 [n + 1], tgt_indices int32; both None: no hit counts, hit is None)
+    -> (shown, hit) int32 [len(Ks), n_items], zeroed here when none are given.  Ks: a host list, strictly ascending.  Ids outside [0, n_items) are
+    ignored.  plain: pda_list_exposure_plain, the same result with one global atomic per entry (the measurement's baseline)."""
+    lib = _lib.load()
+    topk = _need(topk, torch.int32, "topk")
+    ks = exposure_ks(Ks)
+    n_items = int(n_items)
+    if topk.dim() != 2 or topk.shape[0] < 1:
+        raise ValueError("topk must be [n_rows >= 1, k_cols]")
+    n, k = topk.shape
+    if not 1 <= k <= EXPOSURE_MAX_COLS:
+        raise ValueError(f"pda_list_exposure takes lists of 1 .. {EXPOSURE_MAX_COLS} columns, got {k}")
+    if not 1 <= n_items <= 0x7FFFFFFF:
+        raise ValueError(f"n_items must lie in 1 .. 2^31 - 1, got {n_items}")
+    if (tgt_indptr is None) != (tgt_indices is None):
+        raise ValueError("the targets are tgt_indptr and tgt_indices together, or neither")
+    with_hits = tgt_indptr is not None
+    if with_hits:
+        tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
+        tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+        if tgt_indptr.numel() != n + 1:
+            raise ValueError("tgt_indptr holds one row per list (n_rows + 1 entries)")
+        if tgt_indices.numel() == 0:            # (every target row empty: the C ABI wants a pointer, and reads nothing through it)
+            tgt_indices = tgt_indices.new_zeros(1)
+    elif hit is not None:
+        raise ValueError("a hit buffer needs the targets")
+    dev = topk.device
+    for name, buf in (("shown", shown), ("hit", hit)):
+        if buf is not None:
+            _need(buf, torch.int32, name)
+            if tuple(buf.shape) != (len(ks), n_items) or buf.device != dev:
+                raise ValueError(f"{name} must be int32 [len(Ks), n_items] on the lists' device")
+    if shown is None:
+        shown = torch.zeros((len(ks), n_items), dtype=torch.int32, device=dev)
+    if with_hits and hit is None:
+        hit = torch.zeros((len(ks), n_items), dtype=torch.int32, device=dev)
+    ks_dev = _EXPOSURE_KS.get((ks, dev))
+    if ks_dev is None:
+        ks_dev = _EXPOSURE_KS[(ks, dev)] = torch.as_tensor(ks, dtype=torch.int32, device=dev)
+    fn, what = (lib.pda_list_exposure_plain, "pda_list_exposure_plain") if plain else (lib.pda_list_exposure, "pda_list_exposure")
+    check(fn(ptr(topk), n, k, n_items, ptr(tgt_indptr), ptr(tgt_indices), ptr(ks_dev), len(ks), ptr(shown), ptr(hit), stream_ptr()), what)
+    return shown, hit
+
+
 # ---- what the checks of the tagged step kernels (DICE, IPS, MACR) repeat ---------------------------------------------------------------------
 def _triplet_shapes(method: str, tables: str, sizes, U, I, users, pos, neg, *, halves: int = 1, width_note: str = "", mask=None):
     """fp32 2-D tables of equal width (rows of `halves` embeddings of d floats), d in `sizes`, int32 users/pos/neg (and a uint8 mask, where given)

@@ -79,6 +79,9 @@ _EXTENSION_FLAGS = [
     ("xq_candidates", int, 1000, "xQuAD: candidates per user the re-ranking selects from, max(Ks) .. 1024 (above 54 they come from the deep path)"),
     ("xq_head_share", float, 0.8, "xQuAD: the short head is the most popular items that hold this share of the train interactions, strictly inside 0 .. 1"),
     ("xq_variant", str, "smooth", "xQuAD: smooth | binary"),
+    ("bias_report", int, 0, "1: after every metrics line, `||--- bias@K` lines on what the lists do to popularity bias -- recommendation rate, hit share and recall per popularity group, ARP, coverage, Gini, APLT (pda_amd/exposure.py; the head of APLT is --xq_head_share); one GPU; 0 | 1"),
+    ("bias_groups", int, 10, "--bias_report: popularity groups of the items, 1 .. 64 (group 0 = the most popular)"),
+    ("bias_group_by", str, "interactions", "--bias_report: interactions = groups of equal train interactions | items = groups of equal item counts"),
     ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
     ("ips_clip", float, 0.0, "IPS (--train ips): clip the inverse propensity weights at this value (IPS-C); 0: no clip"),
     ("ips_norm", int, 0, "IPS: 1 divides a batch's weighted loss by the sum of its weights instead of the batch size (IPS-CN, with --ips_clip); 0 | 1"),

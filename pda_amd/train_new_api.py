@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .exposure import BiasReport, EvalResult
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
 from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice, check_ips,
                         check_lightgcn, check_macr, gcn_train_pairs, ips_item_counts, macr_c_grid)
@@ -370,6 +371,12 @@ class evaluation:
         self.testing_popularity = None
         self.eval_who = "test"
         self._hist = None
+        self.bias = None
+
+    def set_bias_report(self, bias):
+        """--bias_report 1 (pda_amd/exposure.py): a BiasReport makes every eval() without an accumulator of its own count its lists and return
+        the four metrics as an EvalResult with the pass's bias lines beside them; None (the default) leaves eval() as it is."""
+        self.bias = bias
 
     def set_evaluate_obj(self, eval_who="test"):
         self.eval_who = eval_who
@@ -413,11 +420,19 @@ class evaluation:
         np.cumsum(lens, out=tp[1:])
         flat = np.concatenate([np.asarray(self.eval_user_list[u], dtype=np.int32) for u in users]) if users else np.zeros(0, np.int32)
         self._tp_host = tp
+        self._tgt_host = flat
         self.tgt_indices = torch.from_numpy(flat).to(self.device)
         self.list_batch_user = [users[i:i + self.batch_size] for i in range(0, len(users), self.batch_size)]
 
-    def eval(self, model, sess, rec_type):
-        """-> {'precision','recall','ndcg','hit_ratio': float64[len(Ks)]} = per-user sums / tot_user (:760-778)."""
+    def eval(self, model, sess, rec_type, exposure=None):
+        """-> {'precision','recall','ndcg','hit_ratio': float64[len(Ks)]} = per-user sums / tot_user (:760-778).
+        exposure: an exposure.ExposureAccumulator that every block's lists are added to (with the block's targets when it counts hits), for
+        the caller to read; the metrics do not depend on it."""
+        acc = exposure
+        if acc is None and self.bias is not None:
+            acc = self.bias.accumulator(self.device)
+        if acc is not None and (getattr(model, "_shard", None) is not None or getattr(getattr(model, "model", None), "_shard", None) is not None):
+            raise NotImplementedError("the bias report counts the lists of one GPU (an item-sharded evaluation is out of its scope)")
         pop = None if self.testing_popularity is None else self._pop_dev
         ks = torch.as_tensor(self.Ks, dtype=torch.int32, device=self.device)
         sums = torch.zeros((4, len(self.Ks)), dtype=torch.float64, device=self.device)
@@ -432,9 +447,19 @@ class evaluation:
                 reduce = ops.metrics_sums_deep_ordered if det else ops.metrics_sums_deep
             else:
                 reduce = ops.metrics_sums_ordered if det else ops.metrics_sums
-            reduce(idx, tptr, self.tgt_indices[int(tp[0]):int(tp[-1])], ks, sums)
+            tgt = self.tgt_indices[int(tp[0]):int(tp[-1])]
+            reduce(idx, tptr, tgt, ks, sums)
+            if acc is not None:
+                if acc.hit is not None:
+                    acc.add(idx, tptr, tgt)
+                else:
+                    acc.add(idx)
         s = (sums / float(self.tot_user)).cpu().numpy()
-        return {"precision": s[0], "recall": s[1], "ndcg": s[2], "hit_ratio": s[3]}
+        ret = {"precision": s[0], "recall": s[1], "ndcg": s[2], "hit_ratio": s[3]}
+        if exposure is None and acc is not None:
+            ret = EvalResult(ret)
+            ret.bias, ret.bias_lines = self.bias, self.bias.report(acc, self._tgt_host).lines()
+        return ret
 
 
 def early_stop(hr, ndcg, recall, precision, cur_epoch, config, stopping_step, flag_step=10):   # :911-927
@@ -480,6 +505,10 @@ def _print_result(ret):   # :1118-1123
     print("||---------------------------------------------- recall=[%.5f, %.5f], precision=[%.5f, %.5f], hit=[%.5f, %.5f], ndcg=[%.5f, %.5f]"
           % (ret["recall"][0], ret["recall"][-1], ret["precision"][0], ret["precision"][-1],
              ret["hit_ratio"][0], ret["hit_ratio"][-1], ret["ndcg"][0], ret["ndcg"][-1]))
+    bias = getattr(ret, "bias", None)                # (--bias_report 1: an exposure.EvalResult)
+    if bias is not None:
+        for line in bias.header() + ret.bias_lines:
+            print(line)
 
 
 def main(argv=None):
@@ -487,6 +516,7 @@ def main(argv=None):
     print(os.getcwd())
     configure(argv)
     check_topk_max(args)                   # (refusals before anything is built)
+    bias = BiasReport.from_args(args, data, Ks)
     if args.model == "lightgcn":
         check_lightgcn(args)
     elif args.model != "mf":
@@ -589,6 +619,7 @@ def main(argv=None):
     args.wd = args.regs                                                          # :1020
 
     evaluation_model = evaluation(data, Ks, device)
+    evaluation_model.set_bias_report(bias)
     if args.valid_set == "test":
         evaluation_model.set_evaluate_obj_pre("test")
         print("valid in test set")

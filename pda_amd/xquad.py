@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from .bpr_pc import checkpoint_dir
+from .exposure import BiasReport
 from .sampler import host_generator
 
 
@@ -169,6 +170,7 @@ def main(argv=None):
         raise NotImplementedError("Not implement this training method.....")
     K = check_flags(args, t.Ks)
     t.check_topk_max(args)
+    bias = BiasReport.from_args(args, data, t.Ks)
     random.seed(2020)
     np.random.seed(2020)
     torch.manual_seed(2021)
@@ -188,6 +190,7 @@ def main(argv=None):
     model.set_sess(None)
 
     evaluation_model = t.evaluation(data, t.Ks, device)
+    evaluation_model.set_bias_report(bias)
     if args.valid_set not in ("test", "valid"):
         print("evaluate type error.")
         sys.exit()

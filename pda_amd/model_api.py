@@ -5,6 +5,7 @@
     BPRMF              plain BPR-MF        MF/model_api.py:419-757   (only :419-471, :521-536, :695-706 are live)
     DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
     IPSBPRMF           IPS / IPS-C / IPS-CN (no reference code: DESIGN.md 5g)  a BPRMF trained with inverse propensity weights; Adam sweep only
+    SSMBPRMF           SSM                 (no reference code: DESIGN.md 5l)   a BPRMF trained with the sampled-softmax loss; Adam sweep only
     MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
     LightGCN           the LightGCN backbone (no reference code: DESIGN.md 5j)  ego tables propagated over the train graph; ConditionalLightGCN: PD/PDA on it
 
@@ -718,6 +719,83 @@ class IPSBPRMF(BPRMF):
         return sd
 
 
+def check_ssm(args):
+    """--train ssm: refuse, before anything is built, what the sampled-softmax step has no kernel for.  Every message names its flag."""
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train ssm sums its gradients with float atomics (no planned gradient)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train ssm runs fp32 tables only" % args.table_dtype)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train ssm runs the reference's dense-decay Adam only (--optimizer adam)" % args.optimizer)
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("--adam_sweep %s: --train ssm runs the dense Adam sweep only (auto | sweep)" % getattr(args, "adam_sweep", "auto"))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train ssm trains on one GPU (no item shards)" % args.gpus)
+    if getattr(args, "sampler", "device") != "device":
+        raise NotImplementedError("--sampler %s: --train ssm draws its [B, N] negatives with the device sampler only (--sampler device)" % args.sampler)
+    n = getattr(args, "ssm_negs", 64)
+    if int(n) != n or not 1 <= int(n) <= ops.SSM_MAX_NEGS:
+        raise ValueError("--ssm_negs must be an integer in 1 .. %d, got %s" % (ops.SSM_MAX_NEGS, n))
+    tau = float(getattr(args, "ssm_tau", 0.1))
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError("--ssm_tau must be a finite number > 0, got %s" % args.ssm_tau)
+    if getattr(args, "ssm_norm", 1) not in (0, 1):
+        raise ValueError("--ssm_norm must be 0 or 1, got %s" % args.ssm_norm)
+
+
+class SSMBPRMF(BPRMF):
+    """BPR-MF tables trained with the sampled-softmax loss (include/pda_hip_ssm.h): one positive and --ssm_negs sampled negatives
+    per row under a softmax with temperature --ssm_tau, on cosine similarity with --ssm_norm 1.  Fetchables and checkpoint layout are those of
+    BPRMF; a step is pda_ssm_adam_step_f32.  score_tables() -- what every ranking reads -- returns the raw tables for ssm_norm == 0 and the
+    row-normalised tables for ssm_norm == 1 (the lists then rank by cosine similarity, the quantity the loss trained); weights[...] and the
+    checkpoint always hold the RAW tables."""
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_ssm(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.ssm_negs = int(getattr(args, "ssm_negs", 64))
+        self.ssm_tau = float(getattr(args, "ssm_tau", 0.1))
+        self.ssm_norm = int(getattr(args, "ssm_norm", 1))
+        self._normed = None                  # ((U^, I^), (version of U, version of I) they were computed from)
+
+    def score_tables(self):
+        """ssm_norm == 1: the row-normalised tables of the current weights, recomputed when a step (or a restore) has moved them, cached otherwise."""
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        if not self.ssm_norm:
+            return U, I
+        ver = (U._version, I._version)
+        if self._normed is None or self._normed[1] != ver:
+            self._normed = ((ops.ssm_normalize_rows(U), ops.ssm_normalize_rows(I)), ver)
+        return self._normed[0]
+
+    def train_step(self, users, pos, negs, plan=None) -> torch.Tensor:
+        """One sampled-softmax step on (users [B], pos [B], negs [B, N]); returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this
+        step, as BPRMF.train_step does.  Nothing is read on the host."""
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._opt_state()
+        if "tagU" not in st:
+            st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
+        self._t += 1
+        ops.ssm_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, negs,
+                          tau=self.ssm_tau, norm=self.ssm_norm, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                          lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+        return self._loss
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd.update(ssm_negs=self.ssm_negs, ssm_tau=self.ssm_tau, ssm_norm=self.ssm_norm)
+        return sd
+
+
 MACR_EMBED_SIZES = ops.MACR_EVAL_EMBED_SIZES   # --embed_size of a MACR model: what its lists (the bias head) can rank
 
 
@@ -892,7 +970,7 @@ def gcn_train_pairs(train_user_list):
 def check_lightgcn(args):
     """--model lightgcn: refuse, before anything is built, what the LightGCN backbone has no kernel for.  Every message names the combination."""
     train = getattr(args, "train", "normal")
-    if train in ("temp_pop", "dice", "ips", "macr"):
+    if train in ("temp_pop", "dice", "ips", "macr", "ssm"):
         raise NotImplementedError("--model lightgcn --train %s: the LightGCN backbone trains with --train normal (BPR) or s_condition (PD/PDA) only" % train)
     if train not in ("normal", "s_condition"):
         raise NotImplementedError("--model lightgcn --train %s: normal | s_condition" % train)

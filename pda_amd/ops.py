@@ -2685,3 +2685,136 @@ def gcn_reg(U0, I0, users, pos, neg, gU, gI, *, regs: float, reg_div: float, los
     check(_lib.load().pda_gcn_reg_f32(ptr(U0), ptr(I0), U0.shape[0], I0.shape[0], ptr(users), ptr(pos), ptr(neg), B, U0.shape[1], float(regs),
                                       float(reg_div), ptr(gU), ptr(gI), ptr(loss_acc), stream_ptr()), "pda_gcn_reg_f32")
     mark_modified(gU, gI)
+
+
+# ---- the sampled-softmax loss (include/pda_hip_ssm.h) ------------------------------------------------------------------------------------------
+SSM_EMBED_SIZES = (32, 64, 128, 256)
+SSM_MAX_NEGS = _lib.SSM_MAX_NEGS
+
+
+def _ssm_params(tau, norm):
+    tau = float(tau)
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError(f"SSM: tau must be a finite number > 0, got {tau}")
+    if norm not in (0, 1, False, True):
+        raise ValueError(f"SSM: norm must be 0 or 1, got {norm!r}")
+    return tau, int(norm)
+
+
+def _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids: bool):
+    """The tables and (users, pos) as every tagged step checks them, negs int32 [B, N] with 1 <= N <= SSM_MAX_NEGS -> (d, B, N)."""
+    negs = _need(negs, torch.int32, "negs")
+    d, B = _triplet_shapes("SSM", "U [n_users, d] and I [n_items, d]", SSM_EMBED_SIZES, U, I, users, pos, pos)
+    if negs.dim() != 2 or negs.shape[0] != B or not 1 <= negs.shape[1] <= SSM_MAX_NEGS:
+        raise ValueError(f"SSM negs: int32 [B, N] with B = {B} rows and 1 <= N <= {SSM_MAX_NEGS}, got {tuple(negs.shape)}")
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("SSM loss_acc holds three float32")
+    _triplet_ids("SSM", U, I, users, pos, negs, check_ids)
+    return d, B, int(negs.shape[1])
+
+
+def ssm_step(U, I, users, pos, negs, gU, gI, tagU, tagI, *, tau: float, norm: int, regs: float, reg_div: float, step: int, grouped: bool = False,
+             users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_ssm_step_f32: the batch's sampled-softmax gradient summed into gU / gI (rows tagged `step`), no update.  negs int32 [B, N].
+    loss_acc float32 [3] += (loss, mf_loss, reg_loss)."""
+    d, B, N = _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids)
+    tau, norm = _ssm_params(tau, norm)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    check(_lib.load().pda_ssm_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(negs), B, N, d, tau, norm, float(regs),
+                                       float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step), _ips_flags(grouped, users_distinct),
+                                       ptr(loss_acc), stream_ptr()), "pda_ssm_step_f32")
+    mark_modified(gU, gI)
+
+
+def ssm_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, negs, *, tau: float, norm: int, regs: float, reg_div: float, step: int,
+                  lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False, users_distinct: bool = False,
+                  cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_ssm_adam_step_f32: one sampled-softmax train step (the gradients, TF-1.14 dense-decay Adam over both tables) in two launches;
+    graph-capturable.  The arguments of adam_step with negs int32 [B, N] in place of the negative and the popularities."""
+    d, B, N = _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids)
+    tau, norm = _ssm_params(tau, norm)
+    for t in (mU, vU, gU, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_ssm_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI),
+                                            I.shape[0], ptr(users), ptr(pos), ptr(negs), B, N, d, tau, norm, float(regs), float(reg_div), int(step),
+                                            float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy), ptr(loss_acc),
+                                            stream_ptr()), "pda_ssm_adam_step_f32")
+    mark_modified(U, I)
+
+
+def _ssm_sample_args(train_indptr, train_indices, B, N, neg_range, user_pool, n_pool):
+    if not 1 <= int(N) <= SSM_MAX_NEGS:
+        raise ValueError(f"SSM: the number of negatives per row must lie in 1 .. {SSM_MAX_NEGS}, got {N}")
+    if int(B) < 1:
+        raise ValueError("SSM sampler: B >= 1")
+    if int(neg_range[1]) <= int(neg_range[0]):
+        raise ValueError("SSM sampler: neg_range = (lo, hi) with hi > lo")
+    _need(train_indptr, torch.int64, "train_indptr"), _need(train_indices, torch.int32, "train_indices")
+    if user_pool is not None and _need(user_pool, torch.int32, "user_pool").numel() < int(n_pool):
+        raise ValueError("user_pool holds n_pool int32")
+
+
+def ssm_sample(train_indptr, train_indices, B: int, N: int, *, seed: int, step: int, neg_range, users=None, user_pool=None, n_pool: int = 0):
+    """pda_ssm_sample -> (users, pos, negs [B, N]) on the device: the users and positives of sample_triplets(seed, step), N negatives per row
+    (column 0: the negative of sample_triplets).  users given: they are kept and only positives and negatives are drawn."""
+    _ssm_sample_args(train_indptr, train_indices, B, N, neg_range, user_pool, n_pool)
+    dev = train_indptr.device
+    gen = users is None
+    if gen:
+        if int(n_pool) < 1:
+            raise ValueError("SSM sampler: drawing users needs n_pool >= 1")
+        users = torch.empty(B, dtype=torch.int32, device=dev)
+    elif _need(users, torch.int32, "users").numel() != B:
+        raise ValueError("users holds B int32")
+    pos = torch.empty(B, dtype=torch.int32, device=dev)
+    negs = torch.empty((B, N), dtype=torch.int32, device=dev)
+    check(_lib.load().pda_ssm_sample(ptr(users), int(gen), ptr(user_pool), int(n_pool), int(B), int(N), ptr(train_indptr), ptr(train_indices),
+                                     int(neg_range[0]), int(neg_range[1]), seed & (2 ** 64 - 1), int(step), ptr(pos), ptr(negs), stream_ptr()),
+          "pda_ssm_sample")
+    return users, pos, negs
+
+
+def ssm_sample_into(out, train_indptr, train_indices, *, seed: int, step_dev: torch.Tensor, neg_range, parity: Optional[int] = None, user_pool=None,
+                    n_pool: int = 0):
+    """pda_ssm_sample_dev: one batch into out = (users [B], pos [B], negs [B, N]), the step read from device memory (graph-capturable).
+    step_dev int64 [1]: read only.  step_dev int64 [2] + parity p: read from slot p, step + 1 stored to slot 1 - p (sample_triplets_into)."""
+    users, pos, negs = out
+    users, pos, negs = _need(users, torch.int32, "users"), _need(pos, torch.int32, "pos"), _need(negs, torch.int32, "negs")
+    B = users.numel()
+    if pos.numel() != B or negs.dim() != 2 or negs.shape[0] != B:
+        raise ValueError("SSM sampler output: users [B], pos [B], negs [B, N]")
+    _ssm_sample_args(train_indptr, train_indices, B, negs.shape[1], neg_range, user_pool, n_pool)
+    if int(n_pool) < 1:
+        raise ValueError("SSM sampler: drawing users needs n_pool >= 1")
+    step_dev = _need(step_dev, torch.int64, "step_dev")
+    if parity is None:
+        src, nxt = step_dev, None
+    else:
+        if step_dev.numel() != 2:
+            raise ValueError("parity mode needs a two-slot step counter")
+        src, nxt = step_dev[parity:parity + 1], step_dev[1 - parity:2 - parity]
+    check(_lib.load().pda_ssm_sample_dev(ptr(users), 1, ptr(user_pool), int(n_pool), B, int(negs.shape[1]), ptr(train_indptr), ptr(train_indices),
+                                         int(neg_range[0]), int(neg_range[1]), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(negs),
+                                         stream_ptr()), "pda_ssm_sample_dev")
+    return out
+
+
+def ssm_normalize_rows(X, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_ssm_normalize_rows_f32 -> Y float32 [n_rows, d], Y[r] = X[r] / max(|X[r]|, 1e-12) (the sum of squares in float64, a fixed order):
+    the evaluation tables of a norm == 1 model."""
+    X = _need(X, torch.float32, "X")
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] not in SSM_EMBED_SIZES:
+        raise ValueError(f"ssm_normalize_rows: X float32 [n_rows >= 1, d], d one of {SSM_EMBED_SIZES}, got {tuple(X.shape)}")
+    if out is None:
+        out = torch.empty_like(X)
+    if _need(out, torch.float32, "out").shape != X.shape:
+        raise ValueError("out has the shape of X")
+    check(_lib.load().pda_ssm_normalize_rows_f32(ptr(X), X.shape[0], X.shape[1], ptr(out), stream_ptr()), "pda_ssm_normalize_rows_f32")
+    mark_modified(out)
+    return out

@@ -13,8 +13,8 @@ _REFERENCE_FLAGS = [
     ("data_path", None, "./data/", "root directory that holds <dataset>/"),
     ("dataset", None, "kwai", "dataset directory name"),
     ("source", None, "normal", "(unused)"),
-    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA)"),
-    ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA)"),
+    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm)"),
+    ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the raw head of an SSM model alone)"),
     ("valid_set", None, "test", "test | valid"),
     ("save_dir", None, "/data/zyang/save_model/", "checkpoint root"),
     ("alpha", float, 1e-3, "MACR (--train macr): weight of the item-branch loss L_I; otherwise unused (appears in the checkpoint directory name)"),
@@ -83,6 +83,9 @@ _EXTENSION_FLAGS = [
     ("bias_groups", int, 10, "--bias_report: popularity groups of the items, 1 .. 64 (group 0 = the most popular)"),
     ("bias_group_by", str, "interactions", "--bias_report: interactions = groups of equal train interactions | items = groups of equal item counts"),
     ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
+    ("ssm_negs", int, 64, "SSM (--train ssm): sampled negatives per row of the softmax, 1 .. 256"),
+    ("ssm_tau", float, 0.1, "SSM: the temperature tau of the logits, > 0"),
+    ("ssm_norm", int, 1, "SSM: 1 takes the logits on cosine similarity (rows normalised to length 1, in training and in the lists), 0 on the raw dot product; 0 | 1"),
     ("ips_clip", float, 0.0, "IPS (--train ips): clip the inverse propensity weights at this value (IPS-C); 0: no clip"),
     ("ips_norm", int, 0, "IPS: 1 divides a batch's weighted loss by the sum of its weights instead of the batch size (IPS-CN, with --ips_clip); 0 | 1"),
     ("dice_int_weight", float, 0.1, "DICE (--train dice): weight of the interest loss L_int"),

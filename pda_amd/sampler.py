@@ -12,6 +12,7 @@ yielding, per step, a tuple of sequences of length batch_size -- (users, pos, ne
                      Not stream-identical to the host generators -- parity is defined on injected batches
                      (last bullet).  mode="dice": PNSM, DICE's popularity-margin negative sampler
                      (pda_dice_sample): (users, pos, neg, mask), and the margin's schedule (start_epoch).
+                     mode="ssm": the sampled-softmax batches (pda_ssm_sample_dev): (users, pos, negs [B, n_negs]).
     HostDiceSampler  PNSM in numpy, the debugging twin of mode="dice" (--sampler host): the same algorithm on the
                      host's random streams -- NOT draw for draw the device stream.
 """
@@ -104,9 +105,15 @@ class DeviceSampler:
     batch handed out is a row view of the queue and stays valid until `ahead` further batches have been taken."""
 
     def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0, mode: str = "bpr",
-                 margin: float = 40.0, margin_decay: float = 0.9):
-        if mode not in ("bpr", "dice"):
-            raise ValueError("DeviceSampler mode must be 'bpr' or 'dice', not %r" % (mode,))
+                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0):
+        if mode not in ("bpr", "dice", "ssm"):
+            raise ValueError("DeviceSampler mode must be 'bpr', 'dice' or 'ssm', not %r" % (mode,))
+        if mode == "ssm":
+            if with_pop or temp_slots > 0:
+                raise ValueError("mode='ssm' draws (users, pos, negs): no popularity columns (with_pop), no time slots (temp_slots)")
+            if not 1 <= int(n_negs) <= ops.SSM_MAX_NEGS:
+                raise ValueError("mode='ssm': n_negs must lie in 1 .. %d, got %r" % (ops.SSM_MAX_NEGS, n_negs))
+        self.n_negs = int(n_negs)
         if mode == "dice" and (with_pop or temp_slots > 0 or neg_range is not None):
             raise ValueError("mode='dice' draws (users, pos, neg, mask) over the whole catalogue: no popularity columns, no time slots, no neg_range")
         self.mode = mode
@@ -133,6 +140,23 @@ class DeviceSampler:
         self.distinct_users = data.batch_size <= self.pool.numel()
         self.with_plan = False        # set by the trainer (--optimizer sgd): every batch comes with its pda_triplet_plan
         self.plan = None              # the plan of the batch handed out last
+
+    def _refill_ssm(self):
+        """The next `ahead` batches of mode="ssm", one pda_ssm_sample_dev launch each on the two-slot device counter (the protocol of the bpr
+        queue; bit for bit the batches of ops.ssm_sample(step = 1, 2, ..)).  Two queues in turn, as in _refill."""
+        B, n, N = self.data.batch_size, self.ahead, self.n_negs
+        if self._queue is None:
+            mk = lambda *shape: torch.empty(shape, dtype=torch.int32, device=self.device)      # noqa: E731
+            self._queues = [(mk(n, B), mk(n, B), mk(n, B, N)) for _ in range(2)]
+            self._ctr = torch.tensor([self.step, 0], dtype=torch.int64, device=self.device)      # (batch() has counted this one)
+            self._calls = self._draws = 0
+        self._queue = self._queues[self._calls & 1]
+        for j in range(n):
+            ops.ssm_sample_into(tuple(q[j] for q in self._queue), self.indptr, self.indices, seed=self.seed, step_dev=self._ctr,
+                                parity=self._draws & 1, user_pool=self.pool, n_pool=self.pool.numel(), neg_range=self.neg_range)
+            self._draws += 1
+        self._calls += 1
+        self._left = n
 
     def _refill(self):
         B, n = self.data.batch_size, self.ahead
@@ -169,6 +193,15 @@ class DeviceSampler:
             self.plan = None
             return ops.dice_sample(self.indptr, self.indices, self.dice_pop, self.data.batch_size, margin=self.margin, seed=self.seed,
                                    step=self.step, user_pool=self.pool, n_pool=self.pool.numel())
+        if self.mode == "ssm":
+            if self.with_plan:
+                raise ValueError("mode='ssm' has no triplet plan (with_plan): the sampled-softmax step sums its gradients with float atomics")
+            self.plan = None
+            if self._left == 0:
+                self._refill_ssm()
+            j = self.ahead - self._left
+            self._left -= 1
+            return tuple(q[j] for q in self._queue)
         if self.ahead == 1:
             u, p, n, pp, pn = ops.sample_triplets(self.indptr, self.indices, self.data.batch_size, seed=self.seed,
                                                   step=self.step, user_pool=self.pool, n_pool=self.pool.numel(),

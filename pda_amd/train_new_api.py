@@ -29,8 +29,8 @@ import torch
 from . import ops
 from .exposure import BiasReport, EvalResult
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice, check_ips,
-                        check_lightgcn, check_macr, gcn_train_pairs, ips_item_counts, macr_c_grid)
+from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice,
+                        check_ips, check_lightgcn, check_macr, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -150,6 +150,11 @@ class DatasetApi_Model:
             self.input_type = "without_pop"
             print("dataset api without pop")
             self.Recommender = IPSBPRMF(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train == "ssm":
+            # SSM: a BPRMF under the sampled-softmax loss; batches carry a [B, N] block of negatives, the lists read score_tables()
+            self.input_type = "without_pop"
+            print("dataset api without pop")
+            self.Recommender = SSMBPRMF(args, data_config, use_dataset_api=True, device=self.device)
         elif args.train == "macr":
             # MACR: the tables of a BPRMF plus two branch vectors; lists ranked by (y - c) s_i through the bias head
             self.input_type = "without_pop"
@@ -530,6 +535,11 @@ def main(argv=None):
         if args.test not in ("normal", "ips"):
             raise NotImplementedError("--train ips goes with --test normal (the raw head and the gamma search of a BPRMF) or --test ips, not --test "
                                       + str(args.test))
+    if args.train == "ssm":
+        check_ssm(args)
+        if args.test not in ("normal", "ssm"):
+            raise NotImplementedError("--train ssm goes with --test normal (the raw head and the gamma search of a BPRMF) or --test ssm, not --test "
+                                      + str(args.test))
     if args.train == "macr":
         check_macr(args)
         if args.test != "macr":
@@ -558,12 +568,14 @@ def main(argv=None):
     if args.model == "lightgcn":           # the graph's edges reach the model the way ips_item_counts does
         config["gcn_train_pairs"] = gcn_train_pairs(data.train_user_list)
         args.saveID += "gcn_layers-{}".format(args.gcn_layers)
-    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr"):   # :963-970 (DICE and IPS are evaluated like a BPRMF: --test normal)
+    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr", "ssm"):   # :963-970 (DICE, IPS and SSM are evaluated like a BPRMF: --test normal)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
-        print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------", "macr": "-------    running MACR  ----------------"}
-              .get(args.train, "-------    running IPS  ----------------"))
+        print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------", "macr": "-------    running MACR  ----------------",
+               "ssm": "-------    running SSM  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
         if args.train == "macr":
             args.saveID += "macr"
+        if args.train == "ssm":
+            args.saveID += "ssm"
         if args.train == "ips":
             args.saveID += "ips"
             config["ips_item_counts"] = ips_item_counts(data.train_user_list, data.n_items)
@@ -609,6 +621,8 @@ def main(argv=None):
             sampler = DeviceSampler(data, device, False, mode="dice", margin=args.dice_margin, margin_decay=args.dice_margin_decay)
         else:
             sampler = HostDiceSampler(data, args.dice_margin, args.dice_margin_decay)
+    elif args.train == "ssm":              # (check_ssm has refused --sampler host)
+        sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs)
     elif args.sampler == "device":
         sampler = DeviceSampler(data, device, with_pop)
     else:
@@ -696,7 +710,7 @@ def main(argv=None):
             print("||------------PDA/PDGA injecting linear predicted popularity testing : time: ", int(time() - ttt1))
             _print_result(ret2)
             ret = ret1
-        elif args.test in ("temp_pop", "dice", "ips"):                           # :1192-1200 (--test dice / ips: the main_branch head alone)
+        elif args.test in ("temp_pop", "dice", "ips", "ssm"):                    # :1192-1200 (--test dice / ips / ssm: the main_branch head alone)
             print(perf_str)
             ttt1 = time()
             evaluation_model.set_testing_popularity(None)
@@ -827,11 +841,11 @@ def main(argv=None):
         ret = evaluation_model.eval(model, sess, rec_type="macr")
         print("---- MACR result with the best c of the validation (c = {:.6f}):".format(rec.best_c))
         _print_result(ret)
-    elif args.test in ("temp_pop", "dice", "ips"):                               # :1310-1314
+    elif args.test in ("temp_pop", "dice", "ips", "ssm"):                        # :1310-1314
         evaluation_model.set_testing_popularity(None)
         ret = evaluation_model.eval(model, sess, rec_type="main_branch")
         print({"temp_pop": "---- result with last pop bias for temp_pop model:", "dice": "---- DICE result (interest + conformity):"}
-              .get(args.test, "---- IPS result:"))
+              .get(args.test, "---- SSM result:" if args.test == "ssm" else "---- IPS result:"))
         _print_result(ret)
     print("training and testing end!!!!")
     print("|||  ------------------------ best performance for model selected by PD/PDG/BPRMF ------------------- |||")

@@ -1,5 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
-pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h and pda_hip_ssm.h).
+pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h and
+pda_hip_inbatch.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -241,6 +242,19 @@ SSM_SIGNATURES = {
     "pda_ssm_normalize_rows_f32": (_i, [_vp, _sz, _i, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_inbatch.h (the in-batch softmax: `--train ssm --ssm_source batch`)
+INBATCH_MAX_B = 16384
+INBATCH_ROW_TILE = 32
+INBATCH_COL_TILE = 32
+INBATCH_SIGNATURES = {
+    "pda_inbatch_col_splits": (_i, [_i]),
+    "pda_inbatch_workspace_bytes": (_sz, [_i, _i]),
+    "pda_inbatch_mask": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "pda_inbatch_step_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _f, _f] + [_vp] * 4 + [_i, _i, _vp, _sz, _vp, _vp]),
+    "pda_inbatch_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _f, _f, _i, _f, _f, _f, _f, _i, _i,
+                                       _vp, _sz, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -261,7 +275,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
-            list(SSM_SIGNATURES.items()):
+            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

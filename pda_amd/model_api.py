@@ -741,6 +741,17 @@ def check_ssm(args):
         raise ValueError("--ssm_tau must be a finite number > 0, got %s" % args.ssm_tau)
     if getattr(args, "ssm_norm", 1) not in (0, 1):
         raise ValueError("--ssm_norm must be 0 or 1, got %s" % args.ssm_norm)
+    source = getattr(args, "ssm_source", "sampled")
+    if source not in ("sampled", "batch"):
+        raise ValueError("--ssm_source must be sampled or batch, got %s" % (source,))
+    for flag in ("ssm_logq", "ssm_mask_train"):
+        if getattr(args, flag, 1) not in (0, 1):
+            raise ValueError("--%s must be 0 or 1, got %s" % (flag, getattr(args, flag)))
+    if source == "batch":
+        B = getattr(args, "batch_size", 2048)
+        if int(B) != B or not 2 <= int(B) <= ops.INBATCH_MAX_B:
+            raise ValueError("--batch_size must be an integer in 2 .. %d with --ssm_source batch (a row's negatives are the other rows' "
+                             "positives), got %s" % (ops.INBATCH_MAX_B, B))
 
 
 class SSMBPRMF(BPRMF):
@@ -748,7 +759,10 @@ class SSMBPRMF(BPRMF):
     per row under a softmax with temperature --ssm_tau, on cosine similarity with --ssm_norm 1.  Fetchables and checkpoint layout are those of
     BPRMF; a step is pda_ssm_adam_step_f32.  score_tables() -- what every ranking reads -- returns the raw tables for ssm_norm == 0 and the
     row-normalised tables for ssm_norm == 1 (the lists then rank by cosine similarity, the quantity the loss trained); weights[...] and the
-    checkpoint always hold the RAW tables."""
+    checkpoint always hold the RAW tables.
+    --ssm_source batch (include/pda_hip_inbatch.h): a row's negatives are the other rows' positives, a step is the train mask
+    (--ssm_mask_train 1) and pda_inbatch_adam_step_f32 with the logQ table (--ssm_logq 1); the trainer hands the train graph over with
+    set_train_graph before the first step.  Tables, lists and checkpoint layout are the same."""
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
         check_ssm(args)
@@ -758,6 +772,28 @@ class SSMBPRMF(BPRMF):
         self.ssm_tau = float(getattr(args, "ssm_tau", 0.1))
         self.ssm_norm = int(getattr(args, "ssm_norm", 1))
         self._normed = None                  # ((U^, I^), (version of U, version of I) they were computed from)
+        self.ssm_source = str(getattr(args, "ssm_source", "sampled"))
+        self.ssm_logq = int(getattr(args, "ssm_logq", 1))
+        self.ssm_mask_train = int(getattr(args, "ssm_mask_train", 1))
+        self._graph = None                   # (train_indptr, train_indices, user_pool) of --ssm_source batch
+        self._inbatch = None                 # its workspace, mask and logq, allocated once
+
+    def set_train_graph(self, train_indptr, train_indices, user_pool=None):
+        """--ssm_source batch: the train CSR on the device (int64 indptr, int32 item ids sorted inside a row) the mask is taken from, and the
+        sampler's user pool the logQ table is computed for."""
+        self._graph, self._inbatch = (train_indptr, train_indices, user_pool), None
+
+    def _inbatch_buffers(self, B, U, I):
+        if self._inbatch is None or self._inbatch["B"] != B:
+            if self._graph is None and (self.ssm_logq or self.ssm_mask_train):
+                raise ValueError("--ssm_source batch with --ssm_logq 1 or --ssm_mask_train 1 needs the train graph: call set_train_graph first")
+            b = dict(B=B, ws=ops.inbatch_workspace(B, U.shape[1], U.device), mask=None, logq=None)
+            if self.ssm_mask_train:
+                b["mask"] = torch.empty((B, ops.inbatch_mask_words(B)), dtype=torch.int32, device=U.device)
+            if self.ssm_logq:
+                b["logq"] = torch.from_numpy(ops.inbatch_logq(self._graph[0], self._graph[1], I.shape[0], self._graph[2])).to(U.device)
+            self._inbatch = b
+        return self._inbatch
 
     def score_tables(self):
         """ssm_norm == 1: the row-normalised tables of the current weights, recomputed when a step (or a restore) has moved them, cached otherwise."""
@@ -769,9 +805,9 @@ class SSMBPRMF(BPRMF):
             self._normed = ((ops.ssm_normalize_rows(U), ops.ssm_normalize_rows(I)), ver)
         return self._normed[0]
 
-    def train_step(self, users, pos, negs, plan=None) -> torch.Tensor:
+    def train_step(self, users, pos, negs=None, plan=None) -> torch.Tensor:
         """One sampled-softmax step on (users [B], pos [B], negs [B, N]); returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this
-        step, as BPRMF.train_step does.  Nothing is read on the host."""
+        step, as BPRMF.train_step does.  Nothing is read on the host.  --ssm_source batch: negs is ignored (the triplet sampler's negative)."""
         U, I = self.weights["user_embedding"], self.weights["item_embedding"]
         rows = getattr(self, "_loss_rows", None)
         if rows is not None and self._loss_row_i < rows.shape[0]:
@@ -785,6 +821,15 @@ class SSMBPRMF(BPRMF):
         if "tagU" not in st:
             st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
         self._t += 1
+        if self.ssm_source == "batch":
+            b = self._inbatch_buffers(users.numel(), U, I)
+            if b["mask"] is not None:
+                ops.inbatch_mask(users, pos, self._graph[0], self._graph[1], U.shape[0], I.shape[0], out=b["mask"])
+            ops.inbatch_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, b["ws"],
+                                  tau=self.ssm_tau, norm=self.ssm_norm, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                                  lr_t=ops.adam_lr_t(self.lr, self._t), logq=b["logq"], mask=b["mask"],
+                                  users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+            return self._loss
         ops.ssm_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, negs,
                           tau=self.ssm_tau, norm=self.ssm_norm, regs=self.decay, reg_div=self.batch_size, step=self._t,
                           lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
@@ -793,6 +838,8 @@ class SSMBPRMF(BPRMF):
     def state_dict(self):
         sd = super().state_dict()
         sd.update(ssm_negs=self.ssm_negs, ssm_tau=self.ssm_tau, ssm_norm=self.ssm_norm)
+        if self.ssm_source == "batch":      # (a sampled run's checkpoint keeps the keys it had)
+            sd.update(ssm_source=self.ssm_source, ssm_logq=self.ssm_logq, ssm_mask_train=self.ssm_mask_train)
         return sd
 
 

@@ -2818,3 +2818,131 @@ def ssm_normalize_rows(X, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     check(_lib.load().pda_ssm_normalize_rows_f32(ptr(X), X.shape[0], X.shape[1], ptr(out), stream_ptr()), "pda_ssm_normalize_rows_f32")
     mark_modified(out)
     return out
+
+
+# ---- the in-batch softmax with logQ correction (include/pda_hip_inbatch.h) ----------------------------------------------------------------------
+INBATCH_MAX_B = _lib.INBATCH_MAX_B
+INBATCH_ROW_TILE = _lib.INBATCH_ROW_TILE
+INBATCH_COL_TILE = _lib.INBATCH_COL_TILE
+
+
+def inbatch_col_splits(B: int) -> int:
+    """pda_inbatch_col_splits: the column ranges the tile passes split a batch of B into."""
+    if not 1 <= int(B) <= INBATCH_MAX_B:
+        raise ValueError(f"in-batch softmax: the batch size must lie in 1 .. {INBATCH_MAX_B}, got {B}")
+    return int(_lib.load().pda_inbatch_col_splits(int(B)))
+
+
+def inbatch_workspace(B: int, d: int, device) -> torch.Tensor:
+    """The workspace of one batch size and width (pda_inbatch_workspace_bytes): uint8, private to one stream."""
+    if not 1 <= int(B) <= INBATCH_MAX_B:
+        raise ValueError(f"in-batch softmax: the batch size must lie in 1 .. {INBATCH_MAX_B}, got {B}")
+    if d not in SSM_EMBED_SIZES:
+        raise ValueError(f"in-batch softmax: the embedding width d must be one of {SSM_EMBED_SIZES}, got {d}")
+    return torch.empty(int(_lib.load().pda_inbatch_workspace_bytes(int(B), int(d))), dtype=torch.uint8, device=device)
+
+
+def inbatch_mask_words(B: int) -> int:
+    return (int(B) + 31) // 32
+
+
+def inbatch_logq(train_indptr, train_indices, n_items: int, user_pool=None):
+    """log q_i of the device sampler's columns, on the host -> numpy float32 [n_items].  The sampler draws a user uniformly from its pool (all
+    users without one) and then one of that user's train items uniformly: q_i = (1 / n_pool) sum_{u in pool, i in I_u} 1 / |I_u|, summed in
+    float64 and rounded once.  An item that never appears as a column (q_i = 0) takes the log of the smallest positive q: the table stays finite."""
+    import numpy as np
+    to_np = lambda t: t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)      # noqa: E731
+    indptr, indices = to_np(train_indptr).astype(np.int64), to_np(train_indices).astype(np.int64)
+    pool = np.arange(len(indptr) - 1, dtype=np.int64) if user_pool is None else to_np(user_pool).astype(np.int64)
+    if pool.size < 1:
+        raise ValueError("inbatch_logq: an empty user pool")
+    lens = (indptr[1:] - indptr[:-1])[pool]
+    # a user without train items puts item 0 into its column (the sampler's convention); such users are not in a trainer's pool
+    q = np.zeros(int(n_items), dtype=np.float64)
+    has = lens > 0
+    starts = indptr[pool[has]]
+    flat = np.concatenate([indices[s:s + n] for s, n in zip(starts, lens[has])]) if has.any() else np.zeros(0, np.int64)
+    np.add.at(q, flat, np.repeat(1.0 / lens[has], lens[has]))
+    q[0] += float((~has).sum())
+    q /= float(pool.size)
+    if not (q > 0).any():
+        raise ValueError("inbatch_logq: no item occurs")
+    q[q == 0] = q[q > 0].min()
+    return np.log(q).astype(np.float32)
+
+
+def inbatch_mask(users, pos, train_indptr, train_indices, n_users: int, n_items: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_inbatch_mask -> int32 [B, ceil(B / 32)] (the words are the kernel's uint32): bit (r, c) set iff c != r and pos[c] is a train item of
+    users[r]."""
+    users, pos = _need(users, torch.int32, "users"), _need(pos, torch.int32, "pos")
+    _need(train_indptr, torch.int64, "train_indptr"), _need(train_indices, torch.int32, "train_indices")
+    B = users.numel()
+    if not 1 <= B <= INBATCH_MAX_B or pos.numel() != B:
+        raise ValueError(f"in-batch softmax: users / pos of one length in 1 .. {INBATCH_MAX_B}")
+    if train_indptr.numel() != int(n_users) + 1:
+        raise ValueError("train_indptr holds n_users + 1 int64")
+    W = inbatch_mask_words(B)
+    if out is None:
+        out = torch.empty((B, W), dtype=torch.int32, device=users.device)
+    if _need(out, torch.int32, "mask").numel() != B * W:
+        raise ValueError(f"mask: int32 [B, ceil(B / 32)] = [{B}, {W}]")
+    check(_lib.load().pda_inbatch_mask(ptr(users), ptr(pos), B, ptr(train_indptr), ptr(train_indices), int(n_users), int(n_items), ptr(out),
+                                       stream_ptr()), "pda_inbatch_mask")
+    mark_modified(out)
+    return out
+
+
+def _inbatch_check(U, I, users, pos, logq, mask, tagU, tagI, ws, loss_acc, check_ids: bool):
+    """The tables and (users, pos) as every tagged step checks them, the optional logq float32 [n_items] and mask int32 [B, ceil(B / 32)], the
+    workspace -> (d, B)."""
+    d, B = _triplet_shapes("in-batch softmax", "U [n_users, d] and I [n_items, d]", SSM_EMBED_SIZES, U, I, users, pos, pos)
+    if B > INBATCH_MAX_B:
+        raise ValueError(f"in-batch softmax: the batch size must lie in 1 .. {INBATCH_MAX_B}, got {B}")
+    if _need(logq, torch.float32, "logq", optional=True) is not None and logq.numel() != I.shape[0]:
+        raise ValueError("logq holds one float32 per item")
+    if _need(mask, torch.int32, "mask", optional=True) is not None and mask.numel() != B * inbatch_mask_words(B):
+        raise ValueError(f"mask: int32 [B, ceil(B / 32)] = [{B}, {inbatch_mask_words(B)}]")
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(ws, torch.uint8, "ws").numel() < int(_lib.load().pda_inbatch_workspace_bytes(B, d)):
+        raise ValueError("ws: the workspace of inbatch_workspace(B, d)")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("in-batch softmax loss_acc holds three float32")
+    _triplet_ids("in-batch softmax", U, I, users, pos, pos, check_ids)
+    return d, B
+
+
+def inbatch_step(U, I, users, pos, gU, gI, tagU, tagI, ws, *, tau: float, norm: int, regs: float, reg_div: float, step: int, logq=None, mask=None,
+                 grouped: bool = False, users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_inbatch_step_f32: the batch's in-batch softmax gradient summed into gU / gI (rows tagged `step`), no update.
+    loss_acc float32 [3] += (loss, mf_loss, reg_loss)."""
+    d, B = _inbatch_check(U, I, users, pos, logq, mask, tagU, tagI, ws, loss_acc, check_ids)
+    tau, norm = _ssm_params(tau, norm)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    check(_lib.load().pda_inbatch_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), B, d, tau, norm, ptr(logq), ptr(mask),
+                                           float(regs), float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step),
+                                           _ips_flags(grouped, users_distinct), ptr(ws), ws.numel(), ptr(loss_acc), stream_ptr()),
+          "pda_inbatch_step_f32")
+    mark_modified(gU, gI)
+
+
+def inbatch_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, ws, *, tau: float, norm: int, regs: float, reg_div: float, step: int,
+                      lr_t: float, logq=None, mask=None, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False,
+                      users_distinct: bool = False, cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None,
+                      check_ids: bool = False):
+    """pda_inbatch_adam_step_f32: one in-batch softmax train step (the gradients, TF-1.14 dense-decay Adam over both tables) in five launches;
+    graph-capturable.  The arguments of ssm_adam_step without the block of negatives, with the workspace and the optional logq and mask."""
+    d, B = _inbatch_check(U, I, users, pos, logq, mask, tagU, tagI, ws, loss_acc, check_ids)
+    tau, norm = _ssm_params(tau, norm)
+    for t in (mU, vU, gU, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_inbatch_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI),
+                                                ptr(tagI), I.shape[0], ptr(users), ptr(pos), B, d, tau, norm, ptr(logq), ptr(mask), float(regs),
+                                                float(reg_div), int(step), float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct),
+                                                int(cache_policy), ptr(ws), ws.numel(), ptr(loss_acc), stream_ptr()),
+          "pda_inbatch_adam_step_f32")
+    mark_modified(U, I)

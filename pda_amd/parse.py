@@ -83,7 +83,10 @@ _EXTENSION_FLAGS = [
     ("bias_groups", int, 10, "--bias_report: popularity groups of the items, 1 .. 64 (group 0 = the most popular)"),
     ("bias_group_by", str, "interactions", "--bias_report: interactions = groups of equal train interactions | items = groups of equal item counts"),
     ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
-    ("ssm_negs", int, 64, "SSM (--train ssm): sampled negatives per row of the softmax, 1 .. 256"),
+    ("ssm_source", str, "sampled", "SSM (--train ssm): where a row's negatives come from.  sampled = --ssm_negs uniform draws per row | batch = the other rows' positives (in-batch softmax, include/pda_hip_inbatch.h: --batch_size - 1 shared negatives per row, --batch_size in 2 .. 16384)"),
+    ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1"),
+    ("ssm_mask_train", int, 1, "SSM with --ssm_source batch: 1 leaves a column out of a row's softmax when its item is a train item of the row's user (the sampled path rejects the same items when it draws); 0 | 1"),
+    ("ssm_negs", int, 64, "SSM (--train ssm): sampled negatives per row of the softmax, 1 .. 256; unused with --ssm_source batch"),
     ("ssm_tau", float, 0.1, "SSM: the temperature tau of the logits, > 0"),
     ("ssm_norm", int, 1, "SSM: 1 takes the logits on cosine similarity (rows normalised to length 1, in training and in the lists), 0 on the raw dot product; 0 | 1"),
     ("ips_clip", float, 0.0, "IPS (--train ips): clip the inverse propensity weights at this value (IPS-C); 0: no clip"),

@@ -155,6 +155,9 @@ class DatasetApi_Model:
             self.input_type = "without_pop"
             print("dataset api without pop")
             self.Recommender = SSMBPRMF(args, data_config, use_dataset_api=True, device=self.device)
+            #  the train mask and the logQ table come from the sampler's graph; a model that only ranks (export_topk) has no sampler
+            if self.Recommender.ssm_source == "batch" and hasattr(generator_sampler, "indptr"):
+                self.Recommender.set_train_graph(generator_sampler.indptr, generator_sampler.indices, generator_sampler.pool)
         elif args.train == "macr":
             # MACR: the tables of a BPRMF plus two branch vectors; lists ranked by (y - c) s_i through the bias head
             self.input_type = "without_pop"
@@ -622,7 +625,10 @@ def main(argv=None):
         else:
             sampler = HostDiceSampler(data, args.dice_margin, args.dice_margin_decay)
     elif args.train == "ssm":              # (check_ssm has refused --sampler host)
-        sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs)
+        if args.ssm_source == "batch":     # in-batch negatives: the triplet sampler without popularity columns; its negative is ignored
+            sampler = DeviceSampler(data, device, False)
+        else:
+            sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs)
     elif args.sampler == "device":
         sampler = DeviceSampler(data, device, with_pop)
     else:

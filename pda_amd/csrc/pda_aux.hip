@@ -113,6 +113,25 @@ __global__ void __launch_bounds__(64) sample_batches_kernel(SampleArgs a, int n_
     sample_one(a, r);
 }
 
+__global__ void counter_add_kernel(uint64_t* c, uint64_t inc) { *c += inc; }
+
+// The three triplet entry points.  counter: the step is `step` plus *step_dev (the _dev variants; without it the two are null);
+// n_batches 0: one batch by sample_kernel, else [n_batches][B] buffers by sample_batches_kernel.
+int sample_triplets(bool counter, int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, int n_batches,
+                    const int64_t* train_indptr, const int32_t* train_indices, const int32_t* train_slots, int neg_lo, int neg_hi,
+                    const float* pop_matrix, int n_slots, uint64_t seed, uint64_t step, const uint64_t* step_dev, uint64_t* step_next,
+                    int32_t* pos, int32_t* neg, float* pos_pop, float* neg_pop, void* stream) {
+    const SampleArgs a{users, user_pool, train_indptr, train_indices, train_slots, pop_matrix, pos, neg, pos_pop, neg_pop,
+                       seed, step, B, n_pool, gen_users, neg_lo, neg_hi, n_slots, step_dev, step_next};
+    if (!triplet_sample_ok(a, counter)) return PDA_ERR_ARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const unsigned blocks = (unsigned)((B + 63) / 64);
+    if (n_batches) hipLaunchKernelGGL(sample_batches_kernel, dim3(blocks, (unsigned)n_batches), dim3(64), 0, s, a, n_batches);
+    else hipLaunchKernelGGL(sample_kernel, dim3(blocks), dim3(64), 0, s, a);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -246,36 +265,17 @@ extern "C" int pda_sample_triplets(int32_t* users, int gen_users, const int32_t*
                                    const int32_t* train_slots, int neg_lo, int neg_hi, const float* pop_matrix,
                                    int n_slots, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg,
                                    float* pos_pop, float* neg_pop, void* stream) {
-    if (!users || !train_indptr || !train_indices || !pos || !neg || B <= 0 || neg_hi <= neg_lo) return PDA_ERR_ARG;
-    if (gen_users && n_pool <= 0) return PDA_ERR_ARG;
-    if (pop_matrix && (!pos_pop || !neg_pop || n_slots <= 0)) return PDA_ERR_ARG;
-    SampleArgs a{users, user_pool, train_indptr, train_indices, train_slots, pop_matrix, pos, neg, pos_pop, neg_pop,
-                 seed, step, B, n_pool, gen_users, neg_lo, neg_hi, n_slots, nullptr, nullptr};
-    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    PDA_CHECK_LAUNCH();
-    return PDA_OK;
+    return sample_triplets(false, users, gen_users, user_pool, n_pool, B, 0, train_indptr, train_indices, train_slots, neg_lo, neg_hi, pop_matrix,
+                           n_slots, seed, step, nullptr, nullptr, pos, neg, pos_pop, neg_pop, stream);
 }
-
-namespace {
-__global__ void counter_add_kernel(uint64_t* c, uint64_t inc) { *c += inc; }
-}  // namespace
 
 extern "C" int pda_sample_triplets_dev(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B,
                                        const int64_t* train_indptr, const int32_t* train_indices,
                                        const int32_t* train_slots, int neg_lo, int neg_hi, const float* pop_matrix,
                                        int n_slots, uint64_t seed, const uint64_t* step_dev, uint64_t* step_next, int32_t* pos,
                                        int32_t* neg, float* pos_pop, float* neg_pop, void* stream) {
-    if (!users || !train_indptr || !train_indices || !pos || !neg || !step_dev || B <= 0 || neg_hi <= neg_lo) return PDA_ERR_ARG;
-    if (step_next == step_dev) return PDA_ERR_ARG;      // other workgroups may still be reading *step_dev
-    if (gen_users && n_pool <= 0) return PDA_ERR_ARG;
-    if (pop_matrix && (!pos_pop || !neg_pop || n_slots <= 0)) return PDA_ERR_ARG;
-    SampleArgs a{users, user_pool, train_indptr, train_indices, train_slots, pop_matrix, pos, neg, pos_pop, neg_pop,
-                 seed, 0, B, n_pool, gen_users, neg_lo, neg_hi, n_slots, step_dev, step_next};
-    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    PDA_CHECK_LAUNCH();
-    return PDA_OK;
+    return sample_triplets(true, users, gen_users, user_pool, n_pool, B, 0, train_indptr, train_indices, train_slots, neg_lo, neg_hi, pop_matrix,
+                           n_slots, seed, 0, step_dev, step_next, pos, neg, pos_pop, neg_pop, stream);
 }
 
 extern "C" int pda_group_triplets_by_pos_batches(int32_t* users, int32_t* pos, int32_t* neg, float* pos_pop, float* neg_pop, int B,
@@ -286,19 +286,11 @@ extern "C" int pda_sample_batches_dev(int32_t* users, int gen_users, const int32
                                       int neg_hi, const float* pop_matrix, int n_slots, uint64_t seed, const uint64_t* step_dev,
                                       uint64_t* step_next, int32_t* pos, int32_t* neg, float* pos_pop, float* neg_pop, int group_by_pos,
                                       void* stream) {
-    if (!users || !train_indptr || !train_indices || !pos || !neg || !step_dev || B <= 0 || n_batches <= 0 || n_batches > 65535 ||
-        neg_hi <= neg_lo)
-        return PDA_ERR_ARG;
-    if (step_next == step_dev) return PDA_ERR_ARG;
-    if (gen_users && n_pool <= 0) return PDA_ERR_ARG;
-    if (pop_matrix && (!pos_pop || !neg_pop || n_slots <= 0)) return PDA_ERR_ARG;
-    SampleArgs a{users, user_pool, train_indptr, train_indices, train_slots, pop_matrix, pos, neg, pos_pop, neg_pop,
-                 seed, 0, B, n_pool, gen_users, neg_lo, neg_hi, n_slots, step_dev, step_next};
-    hipLaunchKernelGGL(sample_batches_kernel, dim3((unsigned)((B + 63) / 64), (unsigned)n_batches), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a, n_batches);
-    PDA_CHECK_LAUNCH();
-    if (group_by_pos) return pda_group_triplets_by_pos_batches(users, pos, neg, pos_pop, neg_pop, B, n_batches, stream);
-    return PDA_OK;
+    if (n_batches <= 0 || n_batches > 65535) return PDA_ERR_ARG;
+    const int rc = sample_triplets(true, users, gen_users, user_pool, n_pool, B, n_batches, train_indptr, train_indices, train_slots, neg_lo, neg_hi,
+                                   pop_matrix, n_slots, seed, 0, step_dev, step_next, pos, neg, pos_pop, neg_pop, stream);
+    if (rc != PDA_OK || !group_by_pos) return rc;
+    return pda_group_triplets_by_pos_batches(users, pos, neg, pos_pop, neg_pop, B, n_batches, stream);
 }
 
 extern "C" int pda_counter_add(uint64_t* counter, uint64_t inc, void* stream) {

@@ -800,18 +800,13 @@ extern "C" int pda_bpr_step_sample_f32(float* U, float* I, const int32_t* users,
     update_mode &= ~(PDA_UPD_ANY_ORDER | PDA_UPD_USERS_DISTINCT);
     if (update_mode != PDA_UPD_SGD_FUSED && update_mode != PDA_UPD_NONE) return PDA_ERR_ARG;
     // the sampler job: validated like pda_sample_triplets_dev; its outputs must not be this step's inputs
-    if (!next->users || !next->train_indptr || !next->train_indices || !next->pos || !next->neg || !next->step_dev || next->B <= 0 ||
-        next->neg_hi <= next->neg_lo)
-        return PDA_ERR_ARG;
-    if (next->step_next == next->step_dev) return PDA_ERR_ARG;
-    if (next->gen_users && next->n_pool <= 0) return PDA_ERR_ARG;
-    if (next->pop_matrix && (!next->pos_pop || !next->neg_pop || next->n_slots <= 0)) return PDA_ERR_ARG;
-    if (next->users == users || next->pos == pos || next->neg == neg) return PDA_ERR_ARG;
-    StepArgs a{U, I, users, pos, neg, pos_pop, neg_pop, nullptr, nullptr, nullptr, nullptr, nullptr, loss_acc,
-               B, 1.0f / (float)B, regs / reg_div, lr, update_mode, 0, d, U, I, any_order};
     SampleArgs sa{next->users, next->user_pool, next->train_indptr, next->train_indices, next->train_slots, next->pop_matrix,
                   next->pos, next->neg, next->pos_pop, next->neg_pop, next->seed, 0, next->B, next->n_pool, next->gen_users,
                   next->neg_lo, next->neg_hi, next->n_slots, next->step_dev, next->step_next};
+    if (!triplet_sample_ok(sa, true)) return PDA_ERR_ARG;
+    if (next->users == users || next->pos == pos || next->neg == neg) return PDA_ERR_ARG;
+    StepArgs a{U, I, users, pos, neg, pos_pop, neg_pop, nullptr, nullptr, nullptr, nullptr, nullptr, loss_acc,
+               B, 1.0f / (float)B, regs / reg_div, lr, update_mode, 0, d, U, I, any_order};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (d) {
         case 32: return launch_step<32>(a, s, &sa);
@@ -836,15 +831,12 @@ extern "C" int pda_bpr_train_steps_f32(float* U, float* I, int d, float regs, fl
     const int B = set0->B;
     for (int q = 0; q < 2; ++q) {
         const pda_sample_job* j = sets[q];
-        if (!j->users || !j->train_indptr || !j->train_indices || !j->pos || !j->neg || j->B != B || B <= 0 || j->neg_hi <= j->neg_lo)
-            return PDA_ERR_ARG;
-        if (j->gen_users && j->n_pool <= 0) return PDA_ERR_ARG;
-        if (j->pop_matrix && (!j->pos_pop || !j->neg_pop || j->n_slots <= 0)) return PDA_ERR_ARG;
+        t.sa[q] = SampleArgs{j->users, j->user_pool, j->train_indptr, j->train_indices, j->train_slots, j->pop_matrix, j->pos, j->neg,
+                             j->pos_pop, j->neg_pop, j->seed, 0, B, j->n_pool, j->gen_users, j->neg_lo, j->neg_hi, j->n_slots, nullptr, nullptr};
+        if (j->B != B || !triplet_sample_ok(t.sa[q], false)) return PDA_ERR_ARG;
         if ((j->pos_pop == nullptr) != (j->neg_pop == nullptr)) return PDA_ERR_ARG;
         t.a[q] = StepArgs{U, I, j->users, j->pos, j->neg, j->pos_pop, j->neg_pop, nullptr, nullptr, nullptr, nullptr, nullptr, loss_acc,
                           B, 1.0f / (float)B, regs / reg_div, lr, update_mode, 0, d, U, I, any_order};
-        t.sa[q] = SampleArgs{j->users, j->user_pool, j->train_indptr, j->train_indices, j->train_slots, j->pop_matrix, j->pos, j->neg,
-                             j->pos_pop, j->neg_pop, j->seed, 0, B, j->n_pool, j->gen_users, j->neg_lo, j->neg_hi, j->n_slots, nullptr, nullptr};
     }
     if (set0->users == set1->users || set0->pos == set1->pos || set0->neg == set1->neg) return PDA_ERR_ARG;
     t.step_ctr = step_ctr;

@@ -210,29 +210,24 @@ struct DiceSampleArgs {
     uint64_t* step_next;        // optional: receives *step_dev + 1
 };
 
-// one thread = one triplet.  The user and the positive: sample_one's statements (pda_sample.h) without time slots, so that a row draws what
-// pda_sample_triplets draws for the same (seed, step, row).
+// one thread = one triplet.  The step, the user, the positive and the rejection loop are the pieces sample_one is made of (pda_sample.h; no
+// time slots here): a row draws the user and the positive that pda_sample_triplets draws for the same (seed, step, row).  PNSM's own: the two
+// ranges of `order` around the positive's popularity, the coin between them, the mask.
 __global__ void __launch_bounds__(64) dice_sample_kernel(DiceSampleArgs a) {
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (r >= a.B) return;
-    if (a.step_dev) {
-        const uint64_t cur = *a.step_dev;
-        a.step += cur;
-        if (a.step_next && r == 0) *a.step_next = cur + 1;
-    }
+    a.step = sample_step(a.step, a.step_dev, a.step_next, r == 0);
     const float margin = a.margin_dev ? *a.margin_dev : a.margin;
     int u;
     if (a.gen_users) {
-        const uint64_t key = mix64(a.seed ^ mix64(a.step));
-        const uint32_t x = a.B <= a.n_pool ? feistel_perm((uint32_t)r, (uint32_t)a.n_pool, key) : bounded(draw(a.seed, a.step, r, 7), a.n_pool);
-        u = a.user_pool ? a.user_pool[x] : (int)x;
+        u = sample_user(a.seed, a.step, r, a.B, a.n_pool, a.user_pool);
         a.users[r] = u;
     } else {
         u = a.users[r];
     }
     const int64_t b = a.indptr[u], e = a.indptr[u + 1];
     const int len = (int)(e - b);
-    int p = len == 0 ? 0 : a.indices[b + (int)bounded(draw(a.seed, a.step, r, 0), len)];
+    int p = len == 0 ? 0 : a.indices[b + sample_pos_index(a.seed, a.step, r, len)];
     if ((unsigned)p >= (unsigned)a.n_items) p = 0;      // (memory safety only: the train lists hold ids of the catalogue)
     // H = [hi_at, n_items) and L = [0, lo_end) of `order`, in fp32 like the restatement (tests/dice_ref.py)
     const float P = (float)a.pop[p], above = P + margin, below = P - margin;
@@ -254,17 +249,10 @@ __global__ void __launch_bounds__(64) dice_sample_kernel(DiceSampleArgs a) {
     else if (nL == 0) whole = true;
     const int start = whole ? 0 : (fromH ? hi_at : 0);
     const uint32_t span = (uint32_t)(whole ? a.n_items : (fromH ? nH : nL));
-    int n = 0;
-    for (uint32_t k = 0; k < 4096; ++k) {   // rejection against the (sorted) train row
-        const int at = start + (int)bounded(draw(a.seed, a.step, r, 16 + k), span);
-        n = whole ? at : a.order[at];
-        int64_t l = b, h = e;
-        while (l < h) {
-            const int64_t mid = (l + h) >> 1;
-            if (a.indices[mid] < n) l = mid + 1; else h = mid;
-        }
-        if (!(l < e && a.indices[l] == n)) break;
-    }
+    const int n = sample_negative(a.seed, a.step, r, kNegDraw, span, a.indices, b, e, [&](uint32_t x) {
+        const int at = start + (int)x;
+        return whole ? at : a.order[at];
+    });
     a.pos[r] = p;
     a.neg[r] = n;
     a.mask[r] = whole ? (uint8_t)(a.pop[n] > a.pop[p]) : (uint8_t)fromH;
@@ -272,8 +260,18 @@ __global__ void __launch_bounds__(64) dice_sample_kernel(DiceSampleArgs a) {
 
 bool dice_d_ok(int d) { return d == 32 || d == 64 || d == 128; }       // (the width of ONE embedding: rows of 2 d floats)
 
-int launch_sample(const DiceSampleArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(dice_sample_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+// Both PNSM entry points.  counter (pda_dice_sample_dev): the step and the margin are read on the device; else both travel by value, the
+// three device pointers are null, and the margin is checked here.
+int dice_sample(bool counter, int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, const int64_t* train_indptr,
+                const int32_t* train_indices, int n_items, const int32_t* order, const int32_t* sorted_pop, const int32_t* pop, float margin,
+                const float* margin_dev, uint64_t seed, uint64_t step, const uint64_t* step_dev, uint64_t* step_next, int32_t* pos, int32_t* neg,
+                uint8_t* mask, void* stream) {
+    if (!sample_call_ok(users, train_indptr, train_indices, pos, neg, gen_users, n_pool, counter, step_dev, step_next)) return PDA_ERR_ARG;
+    if (!order || !sorted_pop || !pop || !mask || B <= 0 || n_items <= 0) return PDA_ERR_ARG;
+    if (counter ? !margin_dev : !(margin >= 0.f)) return PDA_ERR_ARG;
+    const DiceSampleArgs a{users, user_pool, train_indptr, train_indices, order, sorted_pop, pop, pos, neg, mask, seed, step, margin, B, n_pool,
+                           gen_users, n_items, margin_dev, step_dev, step_next};
+    hipLaunchKernelGGL(dice_sample_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
@@ -342,25 +340,14 @@ extern "C" int pda_dice_adam_step_f32(float* U, float* mU, float* vU, float* gU,
 extern "C" int pda_dice_sample(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, const int64_t* train_indptr,
                                const int32_t* train_indices, int n_items, const int32_t* order, const int32_t* sorted_pop, const int32_t* pop,
                                float margin, uint64_t seed, uint64_t step, int32_t* pos, int32_t* neg, uint8_t* mask, void* stream) {
-    if (!users || !train_indptr || !train_indices || !order || !sorted_pop || !pop || !pos || !neg || !mask || B <= 0 || n_items <= 0)
-        return PDA_ERR_ARG;
-    if (gen_users && n_pool <= 0) return PDA_ERR_ARG;
-    if (!(margin >= 0.f)) return PDA_ERR_ARG;
-    DiceSampleArgs a{users, user_pool, train_indptr, train_indices, order, sorted_pop, pop, pos, neg, mask, seed, step, margin, B, n_pool,
-                     gen_users, n_items, nullptr, nullptr, nullptr};
-    return launch_sample(a, reinterpret_cast<hipStream_t>(stream));
+    return dice_sample(false, users, gen_users, user_pool, n_pool, B, train_indptr, train_indices, n_items, order, sorted_pop, pop, margin, nullptr,
+                       seed, step, nullptr, nullptr, pos, neg, mask, stream);
 }
 
 extern "C" int pda_dice_sample_dev(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, const int64_t* train_indptr,
                                    const int32_t* train_indices, int n_items, const int32_t* order, const int32_t* sorted_pop,
                                    const int32_t* pop, const float* margin_dev, uint64_t seed, const uint64_t* step_dev, uint64_t* step_next,
                                    int32_t* pos, int32_t* neg, uint8_t* mask, void* stream) {
-    if (!users || !train_indptr || !train_indices || !order || !sorted_pop || !pop || !pos || !neg || !mask || !margin_dev || !step_dev ||
-        B <= 0 || n_items <= 0)
-        return PDA_ERR_ARG;
-    if (step_next == step_dev) return PDA_ERR_ARG;      // other workgroups may still be reading *step_dev
-    if (gen_users && n_pool <= 0) return PDA_ERR_ARG;
-    DiceSampleArgs a{users, user_pool, train_indptr, train_indices, order, sorted_pop, pop, pos, neg, mask, seed, 0, 0.f, B, n_pool, gen_users,
-                     n_items, margin_dev, step_dev, step_next};
-    return launch_sample(a, reinterpret_cast<hipStream_t>(stream));
+    return dice_sample(true, users, gen_users, user_pool, n_pool, B, train_indptr, train_indices, n_items, order, sorted_pop, pop, 0.f, margin_dev,
+                       seed, 0, step_dev, step_next, pos, neg, mask, stream);
 }

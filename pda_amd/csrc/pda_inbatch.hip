@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include "pda_common.h"
 #include "pda_train_common.h"
+#include "pda_sample.h"
 #include "pda_hip_inbatch.h"
 
 namespace {
@@ -421,15 +422,7 @@ __global__ void __launch_bounds__(256) inbatch_mask_kernel(const int32_t* users,
         const int u = users[r];
         if (c < B && c != r && (unsigned)u < n_users && (unsigned)pos[r] < n_items) {
             const int n = pos[c];
-            if ((unsigned)n < n_items && (unsigned)users[c] < n_users) {
-                const int64_t e = indptr[u + 1];
-                int64_t lo = indptr[u], hi = e;
-                while (lo < hi) {                   // (the membership test of the samplers)
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (indices[mid] < n) lo = mid + 1; else hi = mid;
-                }
-                bit = lo < e && indices[lo] == n;
-            }
+            if ((unsigned)n < n_items && (unsigned)users[c] < n_users) bit = train_row_has(indices, indptr[u], indptr[u + 1], n);
         }
     }
     const unsigned long long votes = __ballot(bit);                     // (every lane of the wave is here)

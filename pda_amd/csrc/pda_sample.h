@@ -1,5 +1,10 @@
-// Device-side BPR triplet sampler (N1, MF/train_new_api.py:366-412): shared by the stand-alone sampler kernel
-// (pda_aux.hip) and by the train step that draws the NEXT batch in spare workgroups of its own launch (pda_bpr_step.hip).
+// The device-side samplers (N1, MF/train_new_api.py:366-412).  The draws of a batch row -- the step, the user, the positive,
+// the membership test in the train row, the rejection loop of a negative -- are defined here once, and so is what every sampler
+// entry point checks on the host (sample_call_ok).  sample_one, the BPR triplet of a row, is composed of them; it is the body of
+// the stand-alone and the many-batches kernels (pda_aux.hip), of the train step that draws the NEXT batch in spare workgroups of
+// its own launch and of the looped trainer (pda_bpr_step.hip).  PNSM (pda_dice.hip) and the sampled-softmax sampler (pda_ssm.hip)
+// are the same pieces around their own negatives, the in-batch mask (pda_inbatch.hip) is the membership test: a row draws the
+// same user and positive under every method for one (seed, step, row), by construction.
 #pragma once
 #include "pda_common.h"
 
@@ -77,22 +82,66 @@ __device__ __forceinline__ void out_store(T* p, T v) {
     else *p = v;
 }
 
+// ---- the draws: each defined once, for every sampler kernel ---------------------------------------------------------------------
+// Draw numbers of a row: 0 the positive, 1 the time slot of an empty row, 2 PNSM's coin, 7 the user (with replacement), and from
+// kNegDraw on the tries of the negatives, kRejectTries apiece.
+constexpr uint32_t kNegDraw = 16, kRejectTries = 4096;
+
+// The step a launch draws with: `step` plus the device counter where there is one; the thread for which `first` holds hands
+// *step_dev + 1 on to step_next (a DIFFERENT location: other threads are still reading *step_dev).
+__device__ __forceinline__ uint64_t sample_step(uint64_t step, const uint64_t* step_dev, uint64_t* step_next, bool first) {
+    if (step_dev) {
+        const uint64_t cur = *step_dev;
+        step += cur;
+        if (step_next && first) *step_next = cur + 1;
+    }
+    return step;
+}
+
+// The user of row r.  B <= n_pool: distinct users (rd.sample, MF/train_new_api.py:380-381); else with replacement (:383)
+__device__ __forceinline__ int sample_user(uint64_t seed, uint64_t step, int r, int B, int n_pool, const int32_t* user_pool) {
+    const uint64_t key = mix64(seed ^ mix64(step));
+    const uint32_t x = B <= n_pool ? feistel_perm((uint32_t)r, (uint32_t)n_pool, key) : bounded(draw(seed, step, r, 7), n_pool);
+    return user_pool ? user_pool[x] : (int)x;
+}
+
+// Where in its train row (len > 0 entries) row r finds its positive, :392-396
+__device__ __forceinline__ int sample_pos_index(uint64_t seed, uint64_t step, int r, int len) {
+    return (int)bounded(draw(seed, step, r, 0), len);
+}
+
+// Is item n in the (sorted) train row indices[b, e)?  (hi declared before lo: the order in which the compiler gives the step
+// kernels of pda_bpr_step.hip the instructions they had before this was a function of its own -- profiles/sampler_pieces.txt)
+__device__ __forceinline__ bool train_row_has(const int32_t* indices, int64_t b, int64_t e, int n) {
+    int64_t hi = e, lo = b;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (indices[mid] < n) lo = mid + 1; else hi = mid;
+    }
+    return lo < e && indices[lo] == n;
+}
+
+// The negative of row r, :397-401: item_of(x), x uniform in [0, span), drawn again while the train row holds it; after
+// kRejectTries tries the last draw stays.  first_draw: kNegDraw (+ kRejectTries j for the j-th negative of a row).
+template <typename F>
+__device__ __forceinline__ int sample_negative(uint64_t seed, uint64_t step, int r, uint32_t first_draw, uint32_t span,
+                                               const int32_t* indices, int64_t b, int64_t e, F item_of) {
+    int n = 0;
+    for (uint32_t k = 0; k < kRejectTries; ++k) {
+        n = item_of(bounded(draw(seed, step, r, first_draw + k), span));
+        if (!train_row_has(indices, b, e, n)) break;
+    }
+    return n;
+}
+
 // one thread = one triplet r of the batch
 template <bool COH = false>
 __device__ __forceinline__ void sample_one(SampleArgs a, int r) {
     if (r >= a.B) return;
-    if (a.step_dev) {
-        const uint64_t cur = *a.step_dev;
-        a.step += cur;
-        if (a.step_next && r == 0) *a.step_next = cur + 1;
-    }
+    a.step = sample_step(a.step, a.step_dev, a.step_next, r == 0);
     int u;
     if (a.gen_users) {
-        const uint64_t key = mix64(a.seed ^ mix64(a.step));
-        // B <= n_pool: distinct users (rd.sample, MF/train_new_api.py:380-381); else with replacement (:383)
-        const uint32_t x = a.B <= a.n_pool ? feistel_perm((uint32_t)r, (uint32_t)a.n_pool, key)
-                                           : bounded(draw(a.seed, a.step, r, 7), a.n_pool);
-        u = a.user_pool ? a.user_pool[x] : (int)x;
+        u = sample_user(a.seed, a.step, r, a.B, a.n_pool, a.user_pool);
         out_store<COH>(&a.users[r], u);
     } else {
         u = a.users[r];
@@ -103,28 +152,36 @@ __device__ __forceinline__ void sample_one(SampleArgs a, int r) {
     if (len == 0) {  // :387-390
         p = 0;
         slot = a.n_slots > 0 ? (int)bounded(draw(a.seed, a.step, r, 1), a.n_slots) : 0;
-    } else {         // :392-396
-        const int idx = (int)bounded(draw(a.seed, a.step, r, 0), len);
+    } else {
+        const int idx = sample_pos_index(a.seed, a.step, r, len);
         p = a.indices[b + idx];
         slot = a.slots ? a.slots[b + idx] : 0;
     }
-    int n = a.neg_lo;
-    const uint32_t span = (uint32_t)(a.neg_hi - a.neg_lo);
-    for (uint32_t k = 0; k < 4096; ++k) {  // rejection against the (sorted) train row, :397-401
-        n = a.neg_lo + (int)bounded(draw(a.seed, a.step, r, 16 + k), span);
-        int64_t lo = b, hi = e;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.indices[mid] < n) lo = mid + 1; else hi = mid;
-        }
-        if (!(lo < e && a.indices[lo] == n)) break;
-    }
+    const int n = sample_negative(a.seed, a.step, r, kNegDraw, (uint32_t)(a.neg_hi - a.neg_lo), a.indices, b, e,
+                                  [&](uint32_t x) { return a.neg_lo + (int)x; });
     out_store<COH>(&a.pos[r], p);
     out_store<COH>(&a.neg[r], n);
     if (a.pop && a.pos_pop) {  // :402-403
         out_store<COH>(&a.pos_pop[r], a.pop[(size_t)p * a.n_slots + slot]);
         out_store<COH>(&a.neg_pop[r], a.pop[(size_t)n * a.n_slots + slot]);
     }
+}
+
+// (host) What every sampler entry point checks: the users, the train CSR and the two outputs every method has are there, users
+// can be drawn where they are to be, and with a device counter (counter: the _dev variants) step_dev is there and step_next is
+// another location -- other workgroups may still be reading *step_dev.  Sizes and ranges are each entry point's own.
+inline bool sample_call_ok(const void* users, const void* indptr, const void* indices, const void* out_a, const void* out_b, int gen_users,
+                           int n_pool, bool counter, const uint64_t* step_dev, const uint64_t* step_next) {
+    if (!users || !indptr || !indices || !out_a || !out_b) return false;
+    if (gen_users && n_pool <= 0) return false;
+    return !counter || (step_dev && step_next != step_dev);
+}
+
+// (host) a triplet sampler job as a whole; B is not capped
+inline bool triplet_sample_ok(const SampleArgs& a, bool counter) {
+    if (!sample_call_ok(a.users, a.indptr, a.indices, a.pos, a.neg, a.gen_users, a.n_pool, counter, a.step_dev, a.step_next)) return false;
+    if (a.B <= 0 || a.neg_hi <= a.neg_lo) return false;
+    return !(a.pop && (!a.pos_pop || !a.neg_pop || a.n_slots <= 0));
 }
 
 }  // namespace

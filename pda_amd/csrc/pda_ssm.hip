@@ -206,21 +206,16 @@ struct SsmSampleArgs {
     uint64_t* step_next;        // optional: receives *step_dev + 1 (a DIFFERENT location)
 };
 
-// users and positives: the expressions of sample_one (pda_sample.h) without slots and popularities; the thread of j == 0 writes them
+// The pieces of sample_one (pda_sample.h) without slots and popularities: every thread of a row finds the row's user, the thread of j == 0
+// writes it and the positive; negative j takes the tries [kNegDraw + kRejectTries j, + kRejectTries), so column 0 is the triplet's negative.
 __global__ void __launch_bounds__(64) ssm_sample_kernel(SsmSampleArgs a) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= (size_t)a.B * (size_t)a.N) return;
     const int r = (int)(i / (size_t)a.N), j = (int)(i % (size_t)a.N);
-    if (a.step_dev) {
-        const uint64_t cur = *a.step_dev;
-        a.step += cur;
-        if (a.step_next && i == 0) *a.step_next = cur + 1;
-    }
+    a.step = sample_step(a.step, a.step_dev, a.step_next, i == 0);
     int u;
     if (a.gen_users) {
-        const uint64_t key = mix64(a.seed ^ mix64(a.step));
-        const uint32_t x = a.B <= a.n_pool ? feistel_perm((uint32_t)r, (uint32_t)a.n_pool, key) : bounded(draw(a.seed, a.step, r, 7), a.n_pool);
-        u = a.user_pool ? a.user_pool[x] : (int)x;
+        u = sample_user(a.seed, a.step, r, a.B, a.n_pool, a.user_pool);
         if (j == 0) a.users[r] = u;
     } else {
         u = a.users[r];
@@ -228,20 +223,10 @@ __global__ void __launch_bounds__(64) ssm_sample_kernel(SsmSampleArgs a) {
     const int64_t b = a.indptr[u], e = a.indptr[u + 1];
     if (j == 0) {
         const int len = (int)(e - b);
-        a.pos[r] = len == 0 ? 0 : a.indices[b + (int)bounded(draw(a.seed, a.step, r, 0), len)];
+        a.pos[r] = len == 0 ? 0 : a.indices[b + sample_pos_index(a.seed, a.step, r, len)];
     }
-    int n = a.neg_lo;
-    const uint32_t span = (uint32_t)(a.neg_hi - a.neg_lo), base = 16u + 4096u * (uint32_t)j;
-    for (uint32_t k = 0; k < 4096; ++k) {  // rejection against the (sorted) train row
-        n = a.neg_lo + (int)bounded(draw(a.seed, a.step, r, base + k), span);
-        int64_t lo = b, hi = e;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.indices[mid] < n) lo = mid + 1; else hi = mid;
-        }
-        if (!(lo < e && a.indices[lo] == n)) break;
-    }
-    a.negs[i] = n;
+    a.negs[i] = sample_negative(a.seed, a.step, r, kNegDraw + kRejectTries * (uint32_t)j, (uint32_t)(a.neg_hi - a.neg_lo), a.indices, b, e,
+                                [&](uint32_t x) { return a.neg_lo + (int)x; });
 }
 
 // ---- Y[r] = X[r] / max(|X[r]|, 1e-12): d/4 lanes per row, the sum of squares in float64 (order: include/pda_hip_ssm.h) ---------------------------
@@ -294,17 +279,16 @@ SsmStepArgs step_args(const float* U, const float* I, size_t n_users, size_t n_i
                        1.0f / tau, regs / reg_div, (flags & PDA_UPD_ANY_ORDER) ? 1 : 0, (flags & PDA_UPD_USERS_DISTINCT) ? 1 : 0};
 }
 
-int check_sample(const int32_t* users, int gen_users, int n_pool, int B, int N, const int64_t* train_indptr, const int32_t* train_indices, int neg_lo,
-                 int neg_hi, const int32_t* pos, const int32_t* negs) {
-    if (!users || !train_indptr || !train_indices || !pos || !negs || B <= 0 || B > (1 << 22) || neg_hi <= neg_lo) return PDA_ERR_ARG;
-    if (N < 1 || N > PDA_SSM_MAX_NEGS) return PDA_ERR_ARG;
-    if (gen_users && n_pool <= 0) return PDA_ERR_ARG;
-    return PDA_OK;
-}
-
-int launch_sample(const SsmSampleArgs& a, hipStream_t s) {
-    const size_t n = (size_t)a.B * (size_t)a.N;         // <= 2^30: B <= 2^22, N <= 256
-    hipLaunchKernelGGL(ssm_sample_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a);
+// Both sampler entry points.  counter (pda_ssm_sample_dev): the step is read on the device; else it travels by value and the two are null.
+int ssm_sample(bool counter, int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, int N, const int64_t* train_indptr,
+               const int32_t* train_indices, int neg_lo, int neg_hi, uint64_t seed, uint64_t step, const uint64_t* step_dev, uint64_t* step_next,
+               int32_t* pos, int32_t* negs, void* stream) {
+    if (!sample_call_ok(users, train_indptr, train_indices, pos, negs, gen_users, n_pool, counter, step_dev, step_next)) return PDA_ERR_ARG;
+    if (B <= 0 || B > (1 << 22) || neg_hi <= neg_lo || N < 1 || N > PDA_SSM_MAX_NEGS) return PDA_ERR_ARG;
+    const SsmSampleArgs a{users, user_pool, train_indptr, train_indices, pos, negs, seed, step, B, N, n_pool, gen_users, neg_lo, neg_hi,
+                          step_dev, step_next};
+    const size_t n = (size_t)B * (size_t)N;             // <= 2^30: B <= 2^22, N <= 256
+    hipLaunchKernelGGL(ssm_sample_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
@@ -338,22 +322,15 @@ extern "C" int pda_ssm_adam_step_f32(float* U, float* mU, float* vU, float* gU, 
 extern "C" int pda_ssm_sample(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, int N, const int64_t* train_indptr,
                               const int32_t* train_indices, int neg_lo, int neg_hi, uint64_t seed, uint64_t step, int32_t* pos, int32_t* negs,
                               void* stream) {
-    const int rc = check_sample(users, gen_users, n_pool, B, N, train_indptr, train_indices, neg_lo, neg_hi, pos, negs);
-    if (rc != PDA_OK) return rc;
-    return launch_sample(SsmSampleArgs{users, user_pool, train_indptr, train_indices, pos, negs, seed, step, B, N, n_pool, gen_users, neg_lo, neg_hi,
-                                       nullptr, nullptr},
-                         reinterpret_cast<hipStream_t>(stream));
+    return ssm_sample(false, users, gen_users, user_pool, n_pool, B, N, train_indptr, train_indices, neg_lo, neg_hi, seed, step, nullptr, nullptr, pos,
+                      negs, stream);
 }
 
 extern "C" int pda_ssm_sample_dev(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, int N, const int64_t* train_indptr,
                                   const int32_t* train_indices, int neg_lo, int neg_hi, uint64_t seed, const uint64_t* step_dev,
                                   uint64_t* step_next, int32_t* pos, int32_t* negs, void* stream) {
-    const int rc = check_sample(users, gen_users, n_pool, B, N, train_indptr, train_indices, neg_lo, neg_hi, pos, negs);
-    if (rc != PDA_OK) return rc;
-    if (!step_dev || step_next == step_dev) return PDA_ERR_ARG;      // (other workgroups may still be reading *step_dev)
-    return launch_sample(SsmSampleArgs{users, user_pool, train_indptr, train_indices, pos, negs, seed, 0, B, N, n_pool, gen_users, neg_lo, neg_hi,
-                                       step_dev, step_next},
-                         reinterpret_cast<hipStream_t>(stream));
+    return ssm_sample(true, users, gen_users, user_pool, n_pool, B, N, train_indptr, train_indices, neg_lo, neg_hi, seed, 0, step_dev, step_next, pos,
+                      negs, stream);
 }
 
 extern "C" int pda_ssm_normalize_rows_f32(const float* X, size_t n_rows, int d, float* Y, void* stream) {

@@ -1396,6 +1396,16 @@ def sample_triplets(train_indptr, train_indices, B: int, *, seed: int, step: int
     return users, pos, neg, pp, pn
 
 
+def _step_slots(step_dev: torch.Tensor, parity: Optional[int]):
+    """-> (the slot of the device step counter a sampler reads, the slot that receives step + 1 or None).  parity None: the counter
+    is only read.  parity p on a two-slot counter: slot p is read, slot 1 - p written (never the slot other workgroups still read)."""
+    if parity is None:
+        return step_dev, None
+    if step_dev.numel() != 2:
+        raise ValueError("parity mode needs a two-slot step counter")
+    return step_dev[parity:parity + 1], step_dev[1 - parity:2 - parity]
+
+
 def sample_triplets_into(out, train_indptr, train_indices, *, seed: int, step_dev: torch.Tensor, user_pool=None, n_pool: int = 0,
                           train_slots=None, neg_range=(0, 0), pop_matrix=None, sort_by_pos: bool = False, advance: bool = True,
                           parity: Optional[int] = None):
@@ -1406,12 +1416,7 @@ def sample_triplets_into(out, train_indptr, train_indices, *, seed: int, step_de
     lib = _lib.load()
     users, pos, neg, pp, pn = out
     n_slots = pop_matrix.shape[1] if pop_matrix is not None else 0
-    if parity is None:
-        src, nxt = step_dev, None
-    else:
-        if step_dev.numel() != 2:
-            raise ValueError("parity mode needs a two-slot step counter")
-        src, nxt = step_dev[parity:parity + 1], step_dev[1 - parity:2 - parity]
+    src, nxt = _step_slots(step_dev, parity)
     check(lib.pda_sample_triplets_dev(ptr(users), 1, ptr(user_pool), int(n_pool), users.numel(), ptr(train_indptr),
                                       ptr(train_indices), ptr(train_slots), int(neg_range[0]), int(neg_range[1]),
                                       ptr(pop_matrix), n_slots, seed & (2 ** 64 - 1), ptr(src), ptr(nxt) if advance else None,
@@ -2249,13 +2254,7 @@ def dice_sample_into(out, train_indptr, train_indices, dp: DicePop, *, margin_de
     step_dev int64 [1]: read only.  step_dev int64 [2] + parity p: read from slot p, step + 1 stored to slot 1 - p (sample_triplets_into)."""
     out = _dice_sample_out(out[0].numel(), train_indptr.device, out)
     margin_dev = _need(margin_dev, torch.float32, "margin_dev")
-    step_dev = _need(step_dev, torch.int64, "step_dev")
-    if parity is None:
-        src, nxt = step_dev, None
-    else:
-        if step_dev.numel() != 2:
-            raise ValueError("parity mode needs a two-slot step counter")
-        src, nxt = step_dev[parity:parity + 1], step_dev[1 - parity:2 - parity]
+    src, nxt = _step_slots(_need(step_dev, torch.int64, "step_dev"), parity)
     check(_lib.load().pda_dice_sample_dev(ptr(out[0]), 1, ptr(user_pool), int(n_pool), out[0].numel(), ptr(_need(train_indptr, torch.int64, "train_indptr")),
                                           ptr(_need(train_indices, torch.int32, "train_indices")), dp.n_items, ptr(dp.order), ptr(dp.sorted_pop),
                                           ptr(dp.pop), ptr(margin_dev), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(out[1]), ptr(out[2]),
@@ -2792,13 +2791,7 @@ def ssm_sample_into(out, train_indptr, train_indices, *, seed: int, step_dev: to
     _ssm_sample_args(train_indptr, train_indices, B, negs.shape[1], neg_range, user_pool, n_pool)
     if int(n_pool) < 1:
         raise ValueError("SSM sampler: drawing users needs n_pool >= 1")
-    step_dev = _need(step_dev, torch.int64, "step_dev")
-    if parity is None:
-        src, nxt = step_dev, None
-    else:
-        if step_dev.numel() != 2:
-            raise ValueError("parity mode needs a two-slot step counter")
-        src, nxt = step_dev[parity:parity + 1], step_dev[1 - parity:2 - parity]
+    src, nxt = _step_slots(_need(step_dev, torch.int64, "step_dev"), parity)
     check(_lib.load().pda_ssm_sample_dev(ptr(users), 1, ptr(user_pool), int(n_pool), B, int(negs.shape[1]), ptr(train_indptr), ptr(train_indices),
                                          int(neg_range[0]), int(neg_range[1]), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(negs),
                                          stream_ptr()), "pda_ssm_sample_dev")

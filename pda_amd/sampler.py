@@ -141,45 +141,44 @@ class DeviceSampler:
         self.with_plan = False        # set by the trainer (--optimizer sgd): every batch comes with its pda_triplet_plan
         self.plan = None              # the plan of the batch handed out last
 
-    def _refill_ssm(self):
-        """The next `ahead` batches of mode="ssm", one pda_ssm_sample_dev launch each on the two-slot device counter (the protocol of the bpr
-        queue; bit for bit the batches of ops.ssm_sample(step = 1, 2, ..)).  Two queues in turn, as in _refill."""
-        B, n, N = self.data.batch_size, self.ahead, self.n_negs
-        if self._queue is None:
-            mk = lambda *shape: torch.empty(shape, dtype=torch.int32, device=self.device)      # noqa: E731
-            self._queues = [(mk(n, B), mk(n, B), mk(n, B, N)) for _ in range(2)]
+    def _next_queue(self, columns) -> int:
+        """The bookkeeping of both refills -> which of the two queues is to be filled (now self._queue).  Two queues in turn: a batch
+        handed out stays valid while the next `ahead` are drawn and consumed.  columns: (dtype or None, trailing shape) of each buffer
+        of a queue, [ahead, B, ...] each; allocated, with the two-slot device counter, on the first call and when ahead or B changed."""
+        B, n = self.data.batch_size, self.ahead
+        if self._queue is None or self._queue[0].shape != (n, B):
+            self._queues = [tuple(None if dt is None else torch.empty((n, B) + tail, dtype=dt, device=self.device) for dt, tail in columns)
+                            for _ in range(2)]
             self._ctr = torch.tensor([self.step, 0], dtype=torch.int64, device=self.device)      # (batch() has counted this one)
             self._calls = self._draws = 0
-        self._queue = self._queues[self._calls & 1]
-        for j in range(n):
+            self._plans = None
+        which = self._calls & 1
+        self._queue = self._queues[which]
+        self._calls += 1
+        self._left = n
+        return which
+
+    def _refill_ssm(self):
+        """The next `ahead` batches of mode="ssm", one pda_ssm_sample_dev launch each on the two-slot device counter (the protocol of the bpr
+        queue; bit for bit the batches of ops.ssm_sample(step = 1, 2, ..))."""
+        self._next_queue([(torch.int32, ()), (torch.int32, ()), (torch.int32, (self.n_negs,))])
+        for j in range(self.ahead):
             ops.ssm_sample_into(tuple(q[j] for q in self._queue), self.indptr, self.indices, seed=self.seed, step_dev=self._ctr,
                                 parity=self._draws & 1, user_pool=self.pool, n_pool=self.pool.numel(), neg_range=self.neg_range)
             self._draws += 1
-        self._calls += 1
-        self._left = n
 
     def _refill(self):
-        B, n = self.data.batch_size, self.ahead
-        if self._queue is None or self._queue[0].shape != (n, B):
-            mk = lambda dt: torch.empty((n, B), dtype=dt, device=self.device)
-            # two queues in turn: a batch handed out stays valid while the next `ahead` are drawn and consumed
-            self._queues = [(mk(torch.int32), mk(torch.int32), mk(torch.int32), mk(torch.float32) if self.with_pop else None,
-                             mk(torch.float32) if self.with_pop else None) for _ in range(2)]
-            self._ctr = torch.tensor([self.step, 0], dtype=torch.int64, device=self.device)      # (batch() has counted this one)
-            self._calls = 0
-            self._plans = None
-        self._queue = self._queues[self._calls & 1]
-        ops.sample_batches_into(self._queue, self.indptr, self.indices, seed=self.seed, step_dev=self._ctr, parity=self._calls & 1,
+        pop_dt = torch.float32 if self.with_pop else None
+        which = self._next_queue([(torch.int32, ())] * 3 + [(pop_dt, ())] * 2)
+        ops.sample_batches_into(self._queue, self.indptr, self.indices, seed=self.seed, step_dev=self._ctr, parity=which,
                                 user_pool=self.pool, n_pool=self.pool.numel(), train_slots=self.slots if self.with_pop else None,
                                 neg_range=self.neg_range, pop_matrix=self.pop)
         if self.with_plan:
             # the plans of the whole queue in ONE launch (one workgroup per batch), like the batches themselves
             if self._plans is None:
-                nb = ops.triplet_plan_bytes(B)
-                self._plans = [torch.empty((n, nb), dtype=torch.uint8, device=self.device) for _ in range(2)]
-            ops.triplet_plan(self._queue[0], self._queue[1], self._queue[2], out=self._plans[self._calls & 1])
-        self._calls += 1
-        self._left = n
+                nb = ops.triplet_plan_bytes(self.data.batch_size)
+                self._plans = [torch.empty((self.ahead, nb), dtype=torch.uint8, device=self.device) for _ in range(2)]
+            ops.triplet_plan(self._queue[0], self._queue[1], self._queue[2], out=self._plans[which])
 
     def start_epoch(self, epoch: int) -> float:
         """mode="dice": the margin's schedule -- multiplied by margin_decay at the start of every epoch after the first.  -> the margin."""

@@ -283,6 +283,53 @@ def test_sampler_with_given_users_and_the_margin_schedule(dev):
         np.testing.assert_array_equal(t.cpu().numpy(), ref[name], err_msg=name)
 
 
+def test_sampler_dev_walks_the_two_slot_counter_and_reads_a_one_slot_one(dev):
+    """pda_dice_sample_dev over consecutive steps: parity 0 then parity 1 on a two-slot counter (each call reads its slot and stores step + 1 into
+    the other), then a one-slot counter that is only read.  B = 37 of 50 users (distinct, drawn by the kernel), 40 items, user 3 without train
+    items, user 5 with all items but one.  Every output of every batch equals tests/dice_ref.pnsm at that step."""
+    from pda_amd import ops
+    n_users, n_items, B, M, seed, step = 50, 40, 37, 2.0, 0xD1B54A32D192ED03, 28
+    rng = np.random.default_rng(8)
+    rows = [np.sort(rng.permutation(n_items)[:rng.integers(1, 13)]) for _ in range(n_users)]
+    rows[3] = np.zeros(0, np.int64)
+    rows[5] = np.delete(np.arange(n_items), 17)
+    indptr = np.zeros(n_users + 1, np.int64)
+    indptr[1:] = np.cumsum([len(r) for r in rows])
+    indices = np.concatenate(rows).astype(np.int32)
+    pop = np.bincount(indices, minlength=n_items).astype(np.int32)
+    ip, ix = to(dev, indptr, indices)
+    dp = ops.DicePop(ix, n_items)
+    margin_dev = torch.tensor([M], dtype=torch.float32, device=dev)
+    out = tuple(torch.full((B,), -1, dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.int32, torch.uint8))
+
+    def check(at, what):
+        ref = pnsm(seed, at, B, indptr, indices, pop, M, n_pool=n_users)
+        assert len(np.unique(ref["users"])) == B
+        for name, t in zip(("users", "pos", "neg", "mask"), out):
+            np.testing.assert_array_equal(t.cpu().numpy(), ref[name], err_msg="%s, %s" % (name, what))
+        return ref
+
+    ctr = torch.tensor([step, -1], dtype=torch.int64, device=dev)
+    ops.dice_sample_into(out, ip, ix, dp, margin_dev=margin_dev, seed=seed, step_dev=ctr, parity=0, n_pool=n_users)
+    first = check(step, "parity 0")
+    assert ctr.tolist() == [step, step + 1]
+    ops.dice_sample_into(out, ip, ix, dp, margin_dev=margin_dev, seed=seed, step_dev=ctr, parity=1, n_pool=n_users)
+    second = check(step + 1, "parity 1")
+    assert ctr.tolist() == [step + 2, step + 1]
+    assert not np.array_equal(first["users"], second["users"])          # (two steps, two batches)
+    one = torch.tensor([step + 2], dtype=torch.int64, device=dev)
+    ops.dice_sample_into(out, ip, ix, dp, margin_dev=margin_dev, seed=seed, step_dev=one, n_pool=n_users)
+    third = check(step + 2, "one slot, read only")
+    assert one.tolist() == [step + 2] and ctr.tolist() == [step + 2, step + 1]
+    # the two rows the data was built for are in all three batches (the step was chosen for it): user 3 has positive 0; user 5's negative is the
+    # one item it does not own where its side of the catalogue holds it (the first batch), else the draw of the last try
+    for ref in (first, second, third):
+        assert ref["pos"][ref["users"] == 3].tolist() == [0]
+        r = np.nonzero(ref["users"] == 5)[0]
+        assert r.size == 1 and (ref["neg"][r[0]] == 17) == (ref["rejections"][r[0]] < REJECT_CAP)
+    assert first["neg"][first["users"] == 5].tolist() == [17] and second["rejections"].max() == REJECT_CAP
+
+
 # ---- evaluation: the raw head at row width 2d -----------------------------------------------------------------------------------------------
 def test_evaluation_paths_serve_the_concatenated_tables(dev):
     from pda_amd import ops

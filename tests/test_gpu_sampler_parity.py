@@ -278,3 +278,21 @@ def test_extreme_inputs_through_the_step_that_samples_the_next_batch(dev, extrem
     torch.cuda.synchronize()
     same(nxt, _extreme_ref(x, x["step"] + 1), "bpr_step_and_sample, next batch")
     assert ctr.tolist() == [x["step"] + 1, x["step"] + 2]
+
+
+def test_the_triplet_sampler_has_no_cap_on_the_batch_where_the_ssm_sampler_has_one(dev, world):
+    """B = 2^22 + 1: one row more than pda_ssm_sample takes (its [B, N] block is indexed in 32 bits).  The triplet sampler draws it; rows at
+    both ends and in the middle equal the restatement.  The SSM sampler refuses it as an invalid argument."""
+    from pda_amd import _lib, ops
+    w = world
+    B, n_pool, seed, step = (1 << 22) + 1, 5000, TOP, 5
+    ip, ix = to(dev, w["indptr"], w["indices"])
+    got = ops.sample_triplets(ip, ix, B, seed=seed, step=step, n_pool=n_pool, neg_range=(0, w["n_items"]))
+    torch.cuda.synchronize()
+    rows = np.concatenate([np.arange(64), np.arange(B // 2, B // 2 + 64), np.arange(B - 64, B)])
+    ref = sr.sample(seed, step, B, w["indptr"], w["indices"], n_pool=n_pool, neg_range=(0, w["n_items"]), rows=rows)
+    same([None if t is None else t[torch.from_numpy(rows).to(dev)] for t in got], ref, "B = 2^22 + 1")
+    with pytest.raises(_lib.PdaHipError, match="invalid argument"):
+        ops.ssm_sample(ip, ix, B, 1, seed=seed, step=step, neg_range=(0, w["n_items"]), n_pool=n_pool)
+    u, p, n = ops.ssm_sample(ip, ix, 64, 1, seed=seed, step=step, neg_range=(0, w["n_items"]), n_pool=n_pool)      # (the call itself is sound)
+    assert n.shape == (64, 1)

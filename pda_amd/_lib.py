@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
-pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h and
-pda_hip_inbatch.h).
+pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
+pda_hip_inbatch.h and pda_hip_dns.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -255,6 +255,14 @@ INBATCH_SIGNATURES = {
                                        _vp, _sz, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_dns.h (dynamic hard-negative sampling: `--neg_sampler dns`)
+DNS_MAX_CANDIDATES = 256
+_dns_head = [_vp, _vp, _sz, _sz, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _u64]
+DNS_SIGNATURES = {
+    "pda_dns_sample_f32": (_i, _dns_head + [_u64] + [_vp] * 8),
+    "pda_dns_sample_f32_dev": (_i, _dns_head + [_vp, _vp] + [_vp] * 8),
+}
+
 _lib = None
 
 
@@ -275,7 +283,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
-            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()):
+            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -83,9 +83,9 @@ __device__ __forceinline__ void out_store(T* p, T v) {
 }
 
 // ---- the draws: each defined once, for every sampler kernel ---------------------------------------------------------------------
-// Draw numbers of a row: 0 the positive, 1 the time slot of an empty row, 2 PNSM's coin, 7 the user (with replacement), and from
-// kNegDraw on the tries of the negatives, kRejectTries apiece.
-constexpr uint32_t kNegDraw = 16, kRejectTries = 4096;
+// Draw numbers of a row: 0 the positive, 1 the time slot of an empty row, 2 PNSM's coin, 3 DNS's pick among the best candidates
+// (kPickDraw, pda_dns.hip), 7 the user (with replacement), and from kNegDraw on the tries of the negatives, kRejectTries apiece.
+constexpr uint32_t kPickDraw = 3, kNegDraw = 16, kRejectTries = 4096;
 
 // The step a launch draws with: `step` plus the device counter where there is one; the thread for which `first` holds hands
 // *step_dev + 1 on to step_next (a DIFFERENT location: other threads are still reading *step_dev).

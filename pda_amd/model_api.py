@@ -754,6 +754,39 @@ def check_ssm(args):
                              "positives), got %s" % (ops.INBATCH_MAX_B, B))
 
 
+def check_dns(args):
+    """--neg_sampler dns: refuse, before anything is built, what dynamic negative sampling has no path for.  Every message names its flag.
+    The sampler scores its candidates on the live fp32 tables of a BPRMF / PD model right before the step that trains on them."""
+    mode = getattr(args, "neg_sampler", "uniform")
+    if mode == "uniform":
+        return
+    if mode != "dns":
+        raise ValueError("--neg_sampler must be uniform or dns, got %s" % (mode,))
+    train = getattr(args, "train", "normal")
+    if train not in ("normal", "s_condition"):
+        raise NotImplementedError("--train %s: --neg_sampler dns goes with --train normal (the raw head) and --train s_condition (the popularity "
+                                  "head) only" % (train,))
+    if getattr(args, "model", "mf") != "mf":
+        raise NotImplementedError("--model %s: --neg_sampler dns scores candidates on the embedding tables themselves, a LightGCN's scores live on "
+                                  "the propagated tables (--model mf)" % (args.model,))
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --neg_sampler dns scores fp32 tables only" % (args.table_dtype,))
+    if getattr(args, "adam_sweep", "auto") in ("replay", "replay_fast"):
+        raise NotImplementedError("--adam_sweep %s: --neg_sampler dns reads whole tables before every step, a replayed table's idle rows are stale "
+                                  "then (--adam_sweep auto | sweep)" % (args.adam_sweep,))
+    if getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("adam_exact_lazy: --neg_sampler dns reads whole tables before every step, a lazy table's idle rows are stale then")
+    if getattr(args, "sampler", "device") != "device":
+        raise NotImplementedError("--sampler %s: --neg_sampler dns is the device sampler's (--sampler device)" % (args.sampler,))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --neg_sampler dns trains on one GPU (no item shards)" % (args.gpus,))
+    M, N = getattr(args, "dns_candidates", 16), getattr(args, "dns_topn", 1)
+    if int(M) != M or not 1 <= int(M) <= ops.DNS_MAX_CANDIDATES:
+        raise ValueError("--dns_candidates must be an integer in 1 .. %d, got %s" % (ops.DNS_MAX_CANDIDATES, M))
+    if int(N) != N or not 1 <= int(N) <= int(M):
+        raise ValueError("--dns_topn must be an integer in 1 .. --dns_candidates = %d, got %s" % (int(M), N))
+
+
 class SSMBPRMF(BPRMF):
     """BPR-MF tables trained with the sampled-softmax loss (include/pda_hip_ssm.h): one positive and --ssm_negs sampled negatives
     per row under a softmax with temperature --ssm_tau, on cosine similarity with --ssm_norm 1.  Fetchables and checkpoint layout are those of

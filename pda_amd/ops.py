@@ -2939,3 +2939,112 @@ def inbatch_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, ws, 
                                                 int(cache_policy), ptr(ws), ws.numel(), ptr(loss_acc), stream_ptr()),
           "pda_inbatch_adam_step_f32")
     mark_modified(U, I)
+
+
+# ---- dynamic hard-negative sampling (include/pda_hip_dns.h) -----------------------------------------------------------------------------------------
+DNS_MAX_CANDIDATES = _lib.DNS_MAX_CANDIDATES
+DNS_EMBED_SIZES = (32, 64, 128, 256)
+
+
+def check_dns_sizes(n_cands, topn, what: str = "DNS"):
+    """1 <= n_cands <= DNS_MAX_CANDIDATES, 1 <= topn <= n_cands, both whole numbers (the library's own limits, met before the device is touched)."""
+    if int(n_cands) != n_cands or not 1 <= int(n_cands) <= DNS_MAX_CANDIDATES:
+        raise ValueError(f"{what}: n_cands, the candidates per row, must be an integer in 1 .. {DNS_MAX_CANDIDATES}, got {n_cands}")
+    if int(topn) != topn or not 1 <= int(topn) <= int(n_cands):
+        raise ValueError(f"{what}: topn must be an integer in 1 .. n_cands = {int(n_cands)}, got {topn}")
+
+
+def _dns_args(U, I, train_indptr, train_indices, train_slots, B, M, topn, head, neg_range, pop_matrix, user_pool, n_pool):
+    """The host-side checks of both DNS front-ends -> (n_slots, lo, hi)."""
+    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
+    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1] or U.shape[1] not in DNS_EMBED_SIZES or U.shape[0] < 1 or I.shape[0] < 1:
+        raise ValueError(f"DNS sampler: U float32 [n_users, d], I float32 [n_items, d], d one of {DNS_EMBED_SIZES}, got {tuple(U.shape)}, {tuple(I.shape)}")
+    check_dns_sizes(M, topn, "DNS sampler")
+    if int(B) < 1 or int(B) > (1 << 22):
+        raise ValueError("DNS sampler: B in 1 .. 2^22")
+    lo, hi = int(neg_range[0]), int(neg_range[1])
+    if not 0 <= lo < hi <= I.shape[0]:
+        raise ValueError(f"DNS sampler: neg_range = (lo, hi) with 0 <= lo < hi <= n_items = {I.shape[0]}, got ({lo}, {hi})")
+    if head not in (HEAD_RAW, HEAD_POP):
+        raise ValueError("DNS sampler: head is HEAD_RAW or HEAD_POP")
+    _need(train_indptr, torch.int64, "train_indptr"), _need(train_indices, torch.int32, "train_indices")
+    if train_indptr.numel() != U.shape[0] + 1:
+        raise ValueError("DNS sampler: train_indptr holds n_users + 1 offsets")
+    _need(train_slots, torch.int32, "train_slots", optional=True)
+    if user_pool is not None and _need(user_pool, torch.int32, "user_pool").numel() < int(n_pool):
+        raise ValueError("user_pool holds n_pool int32")
+    n_slots = 0
+    if pop_matrix is not None:
+        pop_matrix = _need(pop_matrix, torch.float32, "pop_matrix")
+        if pop_matrix.dim() != 2 or pop_matrix.shape[0] != I.shape[0] or pop_matrix.shape[1] < 1:
+            raise ValueError("DNS sampler: pop_matrix float32 [n_items, n_slots >= 1]")
+        n_slots = pop_matrix.shape[1]
+    elif head == HEAD_POP:
+        raise ValueError("DNS sampler: HEAD_POP scores (elu(u . i) + 1) * pop and needs pop_matrix")
+    return n_slots, lo, hi
+
+
+def dns_sample(U, I, train_indptr, train_indices, B: int, *, n_cands: int, topn: int = 1, head: int = HEAD_RAW, seed: int, step: int, neg_range,
+               users=None, user_pool=None, n_pool: int = 0, train_slots=None, pop_matrix=None, want_cands: bool = False, check_ids: bool = True):
+    """pda_dns_sample_f32 -> (users, pos, neg, pos_pop|None, neg_pop|None) on the device: the users, positives and slots of
+    sample_triplets(seed, step); neg is one of the topn best-scoring (head, on the tables as they are NOW) of the n_cands candidates a row draws
+    as ssm_sample draws its columns.  want_cands: (.., cand i32 [B, M], cand_score f32 [B, M], pick_col i32 [B]) behind the five.
+    users given: they are kept (check_ids: refused unless all lie in [0, n_users); costs a host sync)."""
+    n_slots, lo, hi = _dns_args(U, I, train_indptr, train_indices, train_slots, B, n_cands, topn, head, neg_range, pop_matrix, user_pool, n_pool)
+    dev = U.device
+    gen = users is None
+    if gen:
+        if int(n_pool) < 1:
+            raise ValueError("DNS sampler: drawing users needs n_pool >= 1")
+        users = torch.empty(B, dtype=torch.int32, device=dev)
+    else:
+        if _need(users, torch.int32, "users").numel() != B:
+            raise ValueError("users holds B int32")
+        if check_ids and B > 0 and not bool(((users >= 0) & (users < U.shape[0])).all()):
+            raise ValueError("DNS sampler: a user id lies outside [0, n_users)")
+    M = int(n_cands)
+    pos = torch.empty(B, dtype=torch.int32, device=dev)
+    neg = torch.empty(B, dtype=torch.int32, device=dev)
+    pp = pn = cand = score = col = None
+    if pop_matrix is not None:
+        pp, pn = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+    if want_cands:
+        cand, score = torch.empty((B, M), dtype=torch.int32, device=dev), torch.empty((B, M), dtype=torch.float32, device=dev)
+        col = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.load().pda_dns_sample_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], U.shape[1], ptr(users), int(gen), ptr(user_pool), int(n_pool), int(B),
+                                         ptr(train_indptr), ptr(train_indices), ptr(train_slots), ptr(pop_matrix), n_slots, lo, hi, M, int(topn),
+                                         int(head), seed & (2 ** 64 - 1), int(step), ptr(pos), ptr(neg), ptr(pp), ptr(pn), ptr(cand), ptr(score),
+                                         ptr(col), stream_ptr()), "pda_dns_sample_f32")
+    return (users, pos, neg, pp, pn) + ((cand, score, col) if want_cands else ())
+
+
+def dns_sample_into(out, U, I, train_indptr, train_indices, *, n_cands: int, topn: int = 1, head: int = HEAD_RAW, seed: int, step_dev: torch.Tensor,
+                    neg_range, parity: Optional[int] = None, user_pool=None, n_pool: int = 0, train_slots=None, pop_matrix=None, cands=None):
+    """pda_dns_sample_f32_dev: one batch into out = (users, pos, neg, pos_pop|None, neg_pop|None), the step read from device memory
+    (graph-capturable; the users are drawn).  step_dev int64 [1]: read only.  step_dev int64 [2] + parity p: read from slot p, step + 1 stored
+    to slot 1 - p (sample_triplets_into).  cands: optional (cand i32 [B, M], cand_score f32 [B, M], pick_col i32 [B]) to fill as well."""
+    users, pos, neg, pp, pn = out
+    users, pos, neg = _need(users, torch.int32, "users"), _need(pos, torch.int32, "pos"), _need(neg, torch.int32, "neg")
+    B, M = users.numel(), int(n_cands)
+    if pos.numel() != B or neg.numel() != B:
+        raise ValueError("DNS sampler output: users [B], pos [B], neg [B]")
+    n_slots, lo, hi = _dns_args(U, I, train_indptr, train_indices, train_slots, B, n_cands, topn, head, neg_range, pop_matrix, user_pool, n_pool)
+    if int(n_pool) < 1:
+        raise ValueError("DNS sampler: drawing users needs n_pool >= 1")
+    if (pp is None) != (pn is None) or (pp is not None and pop_matrix is None):
+        raise ValueError("DNS sampler output: pos_pop and neg_pop come together, and with a pop_matrix")
+    for t, name in ((pp, "pos_pop"), (pn, "neg_pop")):
+        if t is not None and _need(t, torch.float32, name).numel() != B:
+            raise ValueError(f"{name} holds B float32")
+    cand = score = col = None
+    if cands is not None:
+        cand, score, col = cands
+        cand, score, col = _need(cand, torch.int32, "cand"), _need(score, torch.float32, "cand_score"), _need(col, torch.int32, "pick_col")
+        if tuple(cand.shape) != (B, M) or tuple(score.shape) != (B, M) or col.numel() != B:
+            raise ValueError("DNS sampler output: cand [B, M], cand_score [B, M], pick_col [B]")
+    src, nxt = _step_slots(_need(step_dev, torch.int64, "step_dev"), parity)
+    check(_lib.load().pda_dns_sample_f32_dev(ptr(U), ptr(I), U.shape[0], I.shape[0], U.shape[1], ptr(users), 1, ptr(user_pool), int(n_pool), B,
+                                             ptr(train_indptr), ptr(train_indices), ptr(train_slots), ptr(pop_matrix), n_slots, lo, hi, M, int(topn),
+                                             int(head), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(neg), ptr(pp), ptr(pn), ptr(cand),
+                                             ptr(score), ptr(col), stream_ptr()), "pda_dns_sample_f32_dev")
+    return out

@@ -83,6 +83,9 @@ _EXTENSION_FLAGS = [
     ("bias_groups", int, 10, "--bias_report: popularity groups of the items, 1 .. 64 (group 0 = the most popular)"),
     ("bias_group_by", str, "interactions", "--bias_report: interactions = groups of equal train interactions | items = groups of equal item counts"),
     ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
+    ("neg_sampler", str, "uniform", "where a triplet's negative comes from: uniform = one uniform draw outside the user's train items (the reference) | dns = dynamic hard-negative sampling, DNS(M, N): one of the --dns_topn best-scoring of --dns_candidates uniform draws under the current tables (include/pda_hip_dns.h; --train normal | s_condition, fp32 tables, the device sampler, one GPU)"),
+    ("dns_candidates", int, 16, "DNS (--neg_sampler dns): candidates M drawn and scored per triplet, 1 .. 256 (1: the uniform sampler's batches, bit for bit)"),
+    ("dns_topn", int, 1, "DNS: the negative is drawn uniformly from the N best of the M candidates, 1 .. --dns_candidates (1: the best one, the classic DNS)"),
     ("ssm_source", str, "sampled", "SSM (--train ssm): where a row's negatives come from.  sampled = --ssm_negs uniform draws per row | batch = the other rows' positives (in-batch softmax, include/pda_hip_inbatch.h: --batch_size - 1 shared negatives per row, --batch_size in 2 .. 16384)"),
     ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1"),
     ("ssm_mask_train", int, 1, "SSM with --ssm_source batch: 1 leaves a column out of a row's softmax when its item is a train item of the row's user (the sampled path rejects the same items when it draws); 0 | 1"),

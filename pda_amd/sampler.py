@@ -13,6 +13,8 @@ yielding, per step, a tuple of sequences of length batch_size -- (users, pos, ne
                      (last bullet).  mode="dice": PNSM, DICE's popularity-margin negative sampler
                      (pda_dice_sample): (users, pos, neg, mask), and the margin's schedule (start_epoch).
                      mode="ssm": the sampled-softmax batches (pda_ssm_sample_dev): (users, pos, negs [B, n_negs]).
+                     mode="dns": the batches of mode="bpr" with the negative picked among the topn best-scoring of n_cands
+                     uniform candidates under the model's live tables (pda_dns_sample_f32; set_tables).
     HostDiceSampler  PNSM in numpy, the debugging twin of mode="dice" (--sampler host): the same algorithm on the
                      host's random streams -- NOT draw for draw the device stream.
 """
@@ -105,9 +107,13 @@ class DeviceSampler:
     batch handed out is a row view of the queue and stays valid until `ahead` further batches have been taken."""
 
     def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0, mode: str = "bpr",
-                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0):
-        if mode not in ("bpr", "dice", "ssm"):
-            raise ValueError("DeviceSampler mode must be 'bpr', 'dice' or 'ssm', not %r" % (mode,))
+                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0, n_cands: int = 0, topn: int = 1):
+        if mode not in ("bpr", "dice", "ssm", "dns"):
+            raise ValueError("DeviceSampler mode must be 'bpr', 'dice', 'ssm' or 'dns', not %r" % (mode,))
+        if mode == "dns":
+            ops.check_dns_sizes(n_cands, topn, "mode='dns'")
+        self.n_cands, self.topn = int(n_cands), int(topn)
+        self._tables = None           # mode="dns": set_tables
         if mode == "ssm":
             if with_pop or temp_slots > 0:
                 raise ValueError("mode='ssm' draws (users, pos, negs): no popularity columns (with_pop), no time slots (temp_slots)")
@@ -131,6 +137,9 @@ class DeviceSampler:
             self.pop = torch.arange(temp_slots, dtype=torch.float32, device=self.device).repeat(data.n_items, 1).contiguous()
         elif with_pop:
             self.pop = torch.as_tensor(np.ascontiguousarray(data.expo_popularity, dtype=np.float32), device=self.device)
+        # mode="dns": the head the candidates are scored by -- the popularity head on the very matrix the columns are read from (PD/PDA),
+        # the raw dot product otherwise (the time-slot matrix of temp_slots is no popularity)
+        self.dns_head = ops.HEAD_POP if (with_pop and temp_slots <= 0) else ops.HEAD_RAW
         self.neg_range = neg_range or (0, data.n_items)
         self.step = 0
         self.ahead = max(1, int(ahead))
@@ -186,9 +195,29 @@ class DeviceSampler:
             self.margin *= self.margin_decay
         return self.margin
 
+    def set_tables(self, fn):
+        """mode="dns": fn() -> (U, I), the LIVE fp32 tables the candidates are scored on (the trainer hands it over once the Recommender
+        exists; called at every batch, so it may return new tensors)."""
+        self._tables = fn
+
+    def _batch_dns(self):
+        """One pda_dns_sample_f32 launch on the tables as they stand: no look-ahead queue, the tables move between steps.  With popularity
+        columns the candidates are scored by the popularity head on the matrix the columns are read from, else by the raw dot product."""
+        if self._tables is None:
+            raise ValueError("mode='dns' scores its candidates on the model's tables: call set_tables(fn) before the first batch")
+        U, I = self._tables()
+        u, p, n, pp, pn = ops.dns_sample(U, I, self.indptr, self.indices, self.data.batch_size, n_cands=self.n_cands, topn=self.topn,
+                                         head=self.dns_head, seed=self.seed, step=self.step,
+                                         neg_range=self.neg_range, user_pool=self.pool, n_pool=self.pool.numel(),
+                                         train_slots=self.slots if self.with_pop else None, pop_matrix=self.pop)
+        self.plan = ops.triplet_plan(u, p, n)[0] if self.with_plan else None
+        return (u, p, n, pp, pn) if self.with_pop else (u, p, n)
+
     def batch(self):
         self.step += 1
-        if self.mode == "dice":       # one pda_dice_sample launch per step; the margin travels by value
+        if self.mode == "dns":
+            return self._batch_dns()
+        if self.mode == "dice":     # one pda_dice_sample launch per step; the margin travels by value
             self.plan = None
             return ops.dice_sample(self.indptr, self.indices, self.dice_pop, self.data.batch_size, margin=self.margin, seed=self.seed,
                                    step=self.step, user_pool=self.pool, n_pool=self.pool.numel())

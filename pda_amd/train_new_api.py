@@ -30,7 +30,7 @@ from . import ops
 from .exposure import BiasReport, EvalResult
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
 from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice,
-                        check_ips, check_lightgcn, check_macr, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
+                        check_dns, check_ips, check_lightgcn, check_macr, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -168,6 +168,13 @@ class DatasetApi_Model:
         # the device sampler draws a batch's users without replacement (like the reference, :380-381): the fused SGD step may
         # then store its user rows plainly (PDA_UPD_USERS_DISTINCT)
         self.Recommender.users_distinct = bool(getattr(generator_sampler, "distinct_users", False))
+        if getattr(generator_sampler, "mode", None) == "dns":
+            #  the DNS sampler scores its candidates on the live tables: the reverse of the set_train_graph hand-over above.  A
+            # deferred Adam would leave idle rows stale under the sampler, so the dense sweep is the update whatever the size of the tables
+            check_dns(args)
+            rec = self.Recommender
+            rec.adam_exact_lazy = False
+            generator_sampler.set_tables(lambda: (rec.weights["user_embedding"], rec.weights["item_embedding"]))
         self.n_items = data_config["n_items"]
         self._shard = topk_shard            # optional pda_amd.dist.ItemShardedTopK (multi-GPU evaluation)
         self.Create_Recommendation(topk_max)
@@ -529,6 +536,7 @@ def main(argv=None):
         check_lightgcn(args)
     elif args.model != "mf":
         raise NotImplementedError("--model %s: mf | lightgcn" % args.model)
+    check_dns(args)                        # (--neg_sampler dns)
     if args.train == "dice":
         check_dice(args)
         if args.test not in ("normal", "dice"):
@@ -629,6 +637,8 @@ def main(argv=None):
             sampler = DeviceSampler(data, device, False)
         else:
             sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs)
+    elif getattr(args, "neg_sampler", "uniform") == "dns":       # (check_dns has refused everything but --train normal | s_condition on the device sampler)
+        sampler = DeviceSampler(data, device, with_pop, mode="dns", n_cands=args.dns_candidates, topn=args.dns_topn)
     elif args.sampler == "device":
         sampler = DeviceSampler(data, device, with_pop)
     else:

@@ -193,6 +193,8 @@ int pda_score_topk_ordered_bf16(const uint16_t* U, const uint16_t* I_shard, cons
  *   pda_item_prep4_bytes(n, d)
  *   pda_item_prep4_f32 / _bf16(I_shard, pop_shard|NULL, order|NULL, n, d, prep, stream)
  *        pop_shard NULL: a prep for PDA_HEAD_RAW only; with pop_shard: PDA_HEAD_POP, and PDA_HEAD_RAW without early_stop
+ *        Precondition: the sum of squares of every item row neither overflows nor underflows in fp32 (the padded norms are formed from it;
+ *        single squares may be subnormal: under gradual underflow a stored residual norm can fall short of the exact one by at most 1e-21).
  *   pda_item_prep4_check(prep, n, d, stream)   optional, synchronises: PDA_ERR_ARG if `order` was not a permutation
  *   pda_score_topk4_auto_splits(n_users_blk, n_items_local, d)   the n_splits the call picks for n_splits <= 0
  *   pda_score_topk4_f32 / _bf16(.. as pda_score_topk_ordered_*, without hist_indices_ord: train items are masked at the

@@ -48,8 +48,10 @@ def oracle_lists(U, I, pop, users, rows, K):
 
 
 def suffix_bounds(I, pop):
-    """sufA, sufB per 64-item tile of the visiting order (|pop| descending, stable) as tile_bound4_kernel / suffix_max4_kernel pad them;
-    -> (order, sufA, sufB)"""
+    """sufA, sufB per 64-item tile of the visiting order (|pop| descending, stable): a LOWER, tighter restatement of what tile_bound4_kernel /
+    suffix_max4_kernel store, not the kernels' own padding -- the norm here is padded by 1.0000005, the kernel's by 1.0009765625 * 1.0001.  sufA is
+    bit-equal to the kernel's, sufB never above it (tests/test_prep_host.py holds both against the fp32 emulation of the prep), and a larger bound
+    decides later, never earlier: what is proved on these bounds holds on the device's.  -> (order, sufA, sufB)"""
     order = np.argsort(-np.abs(pop), kind="stable")
     p = np.abs(pop[order]).astype(F)
     nr = np.sqrt((I[order].astype(np.float64) ** 2).sum(1)).astype(F) * F(1.0000005)      # (the kernel's norm is an upper bound of the exact one)

@@ -122,6 +122,17 @@ int pda_score_topk4_phase_mask_offsets(int n_users_blk, int n_items_local, int d
  * The word at workspace + 32 says which ran: 0 = the one kernel, 5 = the two.  Blocks of more than 2^21 users (2 GB of scores: the score
  * kernel's 32-bit offsets) run the one kernel whatever the bit. */
 #define PDA_SWEEP_WARM_ONE_KERNEL 2048
+/* early_stop bits 12 .. 14 of pda_score_topk4_* (results never depend on them).  The sweep of the huge geometry shares the test-free tail
+ * of every workgroup (the half-tiles behind its decided half-tile: scored, but no pair of them can enter a list) with the workgroups that
+ * have finished: chunks of local half-tiles claimed from one record per workgroup in the workspace -- where a split has at least 2 048
+ * half-tiles (shorter ones are not worth the extra entries of the loop; the two test bits below share at any length).  Behind a call, workspace + 36 = the
+ * chunks run for another workgroup and workspace + 40 = the half-tiles in them; workspace + 8 and + 28 are added by whoever ran a half-tile.
+ *   PDA_SWEEP_TAIL_NO_SHARE       every workgroup runs its own tail in one piece (A/B measurements, tests)
+ *   PDA_SWEEP_TAIL_OTHERS_FIRST   tests: a workgroup looks at the other workgroups' records before it runs its own range
+ *   PDA_SWEEP_TAIL_MIN2           tests: the smallest chunk is 2 half-tiles instead of 32 */
+#define PDA_SWEEP_TAIL_NO_SHARE 4096
+#define PDA_SWEEP_TAIL_OTHERS_FIRST 8192
+#define PDA_SWEEP_TAIL_MIN2 16384
 
 /* ---- train step variants -------------------------------------------------------------------------------------------------------------- */
 /* ---- The exact mini-batch SGD step without atomics (round 3; pda_bpr_plan.hip): plan + two launches -------------------------

@@ -130,6 +130,11 @@ struct Args4 {
     // the dense call's exact warm-up as two kernels (warm_score5_kernel, warm_select5_kernel): [256 local item ids of the warm positions |
     // n_users_blk x 64 warm_tiles scores as ordered uints, 0 = not a candidate].  NULL: warm4_kernel.
     uint32_t* wscore;
+    // the huge geometry's shared test-free tail (pda_tail_share.h, pda_v5_sweep.h): one record per workgroup of sweep5_kernel, zeroed by the
+    // call's counter memset.  NULL: every workgroup runs its own tail (PDA_SWEEP_TAIL_NO_SHARE, and a phase-2 call, which has no memset).
+    uint64_t* tail_rec;
+    unsigned tail_min;           // the smallest chunk, in half-tiles (kTailMinChunk; PDA_SWEEP_TAIL_MIN2: 2)
+    int tail_others_first;       // PDA_SWEEP_TAIL_OTHERS_FIRST (tests): a workgroup looks at the other records before it runs its own range
 };
 
 // What ONE call launches.  run_score4 forms every decision here, once, from the call's arguments; the launchers follow it and ask nothing
@@ -2380,12 +2385,15 @@ int user_tile4(int d) { return d == 64 ? Geo4<64>::UT : d == 128 ? Geo4<128>::UT
 // every d may live in HBM) | Bloom filters, 128 B per user | warm-position train-item masks, 32 B per user and split | regrouping: 1024 bins,
 // bin and sweep row of every user]
 struct Ws4 {
-    size_t lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, kth, wscore, total;
+    size_t tailrec, lists, bloom, hmask, regroup, handover, ufrag, unorm, seed, kth, wscore, total;
 };
 static Ws4 ws4_layout(int n_users_blk, int d, int n_splits) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     Ws4 w{};
-    w.lists = al(pda_score_topk_workspace_bytes(n_users_blk));
+    // the records of the huge geometry's shared tail (pda_tail_share.h), 8 bytes per workgroup of sweep5_kernel (512-user tiles at d = 256):
+    // directly behind the counters, so that ONE memset zeroes both
+    w.tailrec = al(pda_score_topk_workspace_bytes(n_users_blk));
+    w.lists = al(w.tailrec + ((size_t)n_users_blk + 511) / 512 * (size_t)n_splits * 8);
     size_t b = w.lists;
     const size_t ut = 1024;             // (the widest user tile of any geometry: the huge one's)
     b += ((size_t)n_users_blk + ut - 1) / ut * (size_t)n_splits * ut * kCap4 * 8 + 256;
@@ -2424,9 +2432,11 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     if (!U || !I_shard || !prep || !users || !out_keys || !workspace) return PDA_ERR_ARG;
     if (n_users_blk <= 0 || n_items_local <= 0 || item_offset < 0) return PDA_ERR_ARG;
     if (K < 1 || K > PDA_MAX_K) return PDA_ERR_ARG;
-    if (early_stop < 0 || (early_stop & ~0xFFF) != 0) return PDA_ERR_ARG;
+    if (early_stop < 0 || (early_stop & ~0x7FFF) != 0) return PDA_ERR_ARG;
     const bool warm_per_split = (early_stop & PDA_SWEEP_WARM_PER_SPLIT) != 0;
     const bool warm_one_kernel = (early_stop & PDA_SWEEP_WARM_ONE_KERNEL) != 0;
+    const bool tail_share = (early_stop & PDA_SWEEP_TAIL_NO_SHARE) == 0;
+    const bool tail_others_first = (early_stop & PDA_SWEEP_TAIL_OTHERS_FIRST) != 0, tail_min2 = (early_stop & PDA_SWEEP_TAIL_MIN2) != 0;
     // geometry hints (Geo4<D, 3>, sweep5_kernel): results do not depend on them, and every geometry takes any n_splits and any user count
     // (tests/test_gpu_score_topk.py runs each with 1 / 2 / 3 / 8 splits and ragged blocks)
     // (PDA_SWEEP_FEW_CANDIDATES, PDA_SWEEP_WIDE and the two PDA_SWEEP_HUGE_* sub-variants named geometries that round 5 removed -- each
@@ -2549,6 +2559,19 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
         g.seed_out = reinterpret_cast<float*>(wsb + W.seed);
         g.seed = g.seed_out;
     }
+    // the shared test-free tail: where this call zeroes the records (the memset below)
+    const bool counters_reset = (phase & 1) || from_empty;
+    // ... and where a split is long enough to pay for it: a shared range costs its owner some five more entries of the test-free loop (~3 us
+    // each) and every workgroup a scan of the records, against a few per cent of the range's run time (1.15 us per half-tile at d = 128).
+    // Measured on config 3 (profiles/tail_share.txt section 5): 98 half-tiles per split 3 % SLOWER, 1 248 the same, 6 242 faster.  The
+    // test switches share at any length.
+    constexpr int kTailShareMinHalfTiles = 2048;
+    const bool tail_long = 2 * (L.n_tiles / n_splits) >= kTailShareMinHalfTiles || tail_min2 || tail_others_first;
+    if (c.sweep == Call4::kSweep5 && tail_share && counters_reset && tail_long) {
+        g.tail_rec = reinterpret_cast<uint64_t*>(wsb + W.tailrec);
+        g.tail_min = tail_min2 ? 2u : kTailMinChunk;
+        g.tail_others_first = tail_others_first ? 1 : 0;
+    }
     if (c.warm == Call4::kWarmTwo) g.wscore = reinterpret_cast<uint32_t*>(wsb + W.wscore);
     if (c.bloom) g.bloom = reinterpret_cast<uint32_t*>(wsb + W.bloom);
     if (mask_from_table) {
@@ -2562,7 +2585,9 @@ int run_score4(const void* U, const void* I_shard, bool bf16, const void* prep, 
     }
 
     // ---- the launches
-    if (((phase & 1) || from_empty) && hipMemsetAsync(workspace, 0, pda_score_topk_workspace_bytes(n_users_blk), s) != hipSuccess) return PDA_ERR_LAUNCH;
+    // (the counters and, behind them, the records of the shared tail -- for every geometry and whether or not the call shares, on purpose: at
+    // most a few KB more of the same memset, and no record of this workspace ever outlives a resetting call)
+    if (counters_reset && hipMemsetAsync(workspace, 0, W.lists, s) != hipSuccess) return PDA_ERR_LAUNCH;
     if (c.bloom) {
         hipLaunchKernelGGL(hist_bloom4_kernel, dim3((unsigned)((n_users_blk + 31) / 32)), dim3(256), 0, s, users, hist_indptr, hist_indices,
                            hist_row_mode, n_users_blk, const_cast<uint32_t*>(g.bloom), g.prep_hdr, pop_head ? 1 : 0);
@@ -2726,9 +2751,16 @@ extern "C" int pda_topk_seed_pick(const float* bounds, const int32_t* counts, in
 }
 
 #ifdef PDA_V5_EXITPROF
-extern "C" int pda_debug_v5_exitprof(unsigned long long* out, int n_workgroups) {     /* [n_workgroups][4 waves][8] of the LAST sweep5_kernel launch */
+extern "C" int pda_debug_v5_exitprof(unsigned long long* out, int n_workgroups) {     /* [n_workgroups][4 waves][kXpWords] of the LAST sweep5_kernel launch */
     if (!out || n_workgroups < 1 || n_workgroups > kXpMaxWg) return PDA_ERR_ARG;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pda_v5_exitprof), (size_t)n_workgroups * 4 * 8 * sizeof(unsigned long long)) != hipSuccess) return PDA_ERR_LAUNCH;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pda_v5_exitprof), (size_t)n_workgroups * 4 * kXpWords * sizeof(unsigned long long)) != hipSuccess) return PDA_ERR_LAUNCH;
+    return PDA_OK;
+}
+extern "C" int pda_debug_v5_exitprof_words(void) { return kXpWords; }
+/* n > 0: every workgroup runs its own test-free range in n equal pieces and nobody shares (the cost of one more entry of the loop); 0: off */
+extern "C" int pda_debug_v5_tail_pieces(int n) {
+    if (n < 0) return PDA_ERR_ARG;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(pda_v5_tail_pieces), &n, sizeof(int)) != hipSuccess) return PDA_ERR_LAUNCH;
     return PDA_OK;
 }
 #endif

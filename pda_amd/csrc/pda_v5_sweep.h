@@ -30,6 +30,8 @@
 //     decided half-tile is worked out at every (re-)entry from the thresholds as they are then (they only rise); the tested body gets it as
 //     its end, so every flag below it has been acted on when it returns, and Loop6Free::run takes over from there to the end of the split.
 //     In config 3 that is 94 % of the half-tiles (workspace + 28 counts them: stats["huge_free_halftiles"]).  -DPDA_V5_NO_FREE: never.
+//     The test-free range is run at the END of the kernel, behind the workgroup's rows, in chunks claimed from a record that the other
+//     workgroups claim from as well once they have nothing left of their own (pda_tail_share.h; the comment at next_chunk below).
 // Everything else is generation 4's: warm4_kernel's exact lists (handed over through the workspace), the packed keys, the epilogue.
 // Popularity head, d = 64 / 128, dense sweeps (no early termination); selected by the caller's hint PDA_SWEEP_HUGE.
 #pragma once
@@ -39,15 +41,20 @@
 #include "pda_v6_loop_asm.h"           // the loop, on v_mfma_f32_16x16x32_bf16 (tools/gen_v6_loop_asm.py)
 #endif
 #include "pda_v6_free_asm.h"           // its test-free bodies (tools/gen_v6_loop_asm.py --free: made by the Makefile, not kept in the repository)
+#include "pda_tail_share.h"            // the shared test-free tail: claim / publish over one atomic word per workgroup (host-compilable)
 
 #ifdef PDA_V5_EXITPROF
 // profiling build (tools/build_variant.sh exitprof -DPDA_V5_EXITPROF; read by tools/time_huge_exits.py): what a wave spends OUTSIDE its asm loops,
 // in ticks of the constant 100 MHz wall clock -- per (workgroup, wave): [0] in extract, [1] in rescore_ring behind the extracts, [2] from the end
 // of an exit's work to the next call of a loop body (thresholds, the decided half-tile, the barrier; the AGPR reload and the restart of the DMA
 // pipeline happen inside the asm statement and are not separable here), [3] everything between a loop's return and the next loop's call,
-// [4] exits (returns with a flag), [5] the whole kernel, [6] before the first entry, [7] sort and emit.  No code in the product build.
-constexpr int kXpMaxWg = 4096;
-__device__ unsigned long long pda_v5_exitprof[kXpMaxWg * 4 * 8];
+// [4] exits (returns with a flag), [5] the whole kernel (work for other workgroups included), [6] before the first entry, [7] sort and emit,
+// [8] the workgroup's decided half-tile (the half-tile at which it went test-free), [9] the wall clock, from the kernel's start, at which it
+// entered the test-free body, [10] half-tiles run for other workgroups, [11] the half-tiles of its split.  No code in the product build.
+// pda_v5_tail_pieces (pda_debug_v5_tail_pieces): n > 0 -- every workgroup runs its own test-free range in n equal pieces, nobody shares.
+constexpr int kXpMaxWg = 4096, kXpWords = 12;
+__device__ unsigned long long pda_v5_exitprof[kXpMaxWg * 4 * kXpWords];
+__device__ int pda_v5_tail_pieces;
 #define XP(...) __VA_ARGS__
 #else
 #define XP(...)
@@ -82,7 +89,7 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x % g.n_splits, utile = blockIdx.x / g.n_splits;
-    XP(unsigned long long xp[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long xp_k0 = wall_clock64(); unsigned long long xp_out = 0, xp_re = 0;)
+    XP(unsigned long long xp[kXpWords] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long xp_k0 = wall_clock64(); unsigned long long xp_out = 0, xp_re = 0;)
     // the exact lists: the hand-over rows of the warm-up IN PLACE (a one-call sweep; the rows of the workgroup's padding do not exist
     // and are never touched: no candidate, no output), else the workgroup's rows of the workspace
     uint64_t* lists = g.handover != nullptr ? g.handover + ((size_t)split * g.n_users_blk + (size_t)utile * UT) * kCap4
@@ -176,11 +183,53 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
     }
     __syncthreads();
 
+    // ---- the shared test-free tail (pda_tail_share.h).  Behind a workgroup's decided half-tile the loop only scores: no
+    // accumulator is read, nothing is written, and the operands are the item image and the workgroup's user image -- WHICH CU runs such a
+    // half-tile changes no result -- nor does WHEN: a workgroup that reaches its test-free part publishes the range in its record, rescores
+    // what its rings hold and emits its rows, and only then claims the range back chunk by chunk; when its own record is exhausted it claims
+    // chunks from the record with the most left and runs them on the victim's user image and tile sequence.  (One place, at the end of the
+    // kernel, runs every test-free half-tile: nothing of the tested part is live there.)  Nobody waits for anybody: no spin, no barrier
+    // across workgroups; the owner finishes whatever nobody took.
+    unsigned* bcast = sync + 80;                                         // [3] a claim, from wave 0 to all four: they must run the same chunk
+    uint64_t* const my_rec = g.tail_rec != nullptr ? g.tail_rec + blockIdx.x : nullptr;
+    const unsigned lane16 = (unsigned)lane * 16u;
+    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)tiles;
+    unsigned tail_fixed = 0;                                             // (profiling build: the size of a piece)
+    unsigned own_a = 0, own_b = 0;                                       // the workgroup's decided range [own_a, own_b) of local half-tiles; empty: none
+    // the next chunk: own = from this workgroup's record (first: its first claim), else from the other record with the most left.
+    // One thread claims; false: nothing left there.
+    auto next_chunk = [&](bool own, bool first, unsigned& vb, unsigned& a, unsigned& b) __attribute__((always_inline)) -> bool {
+        if (wave == 0) {
+            unsigned ca = 0, cb = 0, cv = blockIdx.x;
+            if (own) {
+                if (lane == 0 && !pda_ts_claim(my_rec, first, g.tail_min, tail_fixed, ca, cb)) ca = cb = 0;
+            } else {
+                // (a record seen with something left and found exhausted by the claim stays exhausted: at most one failure per record)
+                for (;;) {
+                    unsigned long long key = pda_ts_pick(g.tail_rec, gridDim.x, blockIdx.x, (unsigned)lane, 64u);
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) { const unsigned long long k2 = __shfl_xor(key, o, 64); key = k2 > key ? k2 : key; }
+                    if ((key >> 32) == 0ull) break;
+                    bool ok = false;
+                    if (lane == 0) ok = pda_ts_steal(g.tail_rec, key, g.tail_min, cv, ca, cb);
+                    if (__any(ok)) break;
+                    ca = cb = 0;
+                }
+            }
+            if (lane == 0) { bcast[0] = ca; bcast[1] = cb; bcast[2] = cv; }
+        }
+        __syncthreads();
+        a = (unsigned)__builtin_amdgcn_readfirstlane((int)bcast[0]);
+        b = (unsigned)__builtin_amdgcn_readfirstlane((int)bcast[1]);
+        vb = (unsigned)__builtin_amdgcn_readfirstlane((int)bcast[2]);
+        __syncthreads();
+        return a < b;
+    };
+
     unsigned n_cand = 0;
     if (hend > 0) {
         const int row0 = wave * UPW;                                     // this wave's user rows of the workgroup
         const int j = lane & (UBW - 1), hh = lane / UBW;               // the lane's user of a block; its 8-element group of a fragment's k-range
-        const unsigned lane16 = (unsigned)lane * 16u;
         const unsigned char* my_ufrag = g.ufrag + ((size_t)utile * 4 + wave) * (size_t)(NU * NK * 1024);
         // the wave's largest padded ||u||, the external seeds and the history bounds of the lane's users (block u: row UBW u + j)
         float eu = 0.f, seedv[NU];
@@ -194,7 +243,6 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
         for (int o = 32; o >= 1; o >>= 1) eu = fmaxf(eu, __shfl_xor(eu, o, 64));
         const float numax = eu;                                          // the wave's largest padded ||u|| (the decided half-tile)
         eu = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(eu * (kEps5 * 1.001f))));       // eps x the wave's largest ||u||, wave-uniform
-        const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)tiles;
         const unsigned flags_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(sync);
         uint64_t* my_ring = crings + wave * kRing5;
         unsigned ring_n = 0;                                             // wave-uniform: entries in my_ring
@@ -483,17 +531,34 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             return hend;                                                 // A/B build: every half-tile is tested (tools/build_variant.sh nofree -DPDA_V5_NO_FREE)
 #else
             if (g.tailA == nullptr || !(tw > -1.0e30f)) return hend;
+            // the first tile of [lo, hi) at which the predicate holds (hi: none).  The predicate is monotone along the order (the suffix
+            // maxima fall, nw >= 0), so instead of a bisection -- a dependent pair of loads per step, twelve at config 3 -- the 64 lanes
+            // probe up to 64 evenly spaced tiles per round with independent loads: the first lane that holds brackets the answer, and
+            // two or three rounds end at the same tile
             int lo = (int)(h_now >> 1), hi = n_it;
             while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                const size_t T = (size_t)t0 + (size_t)mid * (size_t)g.n_splits;
-                if (__builtin_fmaf(nw, g.tailB[T], g.tailA[T]) * 1.000002f < tw) hi = mid; else lo = mid + 1;
+                const int n = hi - lo, step = (n + 63) >> 6, p = lo + lane * step;
+                bool ok = false;
+                if (p < hi) {
+                    const size_t T = (size_t)t0 + (size_t)p * (size_t)g.n_splits;
+                    ok = __builtin_fmaf(nw, g.tailB[T], g.tailA[T]) * 1.000002f < tw;
+                }
+                const uint64_t m = __ballot(ok);
+                if (m == 0ull) {
+                    lo += (n - 1) / step * step + 1;                     // behind the last probe
+                } else {
+                    const int f = __builtin_ctzll(m);
+                    hi = lo + f * step;
+                    lo = f > 0 ? hi - step + 1 : hi;
+                }
+                lo = __builtin_amdgcn_readfirstlane(lo);
+                hi = __builtin_amdgcn_readfirstlane(hi);
             }
             return 2u * (unsigned)lo;
 #endif
         };
         float* xch = reinterpret_cast<float*>(sync + 72);                // [8] the waves' lowest thresholds and largest norms
-        unsigned h = 0, issued = 0, n_entries = 0, n_free = 0;
+        unsigned h = 0, issued = 0, n_entries = 0;
         unsigned hlim = hend;            // the end handed to the tested body: what it issued for half-tiles >= hlim are clamped copies
         bool hend_ok = true;
         if ((ring_lds & (D == 256 ? 511u : 255u)) != 0u) { if (lane == 0) g.stats[0] = 6u; hend_ok = false; }      // (the slots must start at multiples of 256 / 512)
@@ -522,10 +587,13 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
                 if (h > hlim) h = hlim;
                 if (issued > hlim) issued = hlim;
                 if (h < hend) {
-                    ++n_entries;
-                    n_free = hend - h;
-                    XP(if (xp_out != 0) { const unsigned long long t_ = wall_clock64(); xp[3] += t_ - xp_out; xp[2] += t_ - xp_re; xp_out = 0; } else xp[6] = wall_clock64() - xp_k0;)
-                    Loop6Free<D, NU>::run(h, issued, hend, ring_lds, 1024u * (unsigned)wave, t0, (unsigned)g.n_splits, (unsigned)img, (unsigned)(img >> 32), my_ufrag, lane16);
+                    XP(if (xp_out != 0) { const unsigned long long t_ = wall_clock64(); xp[3] += t_ - xp_out; xp[2] += t_ - xp_re; xp_out = 0; } else xp[6] = wall_clock64() - xp_k0;
+                       xp[8] = h; xp[9] = wall_clock64() - xp_k0;)
+                    // the range [h, hend) is decided: it is run at the end of the kernel, behind the rows -- with sharing out of the
+                    // workgroup's record, by whoever claims a chunk of it first
+                    own_a = h;
+                    own_b = hend;
+                    if (my_rec != nullptr && tid == 0) pda_ts_publish(my_rec, h, hend);
                 }
                 break;
             }
@@ -554,8 +622,8 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
         if (ring_n > 0u) rescore_ring();
         if (lane == 0) atomicAdd(g.stats + 1, n_cand);
         if (lane == 0) atomicAdd(g.stats + 5, n_entries);                  // (workspace + 20: entries of the asm loop, summed over the waves)
-        if (lane == 0 && wave == 0 && n_free > 0u) atomicAdd(g.stats + 7, n_free);      // (workspace + 28: half-tiles run test-free, summed over the workgroups)
-        if (lane == 0 && wave == 0) atomicAdd(reinterpret_cast<unsigned long long*>(g.stats + 2), (unsigned long long)(2 * n_it * (UT / kUserTile)));
+        // (workspace + 8: the half-tiles run so far -- all of the split but its decided range, which whoever runs it adds below)
+        if (lane == 0 && wave == 0) atomicAdd(reinterpret_cast<unsigned long long*>(g.stats + 2), (unsigned long long)(hend - (own_b - own_a)) * (unsigned long long)(UT / kUserTile));
     }
     // ================================== all waves: sort and emit ==================================
     // Every list comes out of the warm-up unsorted with K .. kCap4 keys, and all but a few per cent of them are untouched since: the
@@ -630,14 +698,65 @@ __global__ void __launch_bounds__(256, 1) sweep5_kernel(Args4 g) {
             }
         }
     }
-    XP(xp[7] = wall_clock64() - xp_e0; xp[5] = wall_clock64() - xp_k0;
-       if (lane == 0 && blockIdx.x < (unsigned)kXpMaxWg) for (int q = 0; q < 8; ++q) pda_v5_exitprof[((size_t)blockIdx.x * 4 + wave) * 8 + q] = xp[q];)
+    XP(xp[7] = wall_clock64() - xp_e0; xp[11] = hend;)
+    // ================================== all waves: the test-free tails ==================================
+    // The rows are out, the rings and the LDS slots are free.  Chunks of the workgroup's own decided range until its record is exhausted,
+    // then chunks from the record with the most left, until nothing is left anywhere: a workgroup that finds nothing leaves.  Without
+    // sharing: the own range in one piece.  (PDA_SWEEP_TAIL_OTHERS_FIRST: the other records first.)  workspace + 8, + 20 and + 28 are added
+    // by whoever ran the half-tiles.
+    {
+        unsigned n_ent2 = 0, n_ran = 0, n_chunks_other = 0, n_ran_other = 0;
+        bool steal = my_rec != nullptr;
+        XP(if (pda_v5_tail_pieces > 0) { steal = false; tail_fixed = (own_b - own_a + (unsigned)pda_v5_tail_pieces - 1u) / (unsigned)pda_v5_tail_pieces; })
+        const bool others_first = steal && g.tail_others_first != 0;
+        bool own_left = own_a < own_b;                                   // (an exhausted record stays exhausted: no second look)
+        __syncthreads();
+        for (;;) {
+            unsigned vb = blockIdx.x, a = own_a, b = own_b;
+            if (my_rec == nullptr) {
+                own_a = own_b;                                           // (one piece)
+            } else {
+                bool got = false;
+                if (others_first) {
+                    got = next_chunk(false, false, vb, a, b);
+                    if (!got && own_left) { got = next_chunk(true, false, vb, a, b); own_left = got; }
+                } else {
+                    if (own_left) { got = next_chunk(true, n_ent2 == 0u, vb, a, b); own_left = got; }
+                    if (!got && steal) got = next_chunk(false, false, vb, a, b);
+                }
+                if (!got) a = b = 0;
+            }
+            if (a >= b) break;
+            // the chunk's tile sequence and user image (as its workgroup's own prologue forms them)
+            const int vsplit = (int)(vb % (unsigned)g.n_splits), vutile = (int)(vb / (unsigned)g.n_splits);
+            const unsigned vt0 = (unsigned)(vsplit + warm_tiles_of(g, vsplit) * g.n_splits);
+            const unsigned char* vfrag = g.ufrag + ((size_t)vutile * 4 + wave) * (size_t)(NU * NK * 1024);
+            const size_t vimg = (size_t)g.rows5;
+            ++n_ent2;
+            n_ran += b - a;
+            if (vb != blockIdx.x) { ++n_chunks_other; n_ran_other += b - a; }
+            unsigned is = a;
+            Loop6Free<D, NU>::run(a, is, b, ring_lds, 1024u * (unsigned)wave, vt0, (unsigned)g.n_splits, (unsigned)vimg, (unsigned)(vimg >> 32), vfrag, lane16);
+        }
+        if (lane == 0 && n_ent2 > 0u) atomicAdd(g.stats + 5, n_ent2);    // (workspace + 20)
+        if (lane == 0 && wave == 0 && n_ran > 0u) {
+            atomicAdd(g.stats + 7, n_ran);                               // (workspace + 28: half-tiles run test-free)
+            atomicAdd(reinterpret_cast<unsigned long long*>(g.stats + 2), (unsigned long long)n_ran * (unsigned long long)(UT / kUserTile));
+        }
+        if (lane == 0 && wave == 0 && n_chunks_other > 0u) {
+            atomicAdd(g.stats + 9, n_chunks_other);                      // (workspace + 36: chunks run for another workgroup)
+            atomicAdd(g.stats + 10, n_ran_other);                        // (workspace + 40: the half-tiles in them)
+        }
+        XP(xp[10] = n_ran_other;)
+    }
+    XP(xp[5] = wall_clock64() - xp_k0;
+       if (lane == 0 && blockIdx.x < (unsigned)kXpMaxWg) for (int q = 0; q < kXpWords; ++q) pda_v5_exitprof[((size_t)blockIdx.x * 4 + wave) * kXpWords + q] = xp[q];)
 }
 
 template <int D, bool BF, bool S16, int UPW>
 int launch_sweep5(const Args4& g, const Call4& c, hipStream_t stream) {
     constexpr int UT = 4 * UPW;
-    constexpr size_t lds = (size_t)kNSlot5 * slot_bytes5(D) + (size_t)UT * 8 + 4 * kRing5 * 8 + 80 * 4 + 64;
+    constexpr size_t lds = (size_t)kNSlot5 * slot_bytes5(D) + (size_t)UT * 8 + 4 * kRing5 * 8 + (80 + 4) * 4 + 64;          // (80 words of sync, 4 of a claim)
     static_assert(UPW == 256 || D == 256 || 2 * lds <= 160 * 1024, "two workgroups per CU");
     static_assert(lds <= 160 * 1024, "LDS per workgroup");
     static char attr_done[kMaxDev4] = {};

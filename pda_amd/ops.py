@@ -164,6 +164,9 @@ def item_prep_ordered(I_shard: torch.Tensor, pop_shard: Optional[torch.Tensor], 
 _PREP4_CACHE = {}      # id(I_shard) -> (weakref(I), I._version, order|None, pop weakref|None, pop _version, prep buffer)
 SWEEP_WARM_PER_SPLIT = 1024   # PDA_SWEEP_WARM_PER_SPLIT (include/pda_hip.h)
 SWEEP_WARM_ONE_KERNEL = 2048  # PDA_SWEEP_WARM_ONE_KERNEL (include/pda_hip_experimental.h)
+SWEEP_TAIL_NO_SHARE = 4096        # PDA_SWEEP_TAIL_NO_SHARE (include/pda_hip_experimental.h): the huge geometry's test-free tails are not shared
+SWEEP_TAIL_OTHERS_FIRST = 8192    # PDA_SWEEP_TAIL_OTHERS_FIRST (tests)
+SWEEP_TAIL_MIN2 = 16384           # PDA_SWEEP_TAIL_MIN2 (tests)
 TOPK_K_V4 = 54         # pda_score_topk4_*: K <= 54 (57 list slots per user)
 
 
@@ -547,6 +550,12 @@ def sweep_from_seed(U, I_shard, users, K, head, pop_shard, hist, item_offset, se
     return out
 
 
+def tail_record_offset(nu: int) -> int:
+    """Byte offset, in the workspace of pda_score_topk4_*, of the huge geometry's shared-tail records (pda_amd/csrc/pda_tail_share.h): directly
+    behind the counters."""
+    return (_lib.load().pda_score_topk_workspace_bytes(nu) + 255) & ~255
+
+
 def seeded_counts(c: SeededCall) -> Optional[torch.Tensor]:
     """Step 2 (after the MAX all-reduce of c.bounds): this shard's warm-up entries at or above the common thresholds ->
     int32 [n_thr, Bu], to be SUM-reduced in place; None below four shards (plain seed: no second collective)."""
@@ -657,6 +666,12 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
             es |= SWEEP_WARM_PER_SPLIT
         if os.environ.get("PDA_WARM_ONE_KERNEL"):     # A/B measurements and tests: the dense call's warm-up as warm4_kernel, not as score + select kernel
             es |= SWEEP_WARM_ONE_KERNEL
+        if os.environ.get("PDA_SWEEP_TAIL_SHARE") == "0":   # A/B measurements and tests: every workgroup of the huge geometry runs its own test-free tail
+            es |= SWEEP_TAIL_NO_SHARE
+        if os.environ.get("PDA_SWEEP_TAIL_OTHERS_FIRST"):    # tests: a workgroup looks at the other workgroups' records before it runs its own range
+            es |= SWEEP_TAIL_OTHERS_FIRST
+        if os.environ.get("PDA_SWEEP_TAIL_MIN_CHUNK") == "2":   # tests: chunks down to 2 half-tiles
+            es |= SWEEP_TAIL_MIN2
         # the warm-position masks of every user, built once per history and order: the call gathers them instead of walking the histories
         # (one warm-up over the front of the whole order: one split, or the shared warm-up of several)
         tab = warm_mask_table(hist, prep, order, item_offset, nloc, d) if hist and (n_splits == 1 or not (es & SWEEP_WARM_PER_SPLIT)) else None
@@ -682,6 +697,9 @@ def score_topk_keys(U, I_shard, users, K=50, head=HEAD_RAW, pop_shard=None, hist
             stats["huge_entries"] = ws[20:24].view(torch.int32)  # huge geometry: entries of its asm loop, summed over the waves (1 per wave + 1 per flagged half-tile)
             stats["huge_free_halftiles"] = ws[28:32].view(torch.int32)  # huge geometry: 32-item half-tiles run without threshold tests (behind the decided half-tile), summed over the workgroups
             stats["warm_kernels"] = ws[32:36].view(torch.int32)  # which exact warm-up ran: 0 = warm4_kernel, 5 = warm_score5_kernel + warm_select5_kernel
+            stats["tail_stolen_chunks"] = ws[36:40].view(torch.int32)     # huge geometry: chunks of test-free half-tiles run for ANOTHER workgroup
+            stats["tail_stolen_halftiles"] = ws[40:44].view(torch.int32)  # ... and the half-tiles in them
+            stats["tail_records"] = ws[tail_record_offset(nu):tail_record_offset(nu) + 8 * (-(-nu // (512 if d == 256 else 1024)) * n_splits)].view(torch.int64)  # one per workgroup: end << 32 | next (0: nothing published)
             stats["error"] = ws[0:4].view(torch.int32)           # 0, or which bounded wait of the sweep ran out (1 .. 4: hand-over words; 5, 6: huge geometry)
             stats["workspace"] = ws                               # (tests read the huge geometry's user image out of it: huge_image_offsets)
             stats["n_splits"] = n_splits

@@ -4,13 +4,18 @@ exits   what the waves of sweep5_kernel spend OUTSIDE their asm loops: needs the
             tools/build_variant.sh exitprof -DPDA_V5_EXITPROF;  PDA_HIP_LIB=pda_amd/csrc/ab/libpda_hip_exitprof.so python tools/time_huge_exits.py exits c3
         (per workgroup the slowest wave of every counter, 100 MHz wall clock; the launch is one round, so the workgroup with the most time
         outside sets the kernel's time).  The counters slow the kernel a little: times of the call itself come from a product build.
+        Beside max / mean / min of the workgroups' whole time: every workgroup's decided half-tile, the wall clock at which it went test-free,
+        and the half-tiles it ran for other workgroups (the shared tail, pda_amd/csrc/pda_tail_share.h; PDA_SWEEP_TAIL_SHARE=0 in front: unshared).
+pieces  the cost of one more entry of the test-free loop, same build: every workgroup runs its own decided range in n = 1, 2, 4, 8, 16 equal pieces,
+        nobody shares; the slope of the call's time over n is the cost of an entry
+            PDA_HIP_LIB=pda_amd/csrc/ab/libpda_hip_exitprof.so python tools/time_huge_exits.py pieces c3
 mask    the warm-position mask table (ops.warm_mask_table): its one-time build, and a call with and without it at several block sizes
             python tools/time_huge_exits.py mask c3 2048,50000,262144 [order|stop]
 warm    the dense call with its warm-up as one kernel (PDA_WARM_ONE_KERNEL=1) and as score + select kernel, at several block sizes
             python tools/time_huge_exits.py warm c3 2048,4096,50000,262144 [order [row]]
         row: the block's histories as a CSR by block row (no mask table: warm_mask4_kernel in front of the score kernel).  Blocks under
         4 096 users get the huge geometry only when forced: PDA_SCORE_LISTS=huge in front of the command
-usage: time_huge_exits.py exits|mask|warm [workload=c3] [users per block(s)] [sweep] [row]"""
+usage: time_huge_exits.py exits|pieces|mask|warm [workload=c3] [users per block(s)] [sweep] [row]"""
 import ctypes as C
 import os
 import sys
@@ -55,7 +60,7 @@ def timed(fn, n):
     return e0.elapsed_time(e1) / n
 
 
-if mode == "exits":
+if mode in ("exits", "pieces"):
     lib = _lib.load()
     if not hasattr(lib, "pda_debug_v5_exitprof"):
         sys.exit("this library has no exit counters: build with tools/build_variant.sh exitprof -DPDA_V5_EXITPROF and select it with PDA_HIP_LIB")
@@ -70,7 +75,27 @@ if mode == "exits":
     assert ident.get("geometry") == "huge" and int(st["error"][0]) == 0, ident
     UT = 512 if W.d == 256 else 1024
     wgs = -(-Bu // UT) * k.shape[0]
-    buf = np.zeros((wgs, 4, 8), dtype=np.uint64)
+    nw = 8
+    if hasattr(lib, "pda_debug_v5_exitprof_words"):
+        lib.pda_debug_v5_exitprof_words.restype = C.c_int
+        nw = int(lib.pda_debug_v5_exitprof_words())
+    if mode == "pieces":
+        lib.pda_debug_v5_tail_pieces.restype, lib.pda_debug_v5_tail_pieces.argtypes = C.c_int, [C.c_int]
+        print("%s %d users x %d splits, %d workgroups: the decided range of every workgroup in n equal pieces, nobody shares" % (wl, Bu, k.shape[0], wgs))
+        res = {}
+        for rnd in range(3):
+            for n in (1, 2, 4, 8, 16):
+                _lib.check(lib.pda_debug_v5_tail_pieces(n), "pda_debug_v5_tail_pieces")
+                call(users, st)
+                res.setdefault(n, []).append((timed(lambda: call(users), 5), float(st["huge_entries"][0]) / (4 * wgs)))
+        _lib.check(lib.pda_debug_v5_tail_pieces(0), "pda_debug_v5_tail_pieces")
+        for n, r in res.items():
+            print("  n = %2d: call %s ms, %.2f entries per wave" % (n, " / ".join("%.4f" % t for t, _ in r), r[0][1]))
+        ns = np.array(sorted(res)), np.array([min(t for t, _ in res[n]) for n in sorted(res)])
+        slope = np.polyfit(ns[0], ns[1], 1)[0]
+        print("  slope of the fastest times over n: %.2f us per entry (all 256 workgroups enter at once: an upper bound for a lone entry)" % (slope * 1e3))
+        sys.exit(0)
+    buf = np.zeros((wgs, 4, nw), dtype=np.uint64)
     _lib.check(lib.pda_debug_v5_exitprof(buf.ctypes.data_as(C.c_void_p), wgs), "pda_debug_v5_exitprof")
     us = buf.astype(np.float64) / 100.0                # 100 MHz -> microseconds
     wg = us.max(axis=1)                                # per workgroup: the slowest wave of every counter
@@ -86,6 +111,17 @@ if mode == "exits":
     longest = int(np.argmax(wg[:, 5]))
     print("  longest workgroup %d: kernel %.1f us, outside %.1f us, %d exits; shortest kernel %.1f us" %
           (longest, wg[longest, 5], wg[longest, 3], exits[longest], wg[:, 5].min()))
+    print("  whole time of the workgroups: max %.1f us   mean %.1f us   min %.1f us   (max - mean %.1f us)" %
+          (wg[:, 5].max(), wg[:, 5].mean(), wg[:, 5].min(), wg[:, 5].max() - wg[:, 5].mean()))
+    if nw >= 12:
+        dec, t_free, other, hend = buf[:, 0, 8].astype(np.int64), us[:, :, 9].max(axis=1), buf[:, 0, 10].astype(np.int64), buf[:, 0, 11].astype(np.int64)
+        went = t_free > 0
+        print("  decided half-tile (of %d .. %d per split): max %d  mean %.1f  min %d; %d of %d workgroups went test-free" %
+              (hend.min(), hend.max(), dec[went].max() if went.any() else -1, dec[went].mean() if went.any() else -1, dec[went].min() if went.any() else -1, int(went.sum()), wgs))
+        print("  entered the test-free part at: max %.1f us   mean %.1f us   min %.1f us" %
+              ((t_free[went].max(), t_free[went].mean(), t_free[went].min()) if went.any() else (0, 0, 0)))
+        print("  half-tiles run for other workgroups: total %d, by %d workgroups (max %d); chunks %d" %
+              (other.sum(), int((other > 0).sum()), other.max(), int(st["tail_stolen_chunks"][0]) if "tail_stolen_chunks" in st else -1))
 else:
     order = ops.visiting_order(W.I, W.pop_last)
     prep = ops.item_prep4(W.I, W.pop_last, order)

@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h and pda_hip_dns.h).
+pda_hip_inbatch.h, pda_hip_dns.h and pda_hip_ials.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -263,6 +263,16 @@ DNS_SIGNATURES = {
     "pda_dns_sample_f32_dev": (_i, _dns_head + [_vp, _vp] + [_vp] * 8),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_ials.h (the iALS baseline: `--train ials`)
+IALS_CHUNK = 4096
+IALS_GRAM_ROWS = 256
+IALS_SIGNATURES = {
+    "pda_ials_workspace_bytes": (_sz, [_sz, _i]),
+    "pda_ials_gram_f32": (_i, [_vp, _sz, _i, _vp, _vp, _sz, _vp]),
+    "pda_ials_half_sweep_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pda_ials_loss_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -283,7 +293,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
-            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()):
+            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -8,6 +8,7 @@
     SSMBPRMF           SSM                 (no reference code: DESIGN.md 5l)   a BPRMF trained with the sampled-softmax loss; Adam sweep only
     MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
     LightGCN           the LightGCN backbone (no reference code: DESIGN.md 5j)  ego tables propagated over the train graph; ConditionalLightGCN: PD/PDA on it
+    IALSMF             iALS                (no reference code: DESIGN.md 5o)   the tables of a BPRMF solved row by row (implicit ALS); no step, train_epoch()
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
 trainer passes to `sess.run`.  Here they are light handle objects understood by `pda_amd.train_new_api.Session`,
@@ -40,6 +41,7 @@ of its flags and data alone, bit for bit.  Combinations that cannot keep that pr
 """
 from __future__ import annotations
 
+import copy
 import math
 
 import torch
@@ -1208,3 +1210,92 @@ class ConditionalLightGCN(LightGCN):
         self.opt_pop_global, self.loss_pop_global = Fetch(self, "opt"), Fetch(self, "loss")
         self.mf_loss_pop_global, self.reg_loss_pop_global = Fetch(self, "mf_loss"), Fetch(self, "reg_loss")
         self.condition_ratings = Fetch(self, "condition_ratings")
+
+
+# ---- iALS (include/pda_hip_ials.h) ------------------------------------------------------------------------------------------------
+IALS_EMBED_SIZES = ops.IALS_EMBED_SIZES     # --embed_size of an iALS model: a d x d fp32 matrix has to fit the LDS (256 does not)
+
+
+def check_ials(args):
+    """--train ials: refuse, before anything is built, what the iALS baseline has no path for.  Every message names its flag.
+    --lr, --optimizer, --adam_sweep, --sampler and --batch_size (for training) are unused: there is no sampler and no optimiser.
+    --deterministic 1 is accepted and changes nothing: the run is a function of its flags and data either way."""
+    if getattr(args, "train", "normal") != "ials":
+        if getattr(args, "test", "normal") == "ials":
+            raise NotImplementedError("--test ials needs an iALS model (--train ials), not --train %s" % (args.train,))
+        return
+    if getattr(args, "model", "mf") != "mf":
+        raise NotImplementedError("--model %s: --train ials solves the two embedding tables of --model mf; a LightGCN has no closed-form row "
+                                  "update" % (args.model,))
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train ials runs fp32 tables only" % (args.table_dtype,))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train ials trains on one GPU (no item shards)" % (args.gpus,))
+    if getattr(args, "neg_sampler", "uniform") != "uniform":
+        raise NotImplementedError("--neg_sampler %s: --train ials has no sampled negatives (every unobserved pair is weighed by --ials_alpha0)"
+                                  % (args.neg_sampler,))
+    if int(args.embed_size) not in IALS_EMBED_SIZES:
+        raise NotImplementedError("--embed_size %s: --train ials takes one of %s (a d x d fp32 matrix per row has to fit the LDS)"
+                                  % (args.embed_size, IALS_EMBED_SIZES))
+    if getattr(args, "test", "normal") not in ("normal", "ials"):
+        raise NotImplementedError("--test %s: --train ials goes with --test normal (the raw head and the gamma search of a BPRMF) or --test ials"
+                                  % (args.test,))
+    regs = float(args.regs)
+    if not (regs > 0.0 and math.isfinite(regs)):
+        raise ValueError("--regs must be a finite number > 0 with --train ials (it is lambda: the row systems are positive definite by it), got %s"
+                         % (args.regs,))
+    a0 = float(getattr(args, "ials_alpha0", 0.1))
+    if not (a0 >= 0.0 and math.isfinite(a0)):
+        raise ValueError("--ials_alpha0 must be a finite number >= 0, got %s" % (args.ials_alpha0,))
+    nu = float(getattr(args, "ials_nu", 1.0))
+    if not 0.0 <= nu <= 1.0:
+        raise ValueError("--ials_nu must lie in 0 .. 1, got %s" % (args.ials_nu,))
+
+
+class IALSMF(BPRMF):
+    """Implicit ALS (Hu et al. ICDM'08 in the form of Rendle et al. RecSys'22; DESIGN.md 5o, include/pda_hip_ials.h).  Tables, fetchables,
+    evaluation and checkpoint are those of BPRMF (model "mf", no optimiser state): the two differ only in how they were trained.  There is no
+    step: train_epoch() is the user half-sweep, the item half-sweep and the objective.  data_config["gcn_train_pairs"] = (users, items), or
+    set_train_pairs: the train pairs -- rebuilt from the data, never stored in a checkpoint; a model that is only restored and evaluated
+    needs none."""
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_ials(args)
+        if int(getattr(args, "deterministic", 0) or 0):
+            # accepted, and it changes nothing: there is no plan and no atomic sum to replace, the run is a function of flags and data either way
+            args = copy.copy(args)
+            args.deterministic = 0
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.optimizer = "ials"
+        self.adam_exact_lazy = False
+        self.ials_alpha0 = float(getattr(args, "ials_alpha0", 0.1))
+        self.ials_nu = float(getattr(args, "ials_nu", 1.0))
+        self.graph = None
+        if data_config.get("gcn_train_pairs") is not None:
+            self.set_train_pairs(*data_config["gcn_train_pairs"])
+
+    def set_train_pairs(self, users, items):
+        self.graph = ops.IalsGraph(users, items, self.n_users, self.n_items, self.device, lam=self.decay, alpha0=self.ials_alpha0, nu=self.ials_nu)
+
+    def train_step(self, *a, **kw):
+        raise NotImplementedError("--train ials has no batch step: train_epoch() runs the two half-sweeps")
+
+    def train_epoch(self) -> torch.Tensor:
+        """One epoch: X <- argmin_X L(X, Y), then Y <- argmin_Y L(X, Y), then the objective at the new tables.  Returns the device float64 [3]
+        (loss, fit, reg) / |S|, [3] read together with the failed-pivot counter by failed_pivots(); no host read here."""
+        g = self.graph
+        if g is None:
+            raise ValueError("IALSMF needs the train pairs before it trains (data_config['gcn_train_pairs'] or set_train_pairs)")
+        X, Y = self.weights["user_embedding"], self.weights["item_embedding"]
+        ops.ials_half_sweep(g, "user", Y, X)
+        ops.ials_half_sweep(g, "item", X, Y)
+        return ops.ials_loss(g, X, Y) / max(1, g.nnz)
+
+    def failed_pivots(self) -> torch.Tensor:
+        """The device int32 [1] count of rows written as NaN by a failed pivot since the model was built (0 on finite tables)."""
+        return self.graph.buffers(self.emb_dim)["fail"]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd.update(optimizer="ials", ials_alpha0=self.ials_alpha0, ials_nu=self.ials_nu)
+        return sd

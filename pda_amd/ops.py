@@ -3066,3 +3066,211 @@ def dns_sample_into(out, U, I, train_indptr, train_indices, *, n_cands: int, top
                                              int(head), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(neg), ptr(pp), ptr(pn), ptr(cand),
                                              ptr(score), ptr(col), stream_ptr()), "pda_dns_sample_f32_dev")
     return out
+
+
+# ---- iALS (include/pda_hip_ials.h) ---------------------------------------------------------------------------------------------------------------
+IALS_EMBED_SIZES = (32, 64, 128)
+IALS_CHUNK = _lib.IALS_CHUNK                  # PDA_IALS_CHUNK: a row with more pairs is cut into chunks of this many
+IALS_GRAM_ROWS = _lib.IALS_GRAM_ROWS          # PDA_IALS_GRAM_ROWS: rows of Z per partial Gram matrix
+
+
+def check_ials_params(lam, alpha0, nu):
+    lam, alpha0, nu = float(lam), float(alpha0), float(nu)
+    if not (lam > 0.0 and math.isfinite(lam)):
+        raise ValueError(f"iALS: lambda must be a finite number > 0, got {lam}")
+    if not (alpha0 >= 0.0 and math.isfinite(alpha0)):
+        raise ValueError(f"iALS: alpha0 must be a finite number >= 0, got {alpha0}")
+    if not 0.0 <= nu <= 1.0:
+        raise ValueError(f"iALS: nu must lie in 0 .. 1, got {nu}")
+    return lam, alpha0, nu
+
+
+def ials_lam_row(deg, n_other: int, lam: float, alpha0: float, nu: float):
+    """lambda_r = fl32(lambda * float64(n_r + alpha0 n_other)^nu), numpy float32 [n_rows]: rounded once, an input of the kernels."""
+    import numpy as np
+    lam, alpha0, nu = check_ials_params(lam, alpha0, nu)
+    return (lam * np.power(np.asarray(deg, dtype=np.float64) + alpha0 * float(n_other), nu)).astype(np.float32)
+
+
+def ials_graph_arrays(users, items, n_users: int, n_items: int, chunk: int = IALS_CHUNK) -> dict:
+    """Both CSR directions and both work lists of include/pda_hip_ials.h from the train pairs, on the host (numpy; no GPU needed): what
+    gcn_graph_arrays yields for the stacked graph, taken apart into the user side (rows: users, columns: item ids) and the item side (rows:
+    items, columns: user ids), each with its own pair offsets and slot numbers.  Every list keeps gcn_graph_arrays' order: falling length,
+    rows and chunks rising among equals."""
+    import numpy as np
+    h = gcn_graph_arrays(users, items, n_users, n_items, chunk)
+    nu_, nnz = h["n_users"], int(h["edge_w"].shape[0])
+    ip, ix, work, lr = h["indptr"], h["indices"], h["work"], h["long_rows"]
+    u_slots = int(lr[lr[:, 0] < nu_, 2].sum())
+    sides = {}
+    for name, r0, n, e0, s0, col0 in (("user", 0, nu_, 0, 0, nu_), ("item", nu_, h["n_items"], nnz, u_slots, 0)):
+        wk = work[(work[:, 0] >= r0) & (work[:, 0] < r0 + n)].copy()
+        wk[:, 0] -= r0
+        wk[:, 1:3] -= e0
+        wk[:, 3] = np.where(wk[:, 3] >= 0, wk[:, 3] - s0, -1)
+        l = lr[(lr[:, 0] >= r0) & (lr[:, 0] < r0 + n)].copy()
+        l[:, 0] -= r0
+        l[:, 1] -= s0
+        indptr = (ip[r0:r0 + n + 1] - e0).astype(np.int64)
+        sides[name] = dict(n_rows=n, n_other=h["n_items"] if name == "user" else nu_, indptr=np.ascontiguousarray(indptr),
+                           indices=np.ascontiguousarray((ix[e0:e0 + nnz] - col0).astype(np.int32)), deg=np.diff(indptr),
+                           work=np.ascontiguousarray(wk), long_rows=np.ascontiguousarray(l), n_slots=int(l[:, 2].sum()))
+    return dict(n_users=nu_, n_items=h["n_items"], chunk=int(chunk), nnz=nnz, user=sides["user"], item=sides["item"])
+
+
+class IalsWork:
+    """A work list of one side on the device: `work` int64 [n_work, 4], `long_rows` int64 [n_long, 3], n_slots."""
+
+    def __init__(self, work, long_rows, n_slots: int, device):
+        self.host_work, self.host_long_rows, self.n_slots = work, long_rows, int(n_slots)
+        self.work = torch.from_numpy(work).to(device)
+        self.long_rows = torch.from_numpy(long_rows).to(device)
+        self.n_work, self.n_long = int(work.shape[0]), int(long_rows.shape[0])
+
+
+class IalsSide:
+    """One side of an IalsGraph: its CSR (int64 indptr, int32 column ids ascending), degrees, lam_row and the work list of all its rows."""
+
+    def __init__(self, h: dict, lam_row, device):
+        self.host, self.device = h, device
+        self.n_rows, self.n_other, self.nnz = int(h["n_rows"]), int(h["n_other"]), int(h["indices"].shape[0])
+        self.indptr, self.indices = torch.from_numpy(h["indptr"]).to(device), torch.from_numpy(h["indices"]).to(device)
+        self.host_lam_row = lam_row
+        self.lam_row = torch.from_numpy(lam_row).to(device)
+        self.all_rows = IalsWork(h["work"], h["long_rows"], h["n_slots"], device)
+
+    def sub_list(self, rows, shuffle_seed=None) -> IalsWork:
+        """The work list of the given rows alone (every entry of the side's own list whose row is among them, slots renumbered from 0),
+        optionally in a shuffled order: what a call needs to solve a subset of the rows."""
+        import numpy as np
+        rows = np.unique(np.asarray(rows, dtype=np.int64))
+        if rows.size == 0 or rows[0] < 0 or rows[-1] >= self.n_rows:
+            raise ValueError("iALS work list: row ids inside the side, at least one")
+        wk = self.host["work"][np.isin(self.host["work"][:, 0], rows)].copy()
+        lr = self.host["long_rows"][np.isin(self.host["long_rows"][:, 0], rows)].copy()
+        new0 = np.cumsum(lr[:, 2]) - lr[:, 2]
+        for (r, s0, n), t0 in zip(lr.tolist(), new0.tolist()):
+            m = wk[:, 0] == r
+            wk[m, 3] += t0 - s0
+        lr[:, 1] = new0
+        if shuffle_seed is not None:
+            g = np.random.default_rng(shuffle_seed)
+            wk, lr = wk[g.permutation(len(wk))], lr[g.permutation(len(lr))]
+        return IalsWork(np.ascontiguousarray(wk), np.ascontiguousarray(lr), int(lr[:, 2].sum()), self.device)
+
+
+class IalsGraph:
+    """The train pairs of an iALS model on the device, built once (ials_graph_arrays): both CSRs, both work lists, the degrees and lam_row of
+    both sides for the given (lambda, alpha0, nu).  Ids and shapes are validated here, on the host, once: the kernels trust the graph.  It also
+    owns what the calls write besides the tables: the workspace, the Gram matrix, the per-row loss terms and the failed-pivot counter, one set
+    per row width."""
+
+    def __init__(self, users, items, n_users: int, n_items: int, device, *, lam: float, alpha0: float = 0.1, nu: float = 1.0,
+                 chunk: int = IALS_CHUNK):
+        self.lam, self.alpha0, self.nu = check_ials_params(lam, alpha0, nu)
+        h = self.host = ials_graph_arrays(users, items, n_users, n_items, chunk)
+        self.n_users, self.n_items, self.nnz, self.chunk = h["n_users"], h["n_items"], h["nnz"], h["chunk"]
+        self.device = torch.device(device)
+        self.user = IalsSide(h["user"], ials_lam_row(h["user"]["deg"], self.n_items, self.lam, self.alpha0, self.nu), self.device)
+        self.item = IalsSide(h["item"], ials_lam_row(h["item"]["deg"], self.n_users, self.lam, self.alpha0, self.nu), self.device)
+        self._bufs = {}
+
+    def side(self, side) -> IalsSide:
+        if side not in ("user", "item"):
+            raise ValueError(f"iALS: side must be 'user' or 'item', got {side!r}")
+        return self.user if side == "user" else self.item
+
+    def buffers(self, d: int) -> dict:
+        if d not in self._bufs:
+            gram_slots = -(-max(self.n_users, self.n_items) // IALS_GRAM_ROWS)
+            slots = max(gram_slots, self.user.all_rows.n_slots, self.item.all_rows.n_slots)
+            nbytes = _lib.load().pda_ials_workspace_bytes(slots, d)
+            self._bufs[d] = dict(ws=torch.empty(max(1, nbytes), dtype=torch.uint8, device=self.device),
+                                 G=torch.empty((d, d), dtype=torch.float32, device=self.device),
+                                 rows=torch.empty((self.n_users, 3), dtype=torch.float32, device=self.device),
+                                 fail=torch.zeros(1, dtype=torch.int32, device=self.device))
+        return self._bufs[d]
+
+
+def _ials_table(t, n_rows: int, what: str):
+    t = _need(t, torch.float32, what)
+    if t.dim() != 2 or t.shape[0] != n_rows or t.shape[1] not in IALS_EMBED_SIZES:
+        raise ValueError(f"iALS: {what} is float32 [{n_rows}, d] with d one of {IALS_EMBED_SIZES}, got {tuple(t.shape)}")
+    return t
+
+
+def ials_gram(Z, G=None, workspace=None):
+    """pda_ials_gram_f32: G = Z^T Z, float32 [d, d], partial Gram matrices over blocks of IALS_GRAM_ROWS rows added in block order."""
+    Z = _need(Z, torch.float32, "Z")
+    if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] not in IALS_EMBED_SIZES:
+        raise ValueError(f"iALS: Z is float32 [n >= 1, d] with d one of {IALS_EMBED_SIZES}, got {tuple(Z.shape)}")
+    n, d = Z.shape
+    if G is None:
+        G = torch.empty((d, d), dtype=torch.float32, device=Z.device)
+    if _need(G, torch.float32, "G").shape != (d, d):
+        raise ValueError("iALS: G is float32 [d, d]")
+    nbytes = _lib.load().pda_ials_workspace_bytes(-(-n // IALS_GRAM_ROWS), d)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=Z.device)
+    if _need(workspace, torch.uint8, "workspace").numel() < nbytes:
+        raise ValueError(f"iALS: the Gram workspace holds {nbytes} bytes")
+    check(_lib.load().pda_ials_gram_f32(ptr(Z), n, d, ptr(G), ptr(workspace), workspace.numel(), stream_ptr()), "pda_ials_gram_f32")
+    return G
+
+
+def ials_half_sweep(graph: IalsGraph, side: str, Z, X_out, *, G=None, work: Optional[IalsWork] = None, dbg_normal=None, fail_count=None):
+    """pda_ials_half_sweep_f32: X_out[r] = A_r^{-1} b_r for the rows of `work` (default: every row of the side), Z the other table held fixed.
+    G: Z^T Z (computed here into the graph's buffer when missing).  dbg_normal float32 [n_rows, d * d + d]: receives (A_r, b_r) as they enter
+    the factorisation.  fail_count int32 [1] (default: the graph's own) is raised once per row with a failed pivot.  Returns X_out."""
+    s = graph.side(side)
+    Z = _ials_table(Z, s.n_other, "Z (the table held fixed)")
+    X_out = _ials_table(X_out, s.n_rows, "X_out")
+    d = Z.shape[1]
+    if X_out.shape[1] != d or X_out.data_ptr() == Z.data_ptr():
+        raise ValueError("iALS: X_out and Z are two tables of one width")
+    b = graph.buffers(d)
+    if G is None:
+        G = ials_gram(Z, b["G"], b["ws"])
+    if _need(G, torch.float32, "G").shape != (d, d):
+        raise ValueError("iALS: G is float32 [d, d]")
+    w = s.all_rows if work is None else work
+    if not isinstance(w, IalsWork):
+        raise TypeError("iALS: work is an IalsWork of this side (IalsSide.sub_list)")
+    if dbg_normal is not None and tuple(_need(dbg_normal, torch.float32, "dbg_normal").shape) != (s.n_rows, d * d + d):
+        raise ValueError(f"iALS: dbg_normal is float32 [{s.n_rows}, {d * d + d}]")
+    fail = b["fail"] if fail_count is None else _need(fail_count, torch.int32, "fail_count")
+    if fail.numel() < 1:
+        raise ValueError("iALS: fail_count holds one int32")
+    nbytes = _lib.load().pda_ials_workspace_bytes(w.n_slots, d)
+    ws = b["ws"]
+    if ws.numel() < nbytes:
+        ws = b["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=graph.device)
+    check(_lib.load().pda_ials_half_sweep_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(w.work), w.n_work,
+                                              ptr(w.long_rows) if w.n_long else None, w.n_long, w.n_slots, ptr(Z), s.n_other, ptr(G), d,
+                                              float(graph.alpha0), ptr(s.lam_row), ptr(X_out), ptr(fail), ptr(dbg_normal),
+                                              ptr(ws) if w.n_slots else None, ws.numel() if w.n_slots else 0, stream_ptr()),
+          "pda_ials_half_sweep_f32")
+    mark_modified(X_out)
+    return X_out
+
+
+def ials_loss(graph: IalsGraph, X, Y, *, G=None):
+    """The objective of include/pda_hip_ials.h at the tables (X, Y) -> float64 [3] on the device, (L, fit, reg): fit = the squared errors of the
+    observed pairs + alpha0 x the squared scores of all pairs, reg = the regulariser of both sides, L = fit + reg.  pda_ials_loss_f32 writes the
+    three terms of every user row; they are summed here in float64 by torch reductions, as is the item side's regulariser.  G: Y^T Y (computed
+    here when missing).  No host read."""
+    X, Y = _ials_table(X, graph.n_users, "X"), _ials_table(Y, graph.n_items, "Y")
+    d = X.shape[1]
+    if Y.shape[1] != d:
+        raise ValueError("iALS: X and Y share the embedding width")
+    b = graph.buffers(d)
+    if G is None:
+        G = ials_gram(Y, b["G"], b["ws"])
+    s = graph.user
+    check(_lib.load().pda_ials_loss_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(X), ptr(Y), graph.n_items, ptr(G), d,
+                                        ptr(s.lam_row), ptr(b["rows"]), stream_ptr()), "pda_ials_loss_f32")
+    t = b["rows"].double().sum(0)
+    reg_items = (graph.item.lam_row.double() * Y.double().square().sum(1)).sum()
+    fit = t[0] + graph.alpha0 * t[1]
+    reg = t[2] + reg_items
+    return torch.stack([fit + reg, fit, reg])

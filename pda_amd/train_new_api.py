@@ -29,8 +29,8 @@ import torch
 from . import ops
 from .exposure import BiasReport, EvalResult
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import (BPRMF, DICE, IPSBPRMF, MACRBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice,
-                        check_dns, check_ips, check_lightgcn, check_macr, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
+from .model_api import (BPRMF, DICE, IALSMF, IPSBPRMF, MACRBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice,
+                        check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -158,6 +158,11 @@ class DatasetApi_Model:
             #  the train mask and the logQ table come from the sampler's graph; a model that only ranks (export_topk) has no sampler
             if self.Recommender.ssm_source == "batch" and hasattr(generator_sampler, "indptr"):
                 self.Recommender.set_train_graph(generator_sampler.indptr, generator_sampler.indices, generator_sampler.pool)
+        elif args.train == "ials":
+            # iALS: the tables of a BPRMF solved row by row; no batches, the trainer calls train_epoch()
+            self.input_type = "without_pop"
+            print("dataset api without pop")
+            self.Recommender = IALSMF(args, data_config, use_dataset_api=True, device=self.device)
         elif args.train == "macr":
             # MACR: the tables of a BPRMF plus two branch vectors; lists ranked by (y - c) s_i through the bias head
             self.input_type = "without_pop"
@@ -537,6 +542,7 @@ def main(argv=None):
     elif args.model != "mf":
         raise NotImplementedError("--model %s: mf | lightgcn" % args.model)
     check_dns(args)                        # (--neg_sampler dns)
+    check_ials(args)                       # (--train ials | --test ials)
     if args.train == "dice":
         check_dice(args)
         if args.test not in ("normal", "dice"):
@@ -579,14 +585,18 @@ def main(argv=None):
     if args.model == "lightgcn":           # the graph's edges reach the model the way ips_item_counts does
         config["gcn_train_pairs"] = gcn_train_pairs(data.train_user_list)
         args.saveID += "gcn_layers-{}".format(args.gcn_layers)
-    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr", "ssm"):   # :963-970 (DICE, IPS and SSM are evaluated like a BPRMF: --test normal)
+    if args.train == "ials":               # the pairs reach the model the way a LightGCN's edges do
+        config["gcn_train_pairs"] = gcn_train_pairs(data.train_user_list)
+    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr", "ssm", "ials"):   # :963-970 (DICE, IPS and SSM are evaluated like a BPRMF: --test normal)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
         print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------", "macr": "-------    running MACR  ----------------",
-               "ssm": "-------    running SSM  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
+               "ssm": "-------    running SSM  ----------------", "ials": "-------    running iALS  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
         if args.train == "macr":
             args.saveID += "macr"
         if args.train == "ssm":
             args.saveID += "ssm"
+        if args.train == "ials":
+            args.saveID += "ials"
         if args.train == "ips":
             args.saveID += "ips"
             config["ips_item_counts"] = ips_item_counts(data.train_user_list, data.n_items)
@@ -622,7 +632,9 @@ def main(argv=None):
     else:
         raise NotImplementedError("do not implement this method")               # :1008
 
-    if args.train == "temp_pop":
+    if args.train == "ials":               # no sampler: every epoch is two half-sweeps over all pairs
+        sampler = None
+    elif args.train == "temp_pop":
         if args.sampler == "device":
             sampler = DeviceSampler(data, device, False, temp_slots=config["temp_num"])
         else:
@@ -683,21 +695,28 @@ def main(argv=None):
         torch.save(rec.state_dict(), save_ckpt_dir + name)
 
     for epoch in range(args.epoch):
-        if args.train == "dice":                        # DICE's schedule: the margin and the two loss weights decay at the start of an epoch
-            rec.start_epoch(epoch, sampler.start_epoch(epoch))
-        model.switch_to_training_or_reinitsampler(sess)
-        rec.start_loss_rows(n_batch + 1)                # losses stay on the device, a row per step: one reduction and one sync per epoch
-        extra = torch.zeros(3, dtype=torch.float64, device=device)
-        try:
-            while True:
-                before = rec._loss_row_i
-                row = sess.run_async(fetches)
-                if rec._loss_row_i == before:           # (a generator longer than n_batch + 1 steps: the step fell back to the ring's rows)
-                    extra += rec.trainer_terms(row) if hasattr(rec, "trainer_terms") else row[:3]
-        except OutOfRangeError:
-            pass
-        acc = rec.finish_loss_rows() + extra
-        loss, mf_loss, reg_loss = (acc / n_batch).tolist()
+        if args.train == "ials":
+            # no batch loop: two half-sweeps and the objective; the epoch's one host read takes (loss, fit, reg) / |S| and the failed-pivot counter
+            loss, mf_loss, reg_loss, failed = torch.cat([rec.train_epoch(), rec.failed_pivots().double()]).tolist()
+            if failed:
+                print("ERROR: %d rows had a failed pivot (non-finite tables?)." % int(failed))
+                sys.exit()
+        else:
+            if args.train == "dice":                    # DICE's schedule: the margin and the two loss weights decay at the start of an epoch
+                rec.start_epoch(epoch, sampler.start_epoch(epoch))
+            model.switch_to_training_or_reinitsampler(sess)
+            rec.start_loss_rows(n_batch + 1)            # losses stay on the device, a row per step: one reduction and one sync per epoch
+            extra = torch.zeros(3, dtype=torch.float64, device=device)
+            try:
+                while True:
+                    before = rec._loss_row_i
+                    row = sess.run_async(fetches)
+                    if rec._loss_row_i == before:       # (a generator longer than n_batch + 1 steps: the step fell back to the ring's rows)
+                        extra += rec.trainer_terms(row) if hasattr(rec, "trainer_terms") else row[:3]
+            except OutOfRangeError:
+                pass
+            acc = rec.finish_loss_rows() + extra
+            loss, mf_loss, reg_loss = (acc / n_batch).tolist()
         if np.isnan(loss):
             print("ERROR: loss is nan.")
             sys.exit()
@@ -726,7 +745,7 @@ def main(argv=None):
             print("||------------PDA/PDGA injecting linear predicted popularity testing : time: ", int(time() - ttt1))
             _print_result(ret2)
             ret = ret1
-        elif args.test in ("temp_pop", "dice", "ips", "ssm"):                    # :1192-1200 (--test dice / ips / ssm: the main_branch head alone)
+        elif args.test in ("temp_pop", "dice", "ips", "ssm", "ials"):            # :1192-1200 (--test dice / ips / ssm / ials: the main_branch head alone)
             print(perf_str)
             ttt1 = time()
             evaluation_model.set_testing_popularity(None)
@@ -857,11 +876,11 @@ def main(argv=None):
         ret = evaluation_model.eval(model, sess, rec_type="macr")
         print("---- MACR result with the best c of the validation (c = {:.6f}):".format(rec.best_c))
         _print_result(ret)
-    elif args.test in ("temp_pop", "dice", "ips", "ssm"):                        # :1310-1314
+    elif args.test in ("temp_pop", "dice", "ips", "ssm", "ials"):                # :1310-1314
         evaluation_model.set_testing_popularity(None)
         ret = evaluation_model.eval(model, sess, rec_type="main_branch")
         print({"temp_pop": "---- result with last pop bias for temp_pop model:", "dice": "---- DICE result (interest + conformity):"}
-              .get(args.test, "---- SSM result:" if args.test == "ssm" else "---- IPS result:"))
+              .get(args.test, {"ssm": "---- SSM result:", "ials": "---- iALS result:"}.get(args.test, "---- IPS result:")))
         _print_result(ret)
     print("training and testing end!!!!")
     print("|||  ------------------------ best performance for model selected by PD/PDG/BPRMF ------------------- |||")

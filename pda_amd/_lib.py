@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h, pda_hip_dns.h and pda_hip_ials.h).
+pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h and pda_hip_fullsm.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -273,6 +273,18 @@ IALS_SIGNATURES = {
     "pda_ials_loss_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_fullsm.h (the full-catalogue softmax: `--train ssm --ssm_source all`)
+FULLSM_MAX_B = 16384
+FULLSM_ROW_TILE = 32
+FULLSM_COL_TILE = 32
+FULLSM_SIGNATURES = {
+    "pda_fullsm_col_splits": (_i, [_sz, _i]),
+    "pda_fullsm_workspace_bytes": (_sz, [_i, _sz, _i]),
+    "pda_fullsm_step_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _f, _f] + [_vp] * 4 + [_i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "pda_fullsm_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _f, _f, _i, _f, _f, _f, _f, _i, _i,
+                                      _vp, _sz, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -293,7 +305,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(TEMP_POP_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + \
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
-            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()):
+            list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()) + \
+            list(FULLSM_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -744,8 +744,8 @@ def check_ssm(args):
     if getattr(args, "ssm_norm", 1) not in (0, 1):
         raise ValueError("--ssm_norm must be 0 or 1, got %s" % args.ssm_norm)
     source = getattr(args, "ssm_source", "sampled")
-    if source not in ("sampled", "batch"):
-        raise ValueError("--ssm_source must be sampled or batch, got %s" % (source,))
+    if source not in ("sampled", "batch", "all"):
+        raise ValueError("--ssm_source must be sampled, batch or all, got %s" % (source,))
     for flag in ("ssm_logq", "ssm_mask_train"):
         if getattr(args, flag, 1) not in (0, 1):
             raise ValueError("--%s must be 0 or 1, got %s" % (flag, getattr(args, flag)))
@@ -754,6 +754,10 @@ def check_ssm(args):
         if int(B) != B or not 2 <= int(B) <= ops.INBATCH_MAX_B:
             raise ValueError("--batch_size must be an integer in 2 .. %d with --ssm_source batch (a row's negatives are the other rows' "
                              "positives), got %s" % (ops.INBATCH_MAX_B, B))
+    if source == "all":
+        B = getattr(args, "batch_size", 2048)
+        if int(B) != B or not 1 <= int(B) <= ops.FULLSM_MAX_B:
+            raise ValueError("--batch_size must be an integer in 1 .. %d with --ssm_source all, got %s" % (ops.FULLSM_MAX_B, B))
 
 
 def check_dns(args):
@@ -797,7 +801,10 @@ class SSMBPRMF(BPRMF):
     checkpoint always hold the RAW tables.
     --ssm_source batch (include/pda_hip_inbatch.h): a row's negatives are the other rows' positives, a step is the train mask
     (--ssm_mask_train 1) and pda_inbatch_adam_step_f32 with the logQ table (--ssm_logq 1); the trainer hands the train graph over with
-    set_train_graph before the first step.  Tables, lists and checkpoint layout are the same."""
+    set_train_graph before the first step.  Tables, lists and checkpoint layout are the same.
+    --ssm_source all (include/pda_hip_fullsm.h): a row's negatives are ALL items the user has not interacted with
+    (--ssm_mask_train 1; every item with 0), the loss the other two sources estimate; a step is pda_fullsm_adam_step_f32 on the train graph of
+    set_train_graph.  --ssm_negs and --ssm_logq play no part."""
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
         check_ssm(args)
@@ -812,11 +819,12 @@ class SSMBPRMF(BPRMF):
         self.ssm_mask_train = int(getattr(args, "ssm_mask_train", 1))
         self._graph = None                   # (train_indptr, train_indices, user_pool) of --ssm_source batch
         self._inbatch = None                 # its workspace, mask and logq, allocated once
+        self._fullsm = None                  # the workspace of --ssm_source all, allocated once
 
     def set_train_graph(self, train_indptr, train_indices, user_pool=None):
-        """--ssm_source batch: the train CSR on the device (int64 indptr, int32 item ids sorted inside a row) the mask is taken from, and the
-        sampler's user pool the logQ table is computed for."""
-        self._graph, self._inbatch = (train_indptr, train_indices, user_pool), None
+        """--ssm_source batch | all: the train CSR on the device (int64 indptr, int32 item ids sorted inside a row) the mask is taken from, and
+        (batch) the sampler's user pool the logQ table is computed for."""
+        self._graph, self._inbatch, self._fullsm = (train_indptr, train_indices, user_pool), None, None
 
     def _inbatch_buffers(self, B, U, I):
         if self._inbatch is None or self._inbatch["B"] != B:
@@ -842,7 +850,7 @@ class SSMBPRMF(BPRMF):
 
     def train_step(self, users, pos, negs=None, plan=None) -> torch.Tensor:
         """One sampled-softmax step on (users [B], pos [B], negs [B, N]); returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this
-        step, as BPRMF.train_step does.  Nothing is read on the host.  --ssm_source batch: negs is ignored (the triplet sampler's negative)."""
+        step, as BPRMF.train_step does.  Nothing is read on the host.  --ssm_source batch | all: negs is ignored (the triplet sampler's negative)."""
         U, I = self.weights["user_embedding"], self.weights["item_embedding"]
         rows = getattr(self, "_loss_rows", None)
         if rows is not None and self._loss_row_i < rows.shape[0]:
@@ -865,6 +873,18 @@ class SSMBPRMF(BPRMF):
                                   lr_t=ops.adam_lr_t(self.lr, self._t), logq=b["logq"], mask=b["mask"],
                                   users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
             return self._loss
+        if self.ssm_source == "all":
+            B = users.numel()
+            if self.ssm_mask_train and self._graph is None:
+                raise ValueError("--ssm_source all with --ssm_mask_train 1 needs the train graph: call set_train_graph first")
+            if self._fullsm is None or self._fullsm[0] != B:
+                self._fullsm = (B, ops.fullsm_workspace(B, I.shape[0], I.shape[1], U.device))
+            indptr, indices = (self._graph[0], self._graph[1]) if self.ssm_mask_train else (None, None)
+            ops.fullsm_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos,
+                                 self._fullsm[1], tau=self.ssm_tau, norm=self.ssm_norm, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                                 lr_t=ops.adam_lr_t(self.lr, self._t), train_indptr=indptr, train_indices=indices,
+                                 users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+            return self._loss
         ops.ssm_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, negs,
                           tau=self.ssm_tau, norm=self.ssm_norm, regs=self.decay, reg_div=self.batch_size, step=self._t,
                           lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
@@ -875,6 +895,8 @@ class SSMBPRMF(BPRMF):
         sd.update(ssm_negs=self.ssm_negs, ssm_tau=self.ssm_tau, ssm_norm=self.ssm_norm)
         if self.ssm_source == "batch":      # (a sampled run's checkpoint keeps the keys it had)
             sd.update(ssm_source=self.ssm_source, ssm_logq=self.ssm_logq, ssm_mask_train=self.ssm_mask_train)
+        elif self.ssm_source == "all":      # (no logQ on the exact softmax)
+            sd.update(ssm_source=self.ssm_source, ssm_mask_train=self.ssm_mask_train)
         return sd
 
 

@@ -2959,6 +2959,95 @@ def inbatch_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, ws, 
     mark_modified(U, I)
 
 
+# ---- the full-catalogue softmax (include/pda_hip_fullsm.h) -----------------------------------------------------------------------------------------
+FULLSM_MAX_B = _lib.FULLSM_MAX_B
+FULLSM_ROW_TILE = _lib.FULLSM_ROW_TILE
+FULLSM_COL_TILE = _lib.FULLSM_COL_TILE
+
+
+def _fullsm_sizes(B, n_items):
+    if not 1 <= int(B) <= FULLSM_MAX_B:
+        raise ValueError(f"full softmax: the batch size must lie in 1 .. {FULLSM_MAX_B}, got {B}")
+    if not 1 <= int(n_items) <= 2 ** 31 - 1:
+        raise ValueError(f"full softmax: n_items must lie in 1 .. 2^31 - 1, got {n_items}")
+
+
+def fullsm_col_splits(n_items: int, B: int) -> int:
+    """pda_fullsm_col_splits: the column ranges the row-statistics pass and the user-side pass split the n_items columns into."""
+    _fullsm_sizes(B, n_items)
+    return int(_lib.load().pda_fullsm_col_splits(int(n_items), int(B)))
+
+
+def fullsm_workspace(B: int, n_items: int, d: int, device) -> torch.Tensor:
+    """The workspace of one batch size, catalogue and width (pda_fullsm_workspace_bytes): uint8, private to one stream."""
+    _fullsm_sizes(B, n_items)
+    if d not in SSM_EMBED_SIZES:
+        raise ValueError(f"full softmax: the embedding width d must be one of {SSM_EMBED_SIZES}, got {d}")
+    return torch.empty(int(_lib.load().pda_fullsm_workspace_bytes(int(B), int(n_items), int(d))), dtype=torch.uint8, device=device)
+
+
+def _fullsm_check(U, I, users, pos, train_indptr, train_indices, tagU, tagI, ws, loss_acc, row_stats, check_ids: bool):
+    """The tables and (users, pos) as every tagged step checks them (the checks of _inbatch_check), the optional train CSR (int64 [n_users + 1],
+    int32, both or neither), the workspace and the optional row_stats float32 [B, 2] -> (d, B)."""
+    d, B = _triplet_shapes("full softmax", "U [n_users, d] and I [n_items, d]", SSM_EMBED_SIZES, U, I, users, pos, pos)
+    if B > FULLSM_MAX_B:
+        raise ValueError(f"full softmax: the batch size must lie in 1 .. {FULLSM_MAX_B}, got {B}")
+    if (train_indptr is None) != (train_indices is None):
+        raise ValueError("full softmax: train_indptr and train_indices go together (both None: no item is excluded)")
+    if _need(train_indptr, torch.int64, "train_indptr", optional=True) is not None:
+        _need(train_indices, torch.int32, "train_indices")
+        if train_indptr.numel() != U.shape[0] + 1:
+            raise ValueError("train_indptr holds n_users + 1 int64")
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(ws, torch.uint8, "ws").numel() < int(_lib.load().pda_fullsm_workspace_bytes(B, I.shape[0], d)):
+        raise ValueError("ws: the workspace of fullsm_workspace(B, n_items, d)")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("full softmax loss_acc holds three float32")
+    if _need(row_stats, torch.float32, "row_stats", optional=True) is not None and row_stats.numel() != 2 * B:
+        raise ValueError(f"row_stats: float32 [B, 2] = [{B}, 2]")
+    _triplet_ids("full softmax", U, I, users, pos, pos, check_ids)
+    return d, B
+
+
+def fullsm_step(U, I, users, pos, gU, gI, tagU, tagI, ws, *, tau: float, norm: int, regs: float, reg_div: float, step: int, train_indptr=None,
+                train_indices=None, users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None,
+                row_stats: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_fullsm_step_f32: the batch's full-catalogue softmax gradient summed into gU / gI (the users' rows and EVERY item row tagged `step`), no
+    update.  loss_acc float32 [3] += (loss, mf_loss, reg_loss); row_stats float32 [B, 2] = (m_r, log se_r)."""
+    d, B = _fullsm_check(U, I, users, pos, train_indptr, train_indices, tagU, tagI, ws, loss_acc, row_stats, check_ids)
+    tau, norm = _ssm_params(tau, norm)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    check(_lib.load().pda_fullsm_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), B, d, tau, norm, ptr(train_indptr),
+                                          ptr(train_indices), float(regs), float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step),
+                                          _ips_flags(False, users_distinct), ptr(ws), ws.numel(), ptr(loss_acc), ptr(row_stats), stream_ptr()),
+          "pda_fullsm_step_f32")
+    mark_modified(gU, gI)
+
+
+def fullsm_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, ws, *, tau: float, norm: int, regs: float, reg_div: float, step: int,
+                     lr_t: float, train_indptr=None, train_indices=None, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS,
+                     users_distinct: bool = False, cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None,
+                     row_stats: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_fullsm_adam_step_f32: one full-catalogue softmax train step (the gradients, TF-1.14 dense-decay Adam over both tables);
+    graph-capturable.  The arguments of inbatch_adam_step with the train CSR in place of logq and mask."""
+    d, B = _fullsm_check(U, I, users, pos, train_indptr, train_indices, tagU, tagI, ws, loss_acc, row_stats, check_ids)
+    tau, norm = _ssm_params(tau, norm)
+    for t in (mU, vU, gU, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_fullsm_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI),
+                                               ptr(tagI), I.shape[0], ptr(users), ptr(pos), B, d, tau, norm, ptr(train_indptr), ptr(train_indices),
+                                               float(regs), float(reg_div), int(step), float(lr_t), beta1, beta2, eps,
+                                               _ips_flags(False, users_distinct), int(cache_policy), ptr(ws), ws.numel(), ptr(loss_acc),
+                                               ptr(row_stats), stream_ptr()),
+          "pda_fullsm_adam_step_f32")
+    mark_modified(U, I)
+
+
 # ---- dynamic hard-negative sampling (include/pda_hip_dns.h) -----------------------------------------------------------------------------------------
 DNS_MAX_CANDIDATES = _lib.DNS_MAX_CANDIDATES
 DNS_EMBED_SIZES = (32, 64, 128, 256)

@@ -88,10 +88,10 @@ _EXTENSION_FLAGS = [
     ("neg_sampler", str, "uniform", "where a triplet's negative comes from: uniform = one uniform draw outside the user's train items (the reference) | dns = dynamic hard-negative sampling, DNS(M, N): one of the --dns_topn best-scoring of --dns_candidates uniform draws under the current tables (include/pda_hip_dns.h; --train normal | s_condition, fp32 tables, the device sampler, one GPU)"),
     ("dns_candidates", int, 16, "DNS (--neg_sampler dns): candidates M drawn and scored per triplet, 1 .. 256 (1: the uniform sampler's batches, bit for bit)"),
     ("dns_topn", int, 1, "DNS: the negative is drawn uniformly from the N best of the M candidates, 1 .. --dns_candidates (1: the best one, the classic DNS)"),
-    ("ssm_source", str, "sampled", "SSM (--train ssm): where a row's negatives come from.  sampled = --ssm_negs uniform draws per row | batch = the other rows' positives (in-batch softmax, include/pda_hip_inbatch.h: --batch_size - 1 shared negatives per row, --batch_size in 2 .. 16384)"),
-    ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1"),
-    ("ssm_mask_train", int, 1, "SSM with --ssm_source batch: 1 leaves a column out of a row's softmax when its item is a train item of the row's user (the sampled path rejects the same items when it draws); 0 | 1"),
-    ("ssm_negs", int, 64, "SSM (--train ssm): sampled negatives per row of the softmax, 1 .. 256; unused with --ssm_source batch"),
+    ("ssm_source", str, "sampled", "SSM (--train ssm): where a row's negatives come from.  sampled = --ssm_negs uniform draws per row | batch = the other rows' positives (in-batch softmax, include/pda_hip_inbatch.h: --batch_size - 1 shared negatives per row, --batch_size in 2 .. 16384) | all = every item of the catalogue, no sampling (the exact softmax both estimate, include/pda_hip_fullsm.h: --batch_size in 1 .. 16384)"),
+    ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1; unused with --ssm_source all (nothing is sampled, so there is nothing to correct)"),
+    ("ssm_mask_train", int, 1, "SSM with --ssm_source batch: 1 leaves a column out of a row's softmax when its item is a train item of the row's user (the sampled path rejects the same items when it draws); with --ssm_source all: 1 leaves the user's other train items out of the row's softmax over the catalogue, 0 keeps every item; 0 | 1"),
+    ("ssm_negs", int, 64, "SSM (--train ssm): sampled negatives per row of the softmax, 1 .. 256; unused with --ssm_source batch and with --ssm_source all"),
     ("ssm_tau", float, 0.1, "SSM: the temperature tau of the logits, > 0"),
     ("ssm_norm", int, 1, "SSM: 1 takes the logits on cosine similarity (rows normalised to length 1, in training and in the lists), 0 on the raw dot product; 0 | 1"),
     ("ips_clip", float, 0.0, "IPS (--train ips): clip the inverse propensity weights at this value (IPS-C); 0: no clip"),

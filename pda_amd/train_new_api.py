@@ -156,7 +156,7 @@ class DatasetApi_Model:
             print("dataset api without pop")
             self.Recommender = SSMBPRMF(args, data_config, use_dataset_api=True, device=self.device)
             #  the train mask and the logQ table come from the sampler's graph; a model that only ranks (export_topk) has no sampler
-            if self.Recommender.ssm_source == "batch" and hasattr(generator_sampler, "indptr"):
+            if self.Recommender.ssm_source in ("batch", "all") and hasattr(generator_sampler, "indptr"):
                 self.Recommender.set_train_graph(generator_sampler.indptr, generator_sampler.indices, generator_sampler.pool)
         elif args.train == "ials":
             # iALS: the tables of a BPRMF solved row by row; no batches, the trainer calls train_epoch()
@@ -645,7 +645,7 @@ def main(argv=None):
         else:
             sampler = HostDiceSampler(data, args.dice_margin, args.dice_margin_decay)
     elif args.train == "ssm":              # (check_ssm has refused --sampler host)
-        if args.ssm_source == "batch":     # in-batch negatives: the triplet sampler without popularity columns; its negative is ignored
+        if args.ssm_source in ("batch", "all"):    # in-batch negatives / the whole catalogue: the triplet sampler without popularity columns; its negative is ignored
             sampler = DeviceSampler(data, device, False)
         else:
             sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs)

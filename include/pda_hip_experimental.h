@@ -114,6 +114,22 @@ int pda_score_topk4_phase_mask_rows(const void* prep, const int32_t* users, int 
                                     const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int warm_tiles, uint32_t* out,
                                     void* stream);
 int pda_score_topk4_phase_mask_offsets(int n_users_blk, int n_items_local, int d, int n_splits, size_t* offs);
+/* The rest of the per-block user data of the pre-filtered paths, each the per-call kernel on one block as a call of its own (tests hold every field
+ * to a restatement computed from the inputs alone):
+ *   pda_score_topk7_phase_user_image   the funnel's image: fp16 MFMA operands in the layout of pda_score_topk4_phase_user_image (ufrag: offs[3] x
+ *            2 d bytes), the padded norms and the padded norms of the rounding residuals u - fp16(u) (unorm, uerr: offs[3] floats each)
+ *   pda_score_topk4_phase_bloom_rows   generation 4's Bloom filters of the block's train items over item ids AS STORED: bloom u32 [n_users_blk][32],
+ *            bits (id * 0x9E3779B1) >> 22 and (id * 0x85EBCA6B + 0x27D4EB2F) >> 22 (uint32 arithmetic) of the row's 1 024.  prep: any generation-4
+ *            prep (its header is read); skip_if_ordered != 0 and a prep built with an order: nothing is written, as in a call of the popularity head
+ *   pda_score_topk7_phase_bloom_rows   the funnel's: the same bits of the VISITING POSITION of every train item inside
+ *            [item_offset, item_offset + n_items_local) (prep: a pda_item_prep7_* blob of that shard); ids outside set nothing
+ * Rows of `bloom` beyond the block are not written. */
+int pda_score_topk7_phase_user_image(const void* U, int bf16, const int32_t* users, int n_users_blk, int d, void* ufrag, float* unorm, float* uerr,
+                                     void* stream);
+int pda_score_topk4_phase_bloom_rows(const void* prep, const int32_t* users, int n_users_blk, const int64_t* hist_indptr,
+                                     const int32_t* hist_indices, int hist_row_mode, int skip_if_ordered, uint32_t* bloom, void* stream);
+int pda_score_topk7_phase_bloom_rows(const void* prep, const int32_t* users, int n_users_blk, int item_offset, int n_items_local, int d,
+                                     const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, uint32_t* bloom, void* stream);
 /* early_stop bit 11 of pda_score_topk4_* (beside PDA_SWEEP_WARM_PER_SPLIT, bit 10; results never depend on it).  The dense call of the
  * huge geometry (PDA_SWEEP_HUGE, popularity head, no early termination, d <= 128, one warm-up over the front of the whole order) runs its
  * exact warm-up as TWO kernels: a score kernel that keeps the 256 warm item rows in the LDS and only multiplies, and a select kernel at

@@ -92,6 +92,9 @@ SIGNATURES = {
     "pda_score_topk4_phase_mask_table": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "pda_score_topk4_phase_mask_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "pda_score_topk4_phase_mask_offsets": (_i, [_i, _i, _i, _i, _vp]),
+    "pda_score_topk7_phase_user_image": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "pda_score_topk4_phase_bloom_rows": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "pda_score_topk7_phase_bloom_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "pda_score_topk4_phase_masked_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "pda_score_topk4_phase_masked_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "pda_score_topk_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp]),

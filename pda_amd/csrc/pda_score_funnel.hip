@@ -422,6 +422,40 @@ extern "C" int pda_score_topk_plan(int n_users_blk, int n_items_local, int d, in
     return PDA_OK;
 }
 
+// ---- what the funnel makes of a user block before its first sweep, as calls of their own (tests hold every field to a float64 restatement) ----
+//   pda_score_topk7_phase_user_image   uprep5_kernel<.., F16 = true>: ufrag n_pad x 2 d bytes of fp16 operands, unorm and uerr n_pad floats each
+//                                      (n_pad: offs[3] of pda_score_topk4_phase_image_offsets)
+extern "C" int pda_score_topk7_phase_user_image(const void* U, int bf16, const int32_t* users, int n_users_blk, int d, void* ufrag, float* unorm, float* uerr,
+                                                void* stream) {
+    if (!U || !users || !ufrag || !unorm || !uerr || n_users_blk <= 0) return PDA_ERR_ARG;
+    if (d != 64 && d != 128 && d != 256) return PDA_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t ut = d == 256 ? 512 : 1024, n_pad = ((size_t)n_users_blk + ut - 1) / ut * ut;
+#define PDA_UIMG7_(DD, BFV, UPWV)                                                                                                                   \
+    hipLaunchKernelGGL((uprep5_kernel<DD, BFV, true, UPWV, true>), dim3((unsigned)((n_pad * (DD / 8) + 255) / 256)), dim3(256), 0, s, U, users, n_users_blk, \
+                       (int)n_pad, reinterpret_cast<unsigned char*>(ufrag), unorm, uerr)
+    if (d == 64) { if (bf16) PDA_UIMG7_(64, true, 256); else PDA_UIMG7_(64, false, 256); }
+    else if (d == 128) { if (bf16) PDA_UIMG7_(128, true, 256); else PDA_UIMG7_(128, false, 256); }
+    else { if (bf16) PDA_UIMG7_(256, true, 128); else PDA_UIMG7_(256, false, 128); }
+#undef PDA_UIMG7_
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+//   pda_score_topk7_phase_bloom_rows   hist_bloom7_kernel on one block: bloom u32 [n_users_blk][32] over the visiting positions of a prep7 (rows beyond
+//                                      the block are not written)
+extern "C" int pda_score_topk7_phase_bloom_rows(const void* prep, const int32_t* users, int n_users_blk, int item_offset, int n_items_local, int d,
+                                                const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, uint32_t* bloom, void* stream) {
+    if (!prep || !users || !hist_indptr || !hist_indices || !bloom || n_users_blk <= 0 || n_items_local <= 0 || item_offset < 0) return PDA_ERR_ARG;
+    if (hist_row_mode != PDA_HIST_BY_USER_ID && hist_row_mode != PDA_HIST_BY_BLOCK_ROW) return PDA_ERR_ARG;
+    if (d != 64 && d != 128 && d != 256) return PDA_ERR_UNSUPPORTED;
+    const Prep4Layout L = prep4_layout(n_items_local, d);
+    hipLaunchKernelGGL(hist_bloom7_kernel, dim3((unsigned)((n_users_blk + 31) / 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), users, hist_indptr,
+                       hist_indices, hist_row_mode, n_users_blk, reinterpret_cast<const int*>(reinterpret_cast<const unsigned char*>(prep) + L.pos_of), item_offset,
+                       n_items_local, bloom);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
 // ---- debug / measurement entry of the funnel's emitting sweep (tools/time_emit.py): one launch against the caller's thresholds ----------
 // workspace: [256 B counters | user image | norms | eu per wave | cursors | lists]; offs[0..4] = byte offsets of (unorm, eu, cursors, lists, end)
 extern "C" size_t pda_debug_emit_layout(int n_users_blk, int d, int n_splits, int cap_e, size_t* offs) {

@@ -2972,3 +2972,14 @@ extern "C" int pda_score_topk4_phase_user_image(const void* U, int bf16, const i
     PDA_CHECK_LAUNCH();
     return PDA_OK;
 }
+//   pda_score_topk4_phase_bloom_rows   hist_bloom4_kernel on one block as a call of its own: bloom u32 [n_users_blk][32] (rows beyond the block are
+//                                      not written; skip_if_ordered != 0 and a prep built with an order: nothing is written, as in the call)
+extern "C" int pda_score_topk4_phase_bloom_rows(const void* prep, const int32_t* users, int n_users_blk, const int64_t* hist_indptr,
+                                                const int32_t* hist_indices, int hist_row_mode, int skip_if_ordered, uint32_t* bloom, void* stream) {
+    if (!prep || !users || !hist_indptr || !hist_indices || !bloom || n_users_blk <= 0) return PDA_ERR_ARG;
+    if (hist_row_mode != PDA_HIST_BY_USER_ID && hist_row_mode != PDA_HIST_BY_BLOCK_ROW) return PDA_ERR_ARG;
+    hipLaunchKernelGGL(hist_bloom4_kernel, dim3((unsigned)((n_users_blk + 31) / 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), users, hist_indptr,
+                       hist_indices, hist_row_mode, n_users_blk, bloom, reinterpret_cast<const int*>(prep), skip_if_ordered ? 1 : 0);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}

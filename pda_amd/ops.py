@@ -862,6 +862,54 @@ def huge_user_image(U: torch.Tensor, users: torch.Tensor):
     return ufrag, unorm
 
 
+def funnel_user_image(U: torch.Tensor, users: torch.Tensor):
+    """pda_score_topk7_phase_user_image: the block as the funnel prepares it -> (fp16 image uint8 [n_pad * 2 d], padded norms float32 [n_pad],
+    padded norms of the rounding residuals float32 [n_pad])."""
+    lib = _lib.load()
+    bf = U.dtype == torch.bfloat16
+    U = _need(U, torch.bfloat16 if bf else torch.float32, "U")
+    users = _need(users, torch.int32, "users")
+    d, nu = U.shape[1], users.numel()
+    ut = 512 if d == 256 else 1024
+    n_pad = -(-nu // ut) * ut
+    ufrag = torch.empty(n_pad * 2 * d, dtype=torch.uint8, device=U.device)
+    unorm = torch.empty(n_pad, dtype=torch.float32, device=U.device)
+    uerr = torch.empty(n_pad, dtype=torch.float32, device=U.device)
+    check(lib.pda_score_topk7_phase_user_image(ptr(U), 1 if bf else 0, ptr(users), nu, d, ptr(ufrag), ptr(unorm), ptr(uerr), stream_ptr()),
+          "pda_score_topk7_phase_user_image")
+    return ufrag, unorm, uerr
+
+
+def _bloom_out(users: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if out is None:
+        return torch.empty((users.numel(), 32), dtype=torch.int32, device=users.device)
+    out = _need(out, torch.int32, "out")
+    if out.dim() != 2 or out.shape[1] != 32 or out.shape[0] < users.numel():
+        raise ValueError("out must be int32 [at least the block's rows, 32]")
+    return out
+
+
+def hist_bloom_rows(prep: torch.Tensor, users: torch.Tensor, hist: "HistoryCSR", skip_if_ordered: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_score_topk4_phase_bloom_rows: hist_bloom4_kernel on a block as a call of its own -> int32 [block rows, 32], the 1 024-bit Bloom filter
+    of every row's train-item ids.  out: the caller's buffer (rows beyond the block, and every row where skip_if_ordered applies, stay as they are)."""
+    users = _need(users, torch.int32, "users")
+    out = _bloom_out(users, out)
+    check(_lib.load().pda_score_topk4_phase_bloom_rows(ptr(prep), ptr(users), users.numel(), ptr(hist.indptr), ptr(hist.indices), hist.mode,
+                                                       1 if skip_if_ordered else 0, ptr(out), stream_ptr()), "pda_score_topk4_phase_bloom_rows")
+    return out
+
+
+def funnel_bloom_rows(prep7: torch.Tensor, users: torch.Tensor, hist: "HistoryCSR", item_offset: int, nloc: int, d: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_score_topk7_phase_bloom_rows: hist_bloom7_kernel on a block as a call of its own -> int32 [block rows, 32], the Bloom filter of the
+    visiting positions (prep7's) of every row's train items inside the shard."""
+    users = _need(users, torch.int32, "users")
+    out = _bloom_out(users, out)
+    check(_lib.load().pda_score_topk7_phase_bloom_rows(ptr(prep7), ptr(users), users.numel(), item_offset, nloc, d, ptr(hist.indptr), ptr(hist.indices),
+                                                       hist.mode, ptr(out), stream_ptr()), "pda_score_topk7_phase_bloom_rows")
+    return out
+
+
 def topk_merge(keys: torch.Tensor, users=None, hist: Optional[HistoryCSR] = None, want="idx_val"):
     """pda_topk_merge.  keys int64[R, Bu, K].  want: 'keys' -> int64[Bu,K];  'idx_val' -> (int32, float32)."""
     lib = _lib.load()

@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h and pda_hip_fullsm.h).
+pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h and pda_hip_rank.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -288,6 +288,16 @@ FULLSM_SIGNATURES = {
                                       _vp, _sz, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_rank.h (exact ranks of held-out items: `--rank_report 1`)
+RANK_TCHUNK = 32
+_rank_head = [_vp] * 4 + [_i, _i, _i, _i, _vp, _vp, _i]
+RANK_SIGNATURES = {
+    "pda_rank_keys_f32": (_i, _rank_head + [_vp, _vp, _i, _vp, _vp]),
+    "pda_rank_keys_bf16": (_i, _rank_head + [_vp, _vp, _i, _vp, _vp]),
+    "pda_rank_count_f32": (_i, _rank_head + [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "pda_rank_count_bf16": (_i, _rank_head + [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -309,7 +319,7 @@ def load():
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
             list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()) + \
-            list(FULLSM_SIGNATURES.items()):
+            list(FULLSM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -21,6 +21,7 @@ import torch
 
 from . import ops
 from .exposure import BiasReport
+from .rank_report import refuse_rank_report
 from .load_data import load_popularity
 from .sampler import host_generator
 
@@ -163,6 +164,7 @@ def main(argv=None):
     if t.check_topk_max(args) > ops.TOPK_K_V4:
         raise NotImplementedError("--topk_max %d: BPR-PC ranks at most %d items per user (its sweep keeps K + 8 candidates on chip and there is "
                                   "no PC head on the deep path)" % (args.topk_max, ops.PC_MAX_K))
+    refuse_rank_report(args, "bpr_pc")
     bias = BiasReport.from_args(args, data, t.Ks)
     random.seed(2020)
     np.random.seed(2020)

@@ -22,6 +22,7 @@ import torch
 
 from .bpr_pc import checkpoint_dir
 from .exposure import BiasReport
+from .rank_report import refuse_rank_report
 from .load_data import get_popularity_from_load, load_popularity
 from .sampler import host_generator
 
@@ -32,6 +33,7 @@ def restore(argv=None):
     t.configure(argv)
     args, data = t.args, t.data
     t.check_topk_max(args)
+    refuse_rank_report(args, "export_topk")
     random.seed(2020)
     np.random.seed(2020)
     torch.manual_seed(2021)

@@ -193,10 +193,11 @@ class ExposureAccumulator:
 
 
 class EvalResult(dict):
-    """The four metric arrays of evaluation.eval, with the bias lines of the same pass (and the BiasReport they come from) beside them, not
-    among the keys."""
+    """The four metric arrays of evaluation.eval, with the bias lines of the same pass (and the BiasReport they come from) and the pass's rank
+    lines (--rank_report 1, pda_amd/rank_report.py) beside them, not among the keys."""
     bias_lines = ()
     bias = None
+    rank_lines = ()
 
 
 def report_ks(Ks, topk_max) -> list:

@@ -3411,3 +3411,100 @@ def ials_loss(graph: IalsGraph, X, Y, *, G=None):
     fit = t[0] + graph.alpha0 * t[1]
     reg = t[2] + reg_items
     return torch.stack([fit + reg, fit, reg])
+
+
+# ---- exact ranks of held-out items (include/pda_hip_rank.h) ---------------------------------------------------------------------------------
+RANK_TCHUNK = _lib.RANK_TCHUNK
+
+
+def _rank_args(U, I_shard, users, tgt_indptr, head, pop_shard, hist):
+    bf = U is not None and U.dtype == torch.bfloat16
+    tdt = torch.bfloat16 if bf else torch.float32
+    U, I_shard = _need(U, tdt, "U"), _need(I_shard, tdt, "I_shard")
+    users = _need(users, torch.int32, "users")
+    tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
+    pop_shard = _need(pop_shard, torch.float32, "pop_shard", optional=True)
+    nu, nloc, d = users.numel(), I_shard.shape[0], I_shard.shape[1]
+    if U.shape[1] != d:
+        raise ValueError("U and I_shard must share the embed dim")
+    if d not in (32, 64, 128, 256):
+        raise ValueError(f"ranks support embed sizes 32, 64, 128 and 256, not {d}")
+    if head not in (HEAD_RAW, HEAD_POP):
+        raise ValueError("ranks are taken by the raw head or the popularity head")
+    if head == HEAD_POP:
+        if pop_shard is None or pop_shard.numel() != nloc:
+            raise ValueError("pop_shard must hold one value per local item row")
+        _check_pop(pop_shard)
+    if nu == 0 or nloc == 0:
+        raise ValueError("empty user block or item shard")
+    if tgt_indptr.numel() != nu + 1:
+        raise ValueError("tgt_indptr holds one row per user of the block")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    head_args = (ptr(U), ptr(I_shard), ptr(pop_shard), ptr(users), nu)
+    hist_args = (ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0)
+    return bf, nloc, d, head_args, hist_args
+
+
+def rank_max_row(tgt_indptr) -> int:
+    """The longest row of a target CSR (one device -> host read)."""
+    return int((tgt_indptr[1:] - tgt_indptr[:-1]).max().item()) if tgt_indptr.numel() > 1 else 0
+
+
+def rank_keys(U, I_shard, users, tgt_indptr, tgt_indices, head=HEAD_RAW, pop_shard=None, hist: Optional[HistoryCSR] = None, item_offset=0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pda_rank_keys_f32 / _bf16: packed keys int64 [n_entries] of the target entries (CSR by block row: int64 indptr, int32 global item ids):
+    the entry's key if its item lies in the shard and ranks for its user, 0 if it lies in the shard and does not (listed in the history, head
+    value not > -inf).  Entries outside the shard are not written: `out` (zeros when missing) keeps what it held, so the keys of several
+    shards collect in one tensor.  No target, no launch."""
+    bf, nloc, d, head_args, hist_args = _rank_args(U, I_shard, users, tgt_indptr, head, pop_shard, hist)
+    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    if out is None:
+        out = torch.zeros(tgt_indices.numel(), dtype=torch.int64, device=tgt_indices.device)
+    out = _need(out, torch.int64, "out")
+    if out.numel() != tgt_indices.numel():
+        raise ValueError("out holds one key per target entry")
+    if tgt_indices.numel() == 0:
+        return out
+    lib = _lib.load()
+    fn = lib.pda_rank_keys_bf16 if bf else lib.pda_rank_keys_f32
+    check(fn(*head_args, int(item_offset), nloc, d, *hist_args, ptr(tgt_indptr), ptr(tgt_indices), int(head), ptr(out), stream_ptr()),
+          "pda_rank_keys_bf16" if bf else "pda_rank_keys_f32")
+    return out
+
+
+def rank_count(U, I_shard, users, tgt_indptr, tgt_keys, head=HEAD_RAW, pop_shard=None, hist: Optional[HistoryCSR] = None, item_offset=0,
+               n_splits=0, above: Optional[torch.Tensor] = None, n_ranked: Optional[torch.Tensor] = None, max_row: Optional[int] = None):
+    """pda_rank_count_f32 / _bf16 -> (above int32 [n_entries], n_ranked int32 [Bu]), both ADDED to (zeros when missing): above[e] += the ranking
+    items of this shard whose key is > tgt_keys[e] (entries with key 0 are left alone), n_ranked[r] += the ranking items of this shard for
+    block row r.  max_row: the longest target row if the caller knows it (else one host read)."""
+    bf, nloc, d, head_args, hist_args = _rank_args(U, I_shard, users, tgt_indptr, head, pop_shard, hist)
+    tgt_keys = _need(tgt_keys, torch.int64, "tgt_keys")
+    dev = tgt_keys.device
+    if above is None:
+        above = torch.zeros(tgt_keys.numel(), dtype=torch.int32, device=dev)
+    if n_ranked is None:
+        n_ranked = torch.zeros(users.numel(), dtype=torch.int32, device=dev)
+    above, n_ranked = _need(above, torch.int32, "above"), _need(n_ranked, torch.int32, "n_ranked")
+    if above.numel() != tgt_keys.numel() or n_ranked.numel() != users.numel():
+        raise ValueError("above holds one count per target entry and n_ranked one per user of the block")
+    if int(n_splits) < 0:
+        raise ValueError("n_splits must be >= 0 (0: the call chooses)")
+    if max_row is None:
+        max_row = rank_max_row(tgt_indptr) if tgt_keys.numel() else 0
+    lib = _lib.load()
+    fn = lib.pda_rank_count_bf16 if bf else lib.pda_rank_count_f32
+    above_arg = above if above.numel() else torch.zeros(1, dtype=torch.int32, device=dev)     # (no entry: the lengths alone; the call wants a buffer)
+    check(fn(*head_args, int(item_offset), nloc, d, *hist_args, ptr(tgt_indptr), ptr(tgt_keys), int(max_row), int(head), int(n_splits),
+             ptr(above_arg), ptr(n_ranked), stream_ptr()), "pda_rank_count_bf16" if bf else "pda_rank_count_f32")
+    return above, n_ranked
+
+
+def rank_targets(U, I_shard, users, tgt_indptr, tgt_indices, head=HEAD_RAW, pop_shard=None, hist: Optional[HistoryCSR] = None, item_offset=0,
+                 n_splits=0, max_row: Optional[int] = None):
+    """The exact position of every target entry in its user's masked ranking of the shard -> (rank int32 [n_entries], n_ranked int32 [Bu]).
+    rank is 0-based (the number of ranking items above the entry's, value descending, id ascending) and -1 for an entry that does not rank:
+    listed in the history, outside the shard, or head value not > -inf.  n_ranked: the length of the row's ranking."""
+    keys = rank_keys(U, I_shard, users, tgt_indptr, tgt_indices, head, pop_shard, hist, item_offset)
+    above, n_ranked = rank_count(U, I_shard, users, tgt_indptr, keys, head, pop_shard, hist, item_offset, n_splits, max_row=max_row)
+    return torch.where(keys != 0, above, torch.full_like(above, -1)), n_ranked

@@ -82,6 +82,8 @@ _EXTENSION_FLAGS = [
     ("bias_report", int, 0, "1: after every metrics line, `||--- bias@K` lines on what the lists do to popularity bias -- recommendation rate, hit share and recall per popularity group, ARP, coverage, Gini, APLT (pda_amd/exposure.py; the head of APLT is --xq_head_share); one GPU; 0 | 1"),
     ("bias_groups", int, 10, "--bias_report: popularity groups of the items, 1 .. 64 (group 0 = the most popular)"),
     ("bias_group_by", str, "interactions", "--bias_report: interactions = groups of equal train interactions | items = groups of equal item counts"),
+    ("rank_report", int, 0, "1: after every metrics line (and the bias lines), `||--- rank` lines from the exact position of every held-out item in its user's masked full-catalogue ranking -- AUC, MRR, mean percentile rank, mean and median rank, recall@K and hit@K at --rank_ks, and MPR, median rank and recall@K per popularity group of the held-out item (--bias_groups, --bias_group_by); include/pda_hip_rank.h, pda_amd/rank_report.py; the raw and the popularity head on one GPU (not --train temp_pop | macr); accepted with --deterministic 1 (integer counts); 0 | 1"),
+    ("rank_ks", str, "[50, 1000]", "--rank_report: the cut-offs of its recall@K and hit@K, a list literal like --Ks; any positive K (positions are exact at every depth, beyond --topk_max and 1024 too)"),
     ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
     ("ials_alpha0", float, 0.1, "iALS (--train ials, include/pda_hip_ials.h): weight alpha0 of the unobserved pairs, >= 0.  --regs is lambda (> 0); --lr, --optimizer, --adam_sweep, --sampler and --batch_size (for training) are unused by iALS"),
     ("ials_nu", float, 1.0, "iALS: frequency scaling of the regulariser, lambda (n + alpha0 n_other)^nu per row, 0 .. 1 (0: plain L2)"),

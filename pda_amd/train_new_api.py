@@ -28,6 +28,7 @@ import torch
 
 from . import ops
 from .exposure import BiasReport, EvalResult
+from .rank_report import RankReport
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
 from .model_api import (BPRMF, DICE, IALSMF, IPSBPRMF, MACRBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dice,
                         check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
@@ -322,6 +323,31 @@ class DatasetApi_Model:
             return ops.recommend_topk_deep(self.Recommender.score_tables()[0], I, users, K, head, pop_t, hist)
         return ops.recommend_topk(self.Recommender.score_tables()[0], I, users, K, head, pop_t, hist)
 
+    def rank_device(self, batch_users, rec_type, tgt_indptr, tgt_indices, pos_pop=None, mask=None):
+        """--rank_report 1: the exact 0-based position of every target entry (a CSR by block row) in its user's masked full-catalogue ranking
+        under the head recommend_device ranks by for this rec_type, and the length of every ranking -> (rank int32 [n_entries], -1 = does
+        not rank; n_ranked int32 [B]).  Reads score_tables(), like the lists (SSM-normalised and LightGCN tables included)."""
+        if self.input_type == "with_temp" or rec_type == "macr":
+            raise NotImplementedError("ranks are taken by the raw and the popularity head (no temp_pop or macr head: --rank_report 0)")
+        if self._shard is not None:
+            raise NotImplementedError("ranks are counted on one GPU (item shards are not wired up)")
+        if rec_type == "main_branch":
+            head, pos_pop = ops.HEAD_RAW, None
+        elif rec_type in ("main_with_pop", "condition"):
+            if rec_type == "condition" and self.input_type != "with_pop":
+                raise NotImplementedError("condition head needs a PD/PDA model")
+            head = ops.HEAD_POP
+            if pos_pop is None:
+                raise ValueError("rec_type %s needs pos_pop" % rec_type)
+        else:
+            raise NotImplementedError("ranks exist for the rec_types main_branch, main_with_pop and condition")
+        users = batch_users if torch.is_tensor(batch_users) else torch.as_tensor(np.asarray(batch_users, dtype=np.int32), device=self.device)
+        pop_t = None
+        if pos_pop is not None:
+            pop_t = pos_pop if torch.is_tensor(pos_pop) else self._pop_on_device(pos_pop)
+        U, I = self.Recommender.score_tables()
+        return ops.rank_targets(U, I, users, tgt_indptr, tgt_indices, head, pop_t, mask)
+
     def testing(self, sess, batch_users, items, model_type, pos_pop=None):
         """Dense scores f32 [B, len(items)] (:642-669): batch_ratings / condition_ratings as the NeuRec evaluators' protocol fetches them (the
         reference imports that protocol and never calls it).  pda_score_dense_f32: every entry is the exact fmaf chain of the top-K kernels, so
@@ -392,6 +418,13 @@ class evaluation:
         self.eval_who = "test"
         self._hist = None
         self.bias = None
+        self.rank = None
+
+    def set_rank_report(self, rank):
+        """--rank_report 1 (pda_amd/rank_report.py): a RankReport makes every eval() rank its blocks' targets in the masked full catalogue
+        (model.rank_device, the history mask of the lists) and return the four metrics as an EvalResult with the pass's rank lines beside
+        them; None (the default) leaves eval() as it is: no kernel call, no allocation."""
+        self.rank = rank
 
     def set_bias_report(self, bias):
         """--bias_report 1 (pda_amd/exposure.py): a BiasReport makes every eval() without an accumulator of its own count its lists and return
@@ -456,6 +489,7 @@ class evaluation:
         pop = None if self.testing_popularity is None else self._pop_dev
         ks = torch.as_tensor(self.Ks, dtype=torch.int32, device=self.device)
         sums = torch.zeros((4, len(self.Ks)), dtype=torch.float64, device=self.device)
+        ranks, lengths = [], []
         for i in range(0, self.tot_user, self.batch_size):
             ub = self.users_dev[i:i + self.batch_size]
             idx, _ = model.recommend_device(ub, None, rec_type, pop, self._hist, eval_pos=i, eval_users=self.users_dev)
@@ -474,11 +508,18 @@ class evaluation:
                     acc.add(idx, tptr, tgt)
                 else:
                     acc.add(idx)
+            if self.rank is not None:
+                r, n = model.rank_device(ub, rec_type, tptr, tgt, pop, self._hist)
+                ranks.append(r)
+                lengths.append(n)
         s = (sums / float(self.tot_user)).cpu().numpy()
         ret = {"precision": s[0], "recall": s[1], "ndcg": s[2], "hit_ratio": s[3]}
         if exposure is None and acc is not None:
             ret = EvalResult(ret)
             ret.bias, ret.bias_lines = self.bias, self.bias.report(acc, self._tgt_host).lines()
+        if self.rank is not None:
+            ret = ret if isinstance(ret, EvalResult) else EvalResult(ret)
+            ret.rank_lines = self.rank.stats(torch.cat(ranks).cpu().numpy(), torch.cat(lengths).cpu().numpy(), self._tp_host, self._tgt_host).lines()
         return ret
 
 
@@ -529,6 +570,8 @@ def _print_result(ret):   # :1118-1123
     if bias is not None:
         for line in bias.header() + ret.bias_lines:
             print(line)
+    for line in getattr(ret, "rank_lines", ()):      # (--rank_report 1)
+        print(line)
 
 
 def main(argv=None):
@@ -537,6 +580,7 @@ def main(argv=None):
     configure(argv)
     check_topk_max(args)                   # (refusals before anything is built)
     bias = BiasReport.from_args(args, data, Ks)
+    rank = RankReport.from_args(args, data)
     if args.model == "lightgcn":
         check_lightgcn(args)
     elif args.model != "mf":
@@ -662,6 +706,7 @@ def main(argv=None):
 
     evaluation_model = evaluation(data, Ks, device)
     evaluation_model.set_bias_report(bias)
+    evaluation_model.set_rank_report(rank)
     if args.valid_set == "test":
         evaluation_model.set_evaluate_obj_pre("test")
         print("valid in test set")

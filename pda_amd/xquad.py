@@ -24,6 +24,7 @@ import torch
 from . import ops
 from .bpr_pc import checkpoint_dir
 from .exposure import BiasReport
+from .rank_report import refuse_rank_report
 from .sampler import host_generator
 
 
@@ -170,6 +171,7 @@ def main(argv=None):
         raise NotImplementedError("Not implement this training method.....")
     K = check_flags(args, t.Ks)
     t.check_topk_max(args)
+    refuse_rank_report(args, "xquad")
     bias = BiasReport.from_args(args, data, t.Ks)
     random.seed(2020)
     np.random.seed(2020)

@@ -5,6 +5,7 @@
     BPRMF              plain BPR-MF        MF/model_api.py:419-757   (only :419-471, :521-536, :695-706 are live)
     DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
     IPSBPRMF           IPS / IPS-C / IPS-CN (no reference code: DESIGN.md 5g)  a BPRMF trained with inverse propensity weights; Adam sweep only
+    PCCBPRMF           BPR + gamma r^2 (no reference code: DESIGN.md 5r)       a BPRMF trained with the popularity-correlation regulariser; Adam sweep only
     SSMBPRMF           SSM                 (no reference code: DESIGN.md 5l)   a BPRMF trained with the sampled-softmax loss; Adam sweep only
     MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
     LightGCN           the LightGCN backbone (no reference code: DESIGN.md 5j)  ego tables propagated over the train graph; ConditionalLightGCN: PD/PDA on it
@@ -718,6 +719,95 @@ class IPSBPRMF(BPRMF):
     def state_dict(self):
         sd = super().state_dict()
         sd.update(ips_clip=self.ips_clip, ips_norm=self.ips_norm)
+        return sd
+
+
+def check_pcc(args):
+    """--train pcc: refuse, before anything is built, what the popularity-correlation step has no kernel for.  Every message names its flag."""
+    if getattr(args, "model", "mf") == "lightgcn":
+        raise NotImplementedError("--model lightgcn: --train pcc trains the tables of a BPRMF only (--model mf)")
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train pcc sums its gradients with float atomics (no planned gradient; the batch statistic "
+                                  "alone is bit-reproducible)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train pcc runs fp32 tables only" % args.table_dtype)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train pcc runs the reference's dense-decay Adam only (--optimizer adam)" % args.optimizer)
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("--adam_sweep %s: --train pcc runs the dense Adam sweep only (auto | sweep)" % getattr(args, "adam_sweep", "auto"))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train pcc trains on one GPU (the statistic is the whole batch's)" % args.gpus)
+    gamma = getattr(args, "pcc_gamma", 1.0)
+    if not (float(gamma) >= 0.0 and math.isfinite(float(gamma))):
+        raise ValueError("--pcc_gamma must be a finite number >= 0, got %s" % (gamma,))
+    if getattr(args, "pcc_on", "pos") not in ops.PCC_ON:
+        raise ValueError("--pcc_on must be pos or margin, got %s" % (args.pcc_on,))
+    if getattr(args, "pcc_pop", "count") not in ops.PCC_POP_MODES:
+        raise ValueError("--pcc_pop must be count or log, got %s" % (args.pcc_pop,))
+
+
+class PCCBPRMF(BPRMF):
+    """BPR-MF trained with the popularity-correlation regulariser: the BPR loss plus --pcc_gamma times the squared Pearson
+    correlation, over the batch, between a score (--pcc_on pos: of the observed pair; margin: the pairwise margin) and the popularity of the
+    positive (--pcc_pop count | log).  Fetchables, tables, evaluation and checkpoint are those of BPRMF -- the two differ only in how they were
+    trained; a step is pda_pcc_adam_step_f32.  data_config["ips_item_counts"] (or set_item_counts): the train interactions per item the
+    popularities are built from; a model that is only restored and evaluated needs none."""
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_pcc(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.pcc_gamma = float(getattr(args, "pcc_gamma", 1.0))
+        self.pcc_on = getattr(args, "pcc_on", "pos")
+        self.pcc_pop = getattr(args, "pcc_pop", "count")
+        self.pcc = None
+        self._pcc_ws = None
+        self.pcc_acc = torch.zeros(2, dtype=torch.float32, device=self.device)     # += (r, r^2) of every step; take_pcc reads and clears it
+        self._pcc_steps = 0
+        if data_config.get("ips_item_counts") is not None:
+            self.set_item_counts(data_config["ips_item_counts"])
+
+    def set_item_counts(self, counts):
+        if len(counts) != self.n_items:
+            raise ValueError("ips_item_counts holds one number per item (%d), got %d" % (self.n_items, len(counts)))
+        self.pcc = ops.PccPop.from_counts(counts, self.pcc_pop, self.device)
+
+    def train_step(self, users, pos, neg, pos_pop=None, neg_pop=None, plan=None) -> torch.Tensor:
+        """One PCC step; returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this step, as BPRMF.train_step does."""
+        if self.pcc is None:
+            raise ValueError("PCCBPRMF needs the train interactions per item before it trains (data_config['ips_item_counts'] or set_item_counts)")
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._opt_state()
+        if "tagU" not in st:
+            st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
+        if self._pcc_ws is None or self._pcc_ws[0].numel() < users.numel():
+            self._pcc_ws = ops.pcc_workspace(users.numel(), self.device)
+        self._t += 1
+        ops.pcc_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, neg, self.pcc.pop,
+                          self._pcc_ws[0], self._pcc_ws[1], gamma=self.pcc_gamma, on=self.pcc_on, regs=self.decay, reg_div=self.batch_size,
+                          step=self._t, lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)),
+                          loss_acc=self._loss, pcc_acc=self.pcc_acc)
+        self._pcc_steps += 1
+        return self._loss
+
+    def take_pcc(self):
+        """(mean r, mean r^2) over the steps since the last call (one host read), and a fresh count."""
+        r, r2 = (self.pcc_acc.double() / max(self._pcc_steps, 1)).tolist()
+        self.pcc_acc.zero_()
+        self._pcc_steps = 0
+        return r, r2
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd.update(pcc_gamma=self.pcc_gamma, pcc_on=self.pcc_on, pcc_pop=self.pcc_pop)
         return sd
 
 

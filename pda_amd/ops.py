@@ -2439,6 +2439,123 @@ def ips_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, neg, ipw
     mark_modified(U, I)
 
 
+# ---- the popularity-correlation regulariser (include/pda_hip_pcc.h) -------------------------------------------------------------------------
+PCC_EMBED_SIZES = (32, 64, 128, 256)
+PCC_ON = {"pos": _lib.PCC_ON_POS, "margin": _lib.PCC_ON_MARGIN}
+PCC_POP_MODES = ("count", "log")
+
+
+class PccPop:
+    """The popularity of every item, built once per data set on the host from n_i, the train interactions of item i: mode "count": (float)n_i;
+    "log": log1p(n_i) in float64, then cast.  pop float32 [n_items] on `device`.  (Pearson's r is invariant to positive affine maps, so counts,
+    shares and propensities give the same model.)"""
+
+    @classmethod
+    def from_counts(cls, counts, mode: str = "count", device="cpu"):
+        import numpy as np
+        counts = np.asarray(counts)
+        if counts.ndim != 1 or counts.size == 0 or (counts < 0).any():
+            raise ValueError("counts: one non-negative number of train interactions per item")
+        if mode not in PCC_POP_MODES:
+            raise ValueError("--pcc_pop must be one of %s, got %r" % (" | ".join(PCC_POP_MODES), mode))
+        counts = counts.astype(np.int64)
+        pop = counts.astype(np.float32) if mode == "count" else np.log1p(counts.astype(np.float64)).astype(np.float32)
+        self = cls.__new__(cls)
+        self.n_items, self.mode, self.counts = int(counts.size), mode, counts
+        self.pop = torch.from_numpy(pop).to(device)
+        return self
+
+
+def pcc_workspace(B: int, device):
+    """(z_ws float32 [B], stat float64 [8]): the workspace of one batch size, private to one stream."""
+    return torch.zeros(int(B), dtype=torch.float32, device=device), torch.zeros(_lib.PCC_STAT_WORDS, dtype=torch.float64, device=device)
+
+
+def _pcc_on(on: str) -> int:
+    if on not in PCC_ON:
+        raise ValueError("--pcc_on must be one of pos | margin, got %r" % (on,))
+    return PCC_ON[on]
+
+
+def _pcc_check(U, I, users, pos, neg, pop, z_ws, stat, check_ids: bool):
+    d, B = _triplet_shapes("PCC", "U [n_users, d] and I [n_items, d]", PCC_EMBED_SIZES, U, I, users, pos, neg)
+    if _need(pop, torch.float32, "pop").numel() != I.shape[0]:
+        raise ValueError("pop holds one float32 per item")
+    if _need(z_ws, torch.float32, "z_ws").numel() < B:
+        raise ValueError("z_ws holds one float32 per triplet")
+    if _need(stat, torch.float64, "stat").numel() < _lib.PCC_STAT_WORDS:
+        raise ValueError("stat holds eight float64")
+    _triplet_ids("PCC", U, I, users, pos, neg, check_ids)
+    return d, B
+
+
+def _pcc_step_check(U, I, tagU, tagI, gamma, loss_acc, pcc_acc):
+    if not float(gamma) >= 0.0:
+        raise ValueError("--pcc_gamma must be >= 0, got %s" % (gamma,))
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("PCC loss_acc holds three float32")
+    if _need(pcc_acc, torch.float32, "pcc_acc", optional=True) is not None and pcc_acc.numel() < 2:
+        raise ValueError("pcc_acc holds two float32")
+
+
+def pcc_stats(U, I, users, pos, neg, pop, *, on: str = "pos", z_ws: Optional[torch.Tensor] = None, stat: Optional[torch.Tensor] = None,
+              check_ids: bool = True):
+    """pda_pcc_stats_f32 -> (z_ws float32 [B], stat float64 [8]) on the device: z_t of every triplet (0 for a refused one) and the batch's
+    statistic (n_v, zbar, qbar, Szz, Sqq, Szq, r, 0): centred float64 moments in a fixed order, the same bits run after run."""
+    if z_ws is None or stat is None:
+        ws = pcc_workspace(_need(users, torch.int32, "users").numel(), users.device)
+        z_ws, stat = (ws[0] if z_ws is None else z_ws), (ws[1] if stat is None else stat)
+    d, B = _pcc_check(U, I, users, pos, neg, pop, z_ws, stat, check_ids)
+    check(_lib.load().pda_pcc_stats_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(pop), B, d, _pcc_on(on),
+                                        ptr(z_ws), ptr(stat), stream_ptr()), "pda_pcc_stats_f32")
+    return z_ws, stat
+
+
+def pcc_grads(U, I, users, pos, neg, pop, gU, gI, tagU, tagI, *, gamma: float, on: str = "pos", regs: float, reg_div: float, step: int,
+              grouped: bool = False, users_distinct: bool = False, z_ws: Optional[torch.Tensor] = None, stat: Optional[torch.Tensor] = None,
+              loss_acc: Optional[torch.Tensor] = None, pcc_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_pcc_stats_f32 + pda_pcc_step_f32: the batch's gradient summed into gU / gI (rows tagged `step`), no update.  loss_acc float32 [3] +=
+    (loss, mf_loss, reg_loss), pcc_acc float32 [2] += (r, r^2).  Returns (z_ws, stat) as pcc_stats does."""
+    if z_ws is None or stat is None:
+        ws = pcc_workspace(_need(users, torch.int32, "users").numel(), users.device)
+        z_ws, stat = (ws[0] if z_ws is None else z_ws), (ws[1] if stat is None else stat)
+    d, B = _pcc_check(U, I, users, pos, neg, pop, z_ws, stat, check_ids)
+    _pcc_step_check(U, I, tagU, tagI, gamma, loss_acc, pcc_acc)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    lib, code = _lib.load(), _pcc_on(on)
+    check(lib.pda_pcc_stats_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(pop), B, d, code, ptr(z_ws), ptr(stat),
+                                stream_ptr()), "pda_pcc_stats_f32")
+    check(lib.pda_pcc_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(pop), ptr(z_ws), ptr(stat), B, d,
+                               float(gamma), code, float(regs), float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step),
+                               _ips_flags(grouped, users_distinct), ptr(loss_acc), ptr(pcc_acc), stream_ptr()), "pda_pcc_step_f32")
+    return z_ws, stat
+
+
+def pcc_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, neg, pop, z_ws, stat, *, gamma: float, on: str = "pos", regs: float,
+                  reg_div: float, step: int, lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False,
+                  users_distinct: bool = False, cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None,
+                  pcc_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_pcc_adam_step_f32: one PCC train step (the scores, their moments, the gradients, TF-1.14 dense-decay Adam over both tables) in four
+    launches; graph-capturable.  The arguments of adam_step with pop float32 [n_items] in place of the popularities and the workspace
+    (z_ws, stat) of pcc_workspace."""
+    d, B = _pcc_check(U, I, users, pos, neg, pop, z_ws, stat, check_ids)
+    _pcc_step_check(U, I, tagU, tagI, gamma, loss_acc, pcc_acc)
+    for t in (mU, vU, gU, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_pcc_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI),
+                                            I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(pop), ptr(z_ws), ptr(stat), B, d, float(gamma),
+                                            _pcc_on(on), float(regs), float(reg_div), int(step), float(lr_t), beta1, beta2, eps,
+                                            _ips_flags(grouped, users_distinct), int(cache_policy), ptr(loss_acc), ptr(pcc_acc), stream_ptr()),
+          "pda_pcc_adam_step_f32")
+    mark_modified(U, I)
+
+
 # ---- MACR (include/pda_hip_macr.h) ----------------------------------------------------------------------------------------------------------
 MACR_EMBED_SIZES = (32, 64, 128, 256)         # the step and the item prep
 MACR_EVAL_EMBED_SIZES = (64, 128, 256)        # the lists: the bias head of include/pda_hip_temp_pop.h

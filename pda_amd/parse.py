@@ -13,8 +13,8 @@ _REFERENCE_FLAGS = [
     ("data_path", None, "./data/", "root directory that holds <dataset>/"),
     ("dataset", None, "kwai", "dataset directory name"),
     ("source", None, "normal", "(unused)"),
-    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm) | ials (implicit ALS, --ials_alpha0 / --ials_nu; no sampler, no optimiser)"),
-    ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the raw head of an SSM model alone) | ials (the raw head of an iALS model alone)"),
+    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm) | ials (implicit ALS, --ials_alpha0 / --ials_nu; no sampler, no optimiser) | pcc (BPR plus the popularity-correlation regulariser, --pcc_gamma / --pcc_on / --pcc_pop)"),
+    ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the raw head of an SSM model alone) | ials (the raw head of an iALS model alone) | pcc (the raw head of a PCC model alone)"),
     ("valid_set", None, "test", "test | valid"),
     ("save_dir", None, "/data/zyang/save_model/", "checkpoint root"),
     ("alpha", float, 1e-3, "MACR (--train macr): weight of the item-branch loss L_I; otherwise unused (appears in the checkpoint directory name)"),
@@ -87,6 +87,9 @@ _EXTENSION_FLAGS = [
     ("gcn_layers", int, 3, "LightGCN (--model lightgcn): propagation layers L, 0 .. 4; the final tables are the mean of the L + 1 layers (0: the ego tables alone, matrix factorisation through this path)"),
     ("ials_alpha0", float, 0.1, "iALS (--train ials, include/pda_hip_ials.h): weight alpha0 of the unobserved pairs, >= 0.  --regs is lambda (> 0); --lr, --optimizer, --adam_sweep, --sampler and --batch_size (for training) are unused by iALS"),
     ("ials_nu", float, 1.0, "iALS: frequency scaling of the regulariser, lambda (n + alpha0 n_other)^nu per row, 0 .. 1 (0: plain L2)"),
+    ("pcc_gamma", float, 1.0, "PCC (--train pcc, include/pda_hip_pcc.h): weight gamma of the penalty gamma r^2, r the Pearson correlation over the batch between a score and the popularity of the positive, >= 0 (0: the BPR loss, r is still reported).  The default is UNTUNED: nothing here has the data sets"),
+    ("pcc_on", str, "pos", "PCC: the score that is correlated with the positive's popularity.  pos = the score of the observed pair (Zhu et al., WSDM'21) | margin = the pairwise margin, positive score minus negative score"),
+    ("pcc_pop", str, "count", "PCC: the popularity of an item.  count = its train interactions n_i | log = log1p(n_i)"),
     ("neg_sampler", str, "uniform", "where a triplet's negative comes from: uniform = one uniform draw outside the user's train items (the reference) | dns = dynamic hard-negative sampling, DNS(M, N): one of the --dns_topn best-scoring of --dns_candidates uniform draws under the current tables (include/pda_hip_dns.h; --train normal | s_condition, fp32 tables, the device sampler, one GPU)"),
     ("dns_candidates", int, 16, "DNS (--neg_sampler dns): candidates M drawn and scored per triplet, 1 .. 256 (1: the uniform sampler's batches, bit for bit)"),
     ("dns_topn", int, 1, "DNS: the negative is drawn uniformly from the N best of the M candidates, 1 .. --dns_candidates (1: the best one, the classic DNS)"),

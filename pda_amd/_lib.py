@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h and pda_hip_pcc.h).
+pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h and pda_hip_dau.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -308,6 +308,20 @@ PCC_SIGNATURES = {
                                    _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_dau.h (the DirectAU loss: `--train dau`)
+DAU_MAX_B = 16384
+DAU_MAX_T = 20.0
+DAU_TILE = 32
+DAU_SAME_KEEP, DAU_SAME_DROP = 0, 1
+DAU_STAT_WORDS = 4
+DAU_SIGNATURES = {
+    "pda_dau_col_splits": (_i, [_i]),
+    "pda_dau_workspace_bytes": (_sz, [_i, _i]),
+    "pda_dau_step_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _i, _i, _f, _f, _i, _f, _f] + [_vp] * 4 + [_i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "pda_dau_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp, _vp, _i, _i, _f, _f, _i, _f, _f, _i, _f, _f, _f, _f, _i, _i, _vp, _sz,
+                                   _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -329,7 +343,8 @@ def load():
             list(DET_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + list(XQUAD_SIGNATURES.items()) + list(DICE_SIGNATURES.items()) + \
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
             list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()) + \
-            list(FULLSM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PCC_SIGNATURES.items()):
+            list(FULLSM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PCC_SIGNATURES.items()) + \
+            list(DAU_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,6 +1,6 @@
 """python -m pda_amd.export_topk <flags of the training run> --topk_max N --export_out FILE.npz
 
-Restores the best_ckpt.ckpt of a `--train normal`, `--train dice`, `--train ips`, `--train ssm`, `--train pcc` or `--train s_condition` run of pda_amd.train_new_api (same flags, as pda_amd.bpr_pc does)
+Restores the best_ckpt.ckpt of a `--train normal`, `--train dice`, `--train ips`, `--train ssm`, `--train pcc`, `--train dau` or `--train s_condition` run of pda_amd.train_new_api (same flags, as pda_amd.bpr_pc does)
 and writes the ranked list of every evaluation user of --valid_set, N items deep (1 .. 1 024; above 54 through the deep path,
 include/pda_hip_deep.h):
 
@@ -8,7 +8,7 @@ include/pda_hip_deep.h):
     idx    int32   [n, N]    item ids, best first (train items masked)
     val    float32 [n, N]    the values they were ranked by
 
-`normal`, `dice`, `ips`, `pcc` and `ssm` rank by the main_branch head (`ssm` with --ssm_norm 1: on the row-normalised tables); `s_condition` by the condition head with the last-stage popularity (PDA).  For candidate generation
+`normal`, `dice`, `ips`, `pcc`, `dau` and `ssm` rank by the main_branch head (`ssm` with --ssm_norm 1 and `dau` with --dau_rank cosine: on the row-normalised tables); `s_condition` by the condition head with the last-stage popularity (PDA).  For candidate generation
 ahead of a re-ranker, and for offline analysis of popularity bias.
 """
 from __future__ import annotations
@@ -37,8 +37,8 @@ def restore(argv=None):
     random.seed(2020)
     np.random.seed(2020)
     torch.manual_seed(2021)
-    if args.model != "mf" or args.train not in ("normal", "s_condition", "dice", "ips", "ssm", "ials", "pcc"):
-        raise NotImplementedError("export_topk restores a --train normal, --train dice, --train ips, --train ssm, --train ials, --train pcc or --train s_condition run, not %r" % (args.train,))
+    if args.model != "mf" or args.train not in ("normal", "s_condition", "dice", "ips", "ssm", "ials", "pcc", "dau"):
+        raise NotImplementedError("export_topk restores a --train normal, --train dice, --train ips, --train ssm, --train ials, --train pcc, --train dau or --train s_condition run, not %r" % (args.train,))
     if torch.cuda.device_count() > 1 and str(args.cuda).isdigit() and int(args.cuda) < torch.cuda.device_count():
         torch.cuda.set_device(int(args.cuda))
     device = torch.device("cuda")
@@ -50,7 +50,7 @@ def restore(argv=None):
         data.add_expo_popularity(np.power(get_popularity_from_load(pop_item_all), args.pop_exp))
         rec_type, popularity = "condition", np.power(pop_item_all[:, -2], args.pop_exp)
     else:
-        args.saveID += "pop_exp-{:.2f}".format(args.pop_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc"}.get(args.train, "")
+        args.saveID += "pop_exp-{:.2f}".format(args.pop_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau"}.get(args.train, "")
         rec_type, popularity = "main_branch", None
     args.wd = args.regs
     path = checkpoint_dir(args) + "best_ckpt.ckpt"

@@ -6,6 +6,7 @@
     DICE               DICE / DICE-A       (no reference code: DESIGN.md 5f)   interest + conformity embeddings in one 2d-wide row; Adam sweep only
     IPSBPRMF           IPS / IPS-C / IPS-CN (no reference code: DESIGN.md 5g)  a BPRMF trained with inverse propensity weights; Adam sweep only
     PCCBPRMF           BPR + gamma r^2 (no reference code: DESIGN.md 5r)       a BPRMF trained with the popularity-correlation regulariser; Adam sweep only
+    DAUMF              DirectAU            (no reference code: DESIGN.md 5s)   a BPRMF trained with the alignment + uniformity loss, no negatives; Adam sweep only
     SSMBPRMF           SSM                 (no reference code: DESIGN.md 5l)   a BPRMF trained with the sampled-softmax loss; Adam sweep only
     MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
     LightGCN           the LightGCN backbone (no reference code: DESIGN.md 5j)  ego tables propagated over the train graph; ConditionalLightGCN: PD/PDA on it
@@ -987,6 +988,112 @@ class SSMBPRMF(BPRMF):
             sd.update(ssm_source=self.ssm_source, ssm_logq=self.ssm_logq, ssm_mask_train=self.ssm_mask_train)
         elif self.ssm_source == "all":      # (no logQ on the exact softmax)
             sd.update(ssm_source=self.ssm_source, ssm_mask_train=self.ssm_mask_train)
+        return sd
+
+
+DAU_RANKS = ("raw", "cosine")
+
+
+def check_dau(args):
+    """--train dau: refuse, before anything is built, what the DirectAU step has no kernel for.  Every message names its flag."""
+    if getattr(args, "model", "mf") == "lightgcn":
+        raise NotImplementedError("--model lightgcn: --train dau trains the tables of a BPRMF only (--model mf)")
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train dau scatters the gradients of repeated ids with float atomics (no planned gradient; "
+                                  "the loss terms alone are bit-reproducible)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train dau runs fp32 tables only" % args.table_dtype)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train dau runs the reference's dense-decay Adam only (--optimizer adam)" % args.optimizer)
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep") or getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("--adam_sweep %s: --train dau runs the dense Adam sweep only (auto | sweep)" % getattr(args, "adam_sweep", "auto"))
+    if getattr(args, "sampler", "device") != "device":
+        raise NotImplementedError("--sampler %s: --train dau draws its batches with the device sampler only (--sampler device)" % args.sampler)
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train dau trains on one GPU (the uniformity terms are the whole batch's)" % args.gpus)
+    if getattr(args, "neg_sampler", "uniform") != "uniform":
+        raise NotImplementedError("--neg_sampler %s: --train dau uses no negatives (--neg_sampler uniform; the triplet sampler's negative is "
+                                  "ignored)" % args.neg_sampler)
+    gamma = getattr(args, "dau_gamma", 1.0)
+    if not (float(gamma) >= 0.0 and math.isfinite(float(gamma))):
+        raise ValueError("--dau_gamma must be a finite number >= 0, got %s" % (gamma,))
+    t = float(getattr(args, "dau_t", 2.0))
+    if not 0.0 < t <= ops.DAU_MAX_T:
+        raise ValueError("--dau_t must lie in (0, %g], got %s" % (ops.DAU_MAX_T, getattr(args, "dau_t", 2.0)))
+    if getattr(args, "dau_same", "keep") not in ops.DAU_SAME:
+        raise ValueError("--dau_same must be keep or drop, got %s" % (args.dau_same,))
+    if getattr(args, "dau_rank", "raw") not in DAU_RANKS:
+        raise ValueError("--dau_rank must be raw or cosine, got %s" % (args.dau_rank,))
+    B = getattr(args, "batch_size", 2048)
+    if int(B) != B or not 2 <= int(B) <= ops.DAU_MAX_B:
+        raise ValueError("--batch_size must be an integer in 2 .. %d with --train dau (uniformity is over pairs of rows), got %s" % (ops.DAU_MAX_B, B))
+
+
+class DAUMF(BPRMF):
+    """BPR-MF tables trained with the DirectAU loss (include/pda_hip_dau.h): alignment of a user with its positive plus --dau_gamma
+    times the mean uniformity of the batch's user rows and item rows on the unit sphere (temperature --dau_t; --dau_same keep | drop: whether
+    pairs of rows with the same id count).  No negatives: the triplet sampler's negative is ignored.  Fetchables, tables, evaluation and
+    checkpoint are those of BPRMF; a step is pda_dau_adam_step_f32.  score_tables() -- what every ranking reads -- returns the raw tables for
+    --dau_rank raw and the row-normalised tables for --dau_rank cosine (the path --ssm_norm 1 takes); weights[...] and the checkpoint always hold
+    the RAW tables."""
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_dau(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.dau_gamma = float(getattr(args, "dau_gamma", 1.0))
+        self.dau_t = float(getattr(args, "dau_t", 2.0))
+        self.dau_same = str(getattr(args, "dau_same", "keep"))
+        self.dau_rank = str(getattr(args, "dau_rank", "raw"))
+        self._normed = None                  # ((U^, I^), (version of U, version of I) they were computed from)
+        self._dau_ws = None                  # (B, workspace), allocated once
+        self.dau_stat = torch.zeros(ops.DAU_STAT_WORDS, dtype=torch.float32, device=self.device)   # += (align, uni_U, uni_I, 1) of every step
+
+    def score_tables(self):
+        """--dau_rank cosine: the row-normalised tables of the current weights, recomputed when a step (or a restore) has moved them."""
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        if self.dau_rank != "cosine":
+            return U, I
+        ver = (U._version, I._version)
+        if self._normed is None or self._normed[1] != ver:
+            self._normed = ((ops.ssm_normalize_rows(U), ops.ssm_normalize_rows(I)), ver)
+        return self._normed[0]
+
+    def train_step(self, users, pos, neg=None, pos_pop=None, neg_pop=None, plan=None) -> torch.Tensor:
+        """One DirectAU step on (users [B], pos [B]); returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this step, as
+        BPRMF.train_step does.  Nothing is read on the host.  neg is ignored (the triplet sampler's negative)."""
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._opt_state()
+        if "tagU" not in st:
+            st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
+        B = users.numel()
+        if self._dau_ws is None or self._dau_ws[0] != B:
+            self._dau_ws = (B, ops.dau_workspace(B, U.shape[1], U.device))
+        self._t += 1
+        ops.dau_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, self._dau_ws[1],
+                          t=self.dau_t, gamma=self.dau_gamma, same=self.dau_same, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                          lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)),
+                          stat=self.dau_stat, loss_acc=self._loss)
+        return self._loss
+
+    def take_dau(self):
+        """(mean align, mean uni_U, mean uni_I) over the steps since the last call (one host read), and a fresh count."""
+        al, uu, ui, n = self.dau_stat.double().tolist()
+        self.dau_stat.zero_()
+        n = max(n, 1.0)
+        return al / n, uu / n, ui / n
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd.update(dau_gamma=self.dau_gamma, dau_t=self.dau_t, dau_same=self.dau_same, dau_rank=self.dau_rank)
         return sd
 
 

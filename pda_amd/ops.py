@@ -3124,6 +3124,95 @@ def inbatch_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, ws, 
     mark_modified(U, I)
 
 
+# ---- the DirectAU loss (include/pda_hip_dau.h) ---------------------------------------------------------------------------------------------------------
+DAU_MAX_B = _lib.DAU_MAX_B
+DAU_MAX_T = _lib.DAU_MAX_T
+DAU_TILE = _lib.DAU_TILE
+DAU_EMBED_SIZES = (32, 64, 128, 256)
+DAU_SAME = {"keep": _lib.DAU_SAME_KEEP, "drop": _lib.DAU_SAME_DROP}
+DAU_STAT_WORDS = _lib.DAU_STAT_WORDS
+
+
+def dau_col_splits(B: int) -> int:
+    """pda_dau_col_splits: the column ranges the pass over the Gram tiles splits a batch of B into."""
+    if not 1 <= int(B) <= DAU_MAX_B:
+        raise ValueError(f"DirectAU: the batch size must lie in 1 .. {DAU_MAX_B}, got {B}")
+    return int(_lib.load().pda_dau_col_splits(int(B)))
+
+
+def dau_workspace(B: int, d: int, device) -> torch.Tensor:
+    """The workspace of one batch size and width (pda_dau_workspace_bytes): uint8, private to one stream."""
+    if not 1 <= int(B) <= DAU_MAX_B:
+        raise ValueError(f"DirectAU: the batch size must lie in 1 .. {DAU_MAX_B}, got {B}")
+    if d not in DAU_EMBED_SIZES:
+        raise ValueError(f"DirectAU: the embedding width d must be one of {DAU_EMBED_SIZES}, got {d}")
+    return torch.empty(int(_lib.load().pda_dau_workspace_bytes(int(B), int(d))), dtype=torch.uint8, device=device)
+
+
+def _dau_params(t, gamma, same):
+    t, gamma = float(t), float(gamma)
+    if not 0.0 < t <= DAU_MAX_T:
+        raise ValueError(f"DirectAU: t must lie in (0, {DAU_MAX_T:g}], got {t}")
+    if not (gamma >= 0.0 and math.isfinite(gamma)):
+        raise ValueError(f"DirectAU: gamma must be a finite number >= 0, got {gamma}")
+    if same not in DAU_SAME:
+        raise ValueError(f"DirectAU: same must be one of {sorted(DAU_SAME)}, got {same!r}")
+    return t, gamma, DAU_SAME[same]
+
+
+def _dau_check(U, I, users, pos, tagU, tagI, ws, stat, loss_acc, check_ids: bool):
+    """The tables and (users, pos) as every tagged step checks them, the workspace, the optional stat float32 [4] and loss_acc float32 [3]
+    -> (d, B)."""
+    d, B = _triplet_shapes("DirectAU", "U [n_users, d] and I [n_items, d]", DAU_EMBED_SIZES, U, I, users, pos, pos)
+    if B > DAU_MAX_B:
+        raise ValueError(f"DirectAU: the batch size must lie in 1 .. {DAU_MAX_B}, got {B}")
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(ws, torch.uint8, "ws").numel() < int(_lib.load().pda_dau_workspace_bytes(B, d)):
+        raise ValueError("ws: the workspace of dau_workspace(B, d)")
+    if _need(stat, torch.float32, "stat", optional=True) is not None and stat.numel() < DAU_STAT_WORDS:
+        raise ValueError(f"DirectAU stat holds {DAU_STAT_WORDS} float32")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("DirectAU loss_acc holds three float32")
+    _triplet_ids("DirectAU", U, I, users, pos, pos, check_ids)
+    return d, B
+
+
+def dau_step(U, I, users, pos, gU, gI, tagU, tagI, ws, *, t: float, gamma: float, same: str = "keep", regs: float, reg_div: float, step: int,
+             grouped: bool = False, users_distinct: bool = False, stat: Optional[torch.Tensor] = None, loss_acc: Optional[torch.Tensor] = None,
+             check_ids: bool = True):
+    """pda_dau_step_f32: the batch's DirectAU gradient summed into gU / gI (rows tagged `step`), no update.
+    loss_acc float32 [3] += (loss, mf_loss, reg_loss); stat float32 [4] += (align, uni_U, uni_I, 1)."""
+    d, B = _dau_check(U, I, users, pos, tagU, tagI, ws, stat, loss_acc, check_ids)
+    t, gamma, same = _dau_params(t, gamma, same)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    check(_lib.load().pda_dau_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), B, d, t, gamma, same, float(regs),
+                                       float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step), _ips_flags(grouped, users_distinct),
+                                       ptr(ws), ws.numel(), ptr(stat), ptr(loss_acc), stream_ptr()), "pda_dau_step_f32")
+    mark_modified(gU, gI)
+
+
+def dau_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, ws, *, t: float, gamma: float, same: str = "keep", regs: float,
+                  reg_div: float, step: int, lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False,
+                  users_distinct: bool = False, cache_policy: int = ADAM_CACHE_AUTO, stat: Optional[torch.Tensor] = None,
+                  loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_dau_adam_step_f32: one DirectAU train step (the gradients, TF-1.14 dense-decay Adam over both tables) in five launches;
+    graph-capturable.  The arguments of inbatch_adam_step with (t, gamma, same) in place of (tau, norm, logq, mask), and the optional stat."""
+    d, B = _dau_check(U, I, users, pos, tagU, tagI, ws, stat, loss_acc, check_ids)
+    t, gamma, same = _dau_params(t, gamma, same)
+    for x in (mU, vU, gU, mI, vI, gI):
+        _need(x, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_dau_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI),
+                                            ptr(tagI), I.shape[0], ptr(users), ptr(pos), B, d, t, gamma, same, float(regs), float(reg_div),
+                                            int(step), float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy),
+                                            ptr(ws), ws.numel(), ptr(stat), ptr(loss_acc), stream_ptr()), "pda_dau_adam_step_f32")
+    mark_modified(U, I)
+
+
 # ---- the full-catalogue softmax (include/pda_hip_fullsm.h) -----------------------------------------------------------------------------------------
 FULLSM_MAX_B = _lib.FULLSM_MAX_B
 FULLSM_ROW_TILE = _lib.FULLSM_ROW_TILE

@@ -13,8 +13,8 @@ _REFERENCE_FLAGS = [
     ("data_path", None, "./data/", "root directory that holds <dataset>/"),
     ("dataset", None, "kwai", "dataset directory name"),
     ("source", None, "normal", "(unused)"),
-    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm) | ials (implicit ALS, --ials_alpha0 / --ials_nu; no sampler, no optimiser) | pcc (BPR plus the popularity-correlation regulariser, --pcc_gamma / --pcc_on / --pcc_pop)"),
-    ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the raw head of an SSM model alone) | ials (the raw head of an iALS model alone) | pcc (the raw head of a PCC model alone)"),
+    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm) | ials (implicit ALS, --ials_alpha0 / --ials_nu; no sampler, no optimiser) | pcc (BPR plus the popularity-correlation regulariser, --pcc_gamma / --pcc_on / --pcc_pop) | dau (the DirectAU alignment + uniformity loss, --dau_gamma / --dau_t / --dau_same / --dau_rank; no negatives)"),
+    ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the raw head of an SSM model alone) | ials (the raw head of an iALS model alone) | pcc (the raw head of a PCC model alone) | dau (the main head of a DirectAU model alone)"),
     ("valid_set", None, "test", "test | valid"),
     ("save_dir", None, "/data/zyang/save_model/", "checkpoint root"),
     ("alpha", float, 1e-3, "MACR (--train macr): weight of the item-branch loss L_I; otherwise unused (appears in the checkpoint directory name)"),
@@ -90,6 +90,10 @@ _EXTENSION_FLAGS = [
     ("pcc_gamma", float, 1.0, "PCC (--train pcc, include/pda_hip_pcc.h): weight gamma of the penalty gamma r^2, r the Pearson correlation over the batch between a score and the popularity of the positive, >= 0 (0: the BPR loss, r is still reported).  The default is UNTUNED: nothing here has the data sets"),
     ("pcc_on", str, "pos", "PCC: the score that is correlated with the positive's popularity.  pos = the score of the observed pair (Zhu et al., WSDM'21) | margin = the pairwise margin, positive score minus negative score"),
     ("pcc_pop", str, "count", "PCC: the popularity of an item.  count = its train interactions n_i | log = log1p(n_i)"),
+    ("dau_gamma", float, 1.0, "DirectAU (--train dau, include/pda_hip_dau.h): weight gamma of the uniformity term gamma (uni_U + uni_I) / 2 beside the alignment term, >= 0 (0: alignment alone).  The default is UNTUNED: nothing here has the data sets"),
+    ("dau_t", float, 2.0, "DirectAU: temperature t of the uniformity kernel exp(-t |x - y|^2) on the unit sphere, 0 < t <= 20"),
+    ("dau_same", str, "keep", "DirectAU: pairs of batch rows that carry the same user (or the same item).  keep = they count, at distance 0 (a pairwise distance over the batch as it stands) | drop = they are left out of the uniformity mean"),
+    ("dau_rank", str, "raw", "DirectAU: what the lists rank by.  raw = the dot product of the raw tables | cosine = of the row-normalised tables (the quantity the loss trained; the path --ssm_norm 1 takes)"),
     ("neg_sampler", str, "uniform", "where a triplet's negative comes from: uniform = one uniform draw outside the user's train items (the reference) | dns = dynamic hard-negative sampling, DNS(M, N): one of the --dns_topn best-scoring of --dns_candidates uniform draws under the current tables (include/pda_hip_dns.h; --train normal | s_condition, fp32 tables, the device sampler, one GPU)"),
     ("dns_candidates", int, 16, "DNS (--neg_sampler dns): candidates M drawn and scored per triplet, 1 .. 256 (1: the uniform sampler's batches, bit for bit)"),
     ("dns_topn", int, 1, "DNS: the negative is drawn uniformly from the N best of the M candidates, 1 .. --dns_candidates (1: the best one, the classic DNS)"),

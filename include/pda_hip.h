@@ -122,6 +122,8 @@ int pda_score_topk_f32(const float* U, const float* I_shard, const float* pop_sh
  * has no such requirement. */
 size_t pda_item_prep_bytes(int n_items_local, int d);
 int pda_item_prep_f32(const float* I_shard, int n_items_local, int d, void* prep, void* stream);
+/* Buffer contract -- workspace (pda_score_topk_workspace_bytes): needs no initialisation -- the call clears all of it itself, stream-ordered; afterwards
+ * a caller may read +4 (pairs rescored), +8 (tiles scored, 64-bit) and +16 (kernel identity); one workspace serves one call at a time. */
 size_t pda_score_topk_workspace_bytes(int n_users_blk);
 int pda_score_topk_prepped_f32(const float* U, const float* I_shard, const void* prep, const float* pop_shard,
                                const int32_t* users, int n_users_blk, int item_offset, int n_items_local, int d,
@@ -247,6 +249,10 @@ int pda_item_prep4_bf16(const uint16_t* I_shard, const float* pop_shard, const i
                         void* stream);
 int pda_item_prep4_check(const void* prep, int n_items_local, int d, void* stream);
 int pda_score_topk4_auto_splits(int n_users_blk, int n_items_local, int d);
+/* Buffer contract -- workspace (pda_score_topk4_workspace_bytes): needs no initialisation -- every call that starts a ranking (pda_score_topk4_*, phase
+ * 1 and phase 4 of pda_score_topk4_phase_*) clears the counters and the shared-tail records behind them itself, stream-ordered, and writes every other
+ * region before it reads it; phase 2 continues on the workspace phase 1 left and must be given the same one; afterwards a caller may read +0 (error
+ * word), +4, +8, +16 (kernel identity), +20 .. +44 (counters); one workspace serves one call (one phase-1 / phase-2 pair) at a time. */
 size_t pda_score_topk4_workspace_bytes(int n_users_blk, int n_items_local, int d, int n_splits);
 int pda_score_topk4_f32(const float* U, const float* I_shard, const void* prep, const float* pop_shard, const int32_t* users,
                         int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr,
@@ -314,6 +320,9 @@ int pda_score_topk_plan(int n_users_blk, int n_items_local, int d, int K, int he
  * Reference counterpart: MF/model_api.py:62 (the raw ratings) + tf.nn.top_k(..., 50) behind the -inf mask, MF/train_new_api.py:594-612. */
 int pda_item_prep7_f32(const float* I_shard, const int32_t* order, int n_items_local, int d, void* prep, void* stream);      /* pda_item_prep4_bytes(n, d) bytes */
 int pda_item_prep7_bf16(const uint16_t* I_shard, const int32_t* order, int n_items_local, int d, void* prep, void* stream);
+/* Buffer contract -- workspace (pda_score_topk7_workspace_bytes): needs no initialisation -- the call clears the first 256 bytes and initialises every
+ * row's state itself, stream-ordered; afterwards a caller may read +0 (error word), +4, +16 (kernel identity) and +24 (rows served by the exact
+ * fallback); one workspace serves one call at a time. */
 size_t pda_score_topk7_workspace_bytes(int n_users_blk, int n_items_local, int d);
 int pda_score_topk7_f32(const float* U, const float* I_shard, const void* prep, const int32_t* users, int n_users_blk, int item_offset,
                         int n_items_local, int d, const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, int K, int head,

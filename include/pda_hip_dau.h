@@ -57,6 +57,8 @@ int pda_dau_col_splits(int B);
 /* Bytes of the step's workspace: the packed image of the 2 B normalised rows, some words per row, and r and G per side, row and column
  * split.  splits x B is bounded by B + 16 384, so the size is linear in B.  No [B, B] matrix exists in global memory.  0 for a B or d the
  * step refuses. */
+/* Buffer contract -- ws (pda_dau_workspace_bytes): needs no initialisation -- every word a kernel of the call reads was written earlier by the same
+ * call; nothing in it is meant for the caller afterwards; one workspace serves one call at a time (private to one stream). */
 size_t pda_dau_workspace_bytes(int B, int d);
 
 /* The batch's gradients, FOUR launches whatever B (pack the 2 B rows with the alignment term; ONE pass over the Gram tiles of both sides; the

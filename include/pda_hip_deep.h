@@ -39,6 +39,9 @@ extern "C" {
 #define PDA_DEEP_MAX_K 1024
 
 /* Bytes of workspace of a pda_deep_topk_* call (0 for arguments the call refuses).  Non-decreasing in n_users_blk and in K. */
+/* Buffer contract -- workspace (pda_deep_topk_workspace_bytes): needs no initialisation -- the call clears the 256-byte header itself, stream-ordered,
+ * and writes every count and list entry before it reads it; afterwards a caller may read the identity word at +16 (the other header words are zero); one
+ * workspace serves one call at a time. */
 size_t pda_deep_topk_workspace_bytes(int n_users_blk, int n_items_local, int d, int K);
 
 /* Score + head + history mask + top-K of a block of users over an item shard, without the rating matrix.
@@ -56,6 +59,8 @@ int pda_deep_topk_bf16(const uint16_t* U, const uint16_t* I_shard, const float* 
 /* pda_metrics on lists of 1 .. PDA_DEEP_MAX_K columns: sums f64 [4, n_ks] of precision, recall, ndcg, hit over the rows (added to `sums`);
  * r[:K] on a k_cols-long row, divided by min(K, k_cols).  workspace NULL: float atomics; else pda_metrics_deep_workspace_bytes(n_rows, n_ks)
  * bytes and the ordered reduction of pda_metrics_ordered (the same bits run after run). */
+/* Buffer contract -- workspace (pda_metrics_deep_workspace_bytes, or NULL): needs no initialisation -- every partial sum is written by its workgroup
+ * before the second launch adds them; nothing in it is meant for the caller afterwards; one workspace serves one call at a time. */
 size_t pda_metrics_deep_workspace_bytes(int n_rows, int n_ks);
 int pda_metrics_deep(const int32_t* topk, int n_rows, int k_cols, const int64_t* tgt_indptr, const int32_t* tgt_indices, const int32_t* Ks,
                      int n_ks, double* sums, void* workspace, void* stream);

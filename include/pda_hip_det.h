@@ -27,6 +27,8 @@ extern "C" {
  * running step.  plan: the batch's plan (pda_triplet_plan_bytes(B) bytes); scratch: pda_bpr_grad_plan_scratch_bytes(B, d) bytes.
  * A batch the plan rejects (a user occurs twice): loss_acc receives NaN, nothing else is written.
  * d in {32, 64, 128, 256}, else PDA_ERR_UNSUPPORTED.  U, I are read only. */
+/* Buffer contract -- scratch (pda_bpr_grad_plan_scratch_bytes): needs no initialisation -- the first launch writes what the second reads; nothing in it
+ * is meant for the caller afterwards; one scratch buffer serves one call at a time. */
 size_t pda_bpr_grad_plan_scratch_bytes(int B, int d);
 int pda_bpr_grad_plan_f32(const float* U, const float* I, const int32_t* users, const int32_t* pos, const int32_t* neg,
                           const float* pos_pop, const float* neg_pop, int B, int d, float regs, float reg_div, const void* plan,
@@ -45,6 +47,8 @@ int pda_adam_step_plan_f32(float* U, float* mU, float* vU, float* gU, int32_t* t
 /* pda_metrics with an ordered reduction: the same four metrics in the same layout of `sums` (f64 [4][n_ks], added to), but every
  * wave's partial sums go to `workspace` (pda_metrics_ordered_workspace_bytes(n_rows, n_ks) bytes, 8-byte aligned) and a second launch adds
  * them in a fixed order.  Calls that share `sums` must share a stream (the final add is a plain read-modify-write). */
+/* Buffer contract -- workspace (pda_metrics_ordered_workspace_bytes): needs no initialisation -- every partial sum is written by its wave before the
+ * second launch adds them; nothing in it is meant for the caller afterwards; one workspace serves one call at a time. */
 size_t pda_metrics_ordered_workspace_bytes(int n_rows, int n_ks);
 int pda_metrics_ordered(const int32_t* topk, int n_rows, int k_cols, const int64_t* tgt_indptr, const int32_t* tgt_indices,
                         const int32_t* Ks, int n_ks, double* sums, void* workspace, void* stream);

@@ -27,6 +27,9 @@ extern "C" {
 
 /* rows_ws: int32 [pda_dice_rows_ws_words(B)], 16-byte aligned, private to one stream.  Words 0 / 1: |S_u| / |S_i| of the batch seen last
  * (pda_dice_step_f32 zeroes them itself and counts); words from 4 on: the distinct users [B], then the distinct items [2 B]. */
+/* Buffer contract -- rows_ws (pda_dice_rows_ws_words): needs no initialisation -- pda_dice_step_f32 clears words 0 .. 3 itself, stream-ordered, and
+ * lists a row before pda_dice_dis_f32 reads it; afterwards a caller may read words 0 / 1 (the counts); one rows_ws serves one step (step + dis) at a
+ * time. */
 size_t pda_dice_rows_ws_words(int B);
 
 /* The batch's gradients of everything except L_dis (a memset of 16 bytes and one launch).  mask u8 [B]: m.  The gradients are SUMMED into

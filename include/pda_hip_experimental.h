@@ -176,8 +176,13 @@ int pda_score_topk7_phase_bloom_rows(const void* prep, const int32_t* users, int
  *            lets the exact step run at batch sizes where the launch floor no longer matters (B = 32 768 at config 2: see
  *            profiles/round3_train_b_sweep.txt).  workspace: pda_triplet_plan_large_workspace_bytes(B) bytes. */
 size_t pda_triplet_plan_bytes(int B);
+/* Buffer contract -- workspace (pda_triplet_plan_large_workspace_bytes): needs no initialisation -- the call clears the histogram and the plan's header
+ * and flags itself, stream-ordered; nothing in it is meant for the caller afterwards; one workspace serves one call at a time.  A plan's bytes behind
+ * its used part (capacity for 2 B segments) are never written and never read. */
 size_t pda_triplet_plan_large_workspace_bytes(int B);
 int pda_triplet_plan_large(const int32_t* users, const int32_t* pos, const int32_t* neg, int B, void* plan, void* workspace, void* stream);
+/* Buffer contract -- scratch (pda_bpr_step_plan_scratch_bytes): needs no initialisation -- launch A writes what launch B reads; nothing in it is meant
+ * for the caller afterwards; one scratch buffer serves one call at a time. */
 size_t pda_bpr_step_plan_scratch_bytes(int B, int d);
 int pda_triplet_plan(const int32_t* users, const int32_t* pos, const int32_t* neg, int B, int n_batches, void* plans, void* stream);
 int pda_bpr_step_plan_f32(float* U, float* I, const int32_t* users, const int32_t* pos, const int32_t* neg, const float* pos_pop,
@@ -293,6 +298,8 @@ int pda_group_triplets_by_pos_batches(int32_t* users, int32_t* pos, int32_t* neg
  * stream is next synchronised.  update_mode: PDA_UPD_SGD_FUSED (| PDA_UPD_ANY_ORDER).  Equals n_steps x
  * (pda_bpr_step_f32, pda_sample_triplets_dev) on one stream (fp32 atomics: 1e-6).  The grid is at most 384 + 64
  * workgroups, striding over larger batches. */
+/* Buffer contract -- barrier_ws (8 bytes): the ONE workspace of this library with a precondition: both words are ZERO before the first call (word 1
+ * is sticky state the caller reads and clears; word 0 is reset by every call itself, stream-ordered); one barrier_ws serves one call at a time. */
 int pda_bpr_train_steps_f32(float* U, float* I, int d, float regs, float reg_div, float lr, int update_mode,
                             const pda_sample_job* set0, const pda_sample_job* set1, uint64_t* step_ctr, int n_steps,
                             float* loss_acc, float* loss_steps, void* barrier_ws, void* stream);

@@ -47,6 +47,8 @@ int pda_fullsm_col_splits(size_t n_items, int B);
 /* Bytes of the step's workspace: the packed image of the B user rows, 1 / max(|i_c|, 1e-12) per item, the exclusion bit mask of
  * B x ceil(n_items / 32) words, (m, se) per row and column split, the partial g_r [B, d] per column split and some words per row.  No array of
  * B x n_items logits or probabilities exists.  0 for a B, n_items or d the step refuses. */
+/* Buffer contract -- ws (pda_fullsm_workspace_bytes): needs no initialisation -- every word a kernel of the call reads was written earlier by the same
+ * call; nothing in it is meant for the caller afterwards; one workspace serves one call at a time (private to one stream). */
 size_t pda_fullsm_workspace_bytes(int B, size_t n_items, int d);
 
 /* The batch's gradients, nothing read on the host: capturable in a HIP graph.  The launches: pack the user rows; the items' inverse norms

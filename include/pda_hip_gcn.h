@@ -46,6 +46,8 @@ extern "C" {
  * row < n_rows, slot < n_slots, every row finished by exactly one entry of `work` or of `long_rows`. */
 
 /* Bytes of workspace a product over a graph with n_slots partial-sum rows needs (0 slots: 0 bytes, workspace may be NULL). */
+/* Buffer contract -- workspace (pda_gcn_spmm_workspace_bytes; may be NULL when n_slots == 0): needs no initialisation -- every chunk's partial row is
+ * written before the row's sum reads it; nothing in it is meant for the caller afterwards; one workspace serves one call at a time. */
 size_t pda_gcn_spmm_workspace_bytes(size_t n_slots, int d);
 
 /* One weighted CSR x dense product with the fused forms of the two passes, for every row r of the n_rows:

@@ -63,6 +63,9 @@ extern "C" {
  * of bounds. */
 
 /* Bytes of n_slots workspace slots of d * d + d floats (0 slots or an unsupported d: 0 bytes). */
+/* Buffer contract -- workspace (pda_ials_workspace_bytes; may be NULL when n_slots == 0): needs no initialisation -- every slot is written by its chunk
+ * (its block of rows, for the Gram matrix) before it is added up; nothing in it is meant for the caller afterwards; one workspace serves one call at a
+ * time. */
 size_t pda_ials_workspace_bytes(size_t n_slots, int d);
 
 /* G = Z^T Z, f32 [d, d] row-major, over the n_rows rows of Z f32 [n_rows, d]; d in {32, 64, 128}.  The workspace holds

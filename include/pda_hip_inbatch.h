@@ -45,6 +45,8 @@ int pda_inbatch_col_splits(int B);
 
 /* Bytes of the step's workspace, linear in B: the packed image of the 2 B gathered rows, two [B, d] gradient buffers, some words per row and
  * (m, se) per row and column split.  The [B, B] matrix never exists in global memory.  0 for a B or d the step refuses. */
+/* Buffer contract -- ws (pda_inbatch_workspace_bytes): needs no initialisation -- every word a kernel of the call reads was written earlier by the same
+ * call; nothing in it is meant for the caller afterwards; one workspace serves one call at a time (private to one stream). */
 size_t pda_inbatch_workspace_bytes(int B, int d);
 
 /* mask u32 [B, ceil(B / 32)]: bit (r, c) is set iff c != r and pos[c] is in the sorted train row of users[r] (binary search, the sampler's own

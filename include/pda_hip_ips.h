@@ -48,6 +48,8 @@ int pda_ips_step_f32(const float* U, const float* I, size_t n_users, size_t n_it
  * over both tables by pda_adam_dense_sweep4_f32 (the sweep of pda_adam_step_f32: g = 0 off the tagged rows, g zeroed behind itself).  Two or three
  * launches, no host read: capturable in a HIP graph.  wsum_ws: one float of device memory private to the stream.  flags and cache_policy: those
  * of pda_adam_step_f32. */
+/* Buffer contract -- wsum_ws (one float, or NULL: no self-normalisation): needs no initialisation -- the call writes it (pda_ips_weight_sum) before its
+ * step reads it; afterwards a caller may read it (the batch's S); one wsum_ws serves one call at a time. */
 int pda_ips_adam_step_f32(float* U, float* mU, float* vU, float* gU, int32_t* tagU, size_t n_users, float* I, float* mI, float* vI, float* gI,
                           int32_t* tagI, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* neg, const float* ipw,
                           float* wsum_ws, int B, int d, float regs, float reg_div, int step_tag, float lr_t, float beta1, float beta2, float eps,

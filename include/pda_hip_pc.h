@@ -29,6 +29,8 @@ extern "C" {
 
 /* Item moments, float64, once per (I, pop): moments f64 [2 d^2 + d + 1] = G [d][d] = sum_i v_i v_i^T, H [d][d] = sum_i p_i^2 v_i v_i^T,
  * h [d] = sum_i p_i^2 v_i, P = sum_i p_i^2.  workspace: pda_pc_moments_workspace_bytes(n_items, d) bytes.  pop f32 [n_items], > 0. */
+/* Buffer contract -- workspace (pda_pc_moments_workspace_bytes): needs no initialisation -- every block's partial moments are written before the second
+ * launch adds them; nothing in it is meant for the caller afterwards; one workspace serves one call at a time. */
 size_t pda_pc_moments_workspace_bytes(int n_items, int d);
 int pda_pc_item_moments_f32(const float* I, const float* pop, int n_items, int d, double* moments, void* workspace, void* stream);
 
@@ -45,6 +47,9 @@ int pda_pc_user_stats_f32(const float* U, const float* I, const float* pop, cons
  * Synchronises the stream once (to read the number of rows the ranking by r could not settle; those rows alone are swept again,
  * ranked by g).  workspace: pda_pc_score_workspace_bytes(n_users_blk, n_items, d, K) bytes, 256-byte aligned.  Behind the call:
  * workspace + 16 the identity word (1 << 28 | 1 << 16 | d / 64: generation 1, PC head), workspace + 20 the number of fallback rows. */
+/* Buffer contract -- workspace (pda_pc_score_workspace_bytes): needs no initialisation -- its first kernel initialises the two block headers, and every
+ * row minimum, key and list is written before it is read; afterwards a caller may read +16 (kernel identity) and +20 (rows served by the fallback); one
+ * workspace serves one call at a time. */
 size_t pda_pc_score_workspace_bytes(int n_users_blk, int n_items, int d, int K);
 int pda_pc_score_topk_f32(const float* U, const float* I, const float* pop, const float* scale, const int32_t* users, int n_users_blk,
                           int n_items, int d, const int64_t* hist_indptr, const int32_t* hist_indices, int hist_row_mode, double alpha,

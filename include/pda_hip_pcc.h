@@ -44,6 +44,9 @@ extern "C" {
 /* The batch's statistic, two launches.  The score pass (the layout of pda_bpr_step_f32: d / 4 lanes per triplet) writes z_ws f32 [B]: z_t, and 0
  * for a refused triplet (which triplets count is always decided by the ids, never by the value).  The moments pass is ONE workgroup of 1 024
  * threads looping over B: stat f64 [8] = (n_v, zbar, qbar, Szz, Sqq, Szq, r, 0). */
+/* Buffer contract -- z_ws (f32 [B]): needs no initialisation -- the score pass writes every one of its B elements before the moments pass, pda_pcc_grads_f32
+ * and the step read them; afterwards a caller may read all of it (the z_t of this batch); one z_ws (with its stat) serves one batch at a time.
+ * stat is an output, written in full by the moments pass. */
 int pda_pcc_stats_f32(const float* U, const float* I, size_t n_users, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* neg,
                       const float* pop, int B, int d, int on, float* z_ws, double* stat, void* stream);
 

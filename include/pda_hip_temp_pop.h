@@ -50,6 +50,9 @@ int pda_temp_pop_adam_step_f32(float* U, float* mU, float* vU, float* gU, int32_
  *   covers the bias head, a candidate ring, exact fp32 rescoring) wherever it can run (K <= PDA_TOPK_CAP - 4, item ids below 2^27); the exact
  *   one (generation 1, fp32 MFMA) otherwise.  PDA_TEMP_POP_KERNEL=exact | prefiltered forces one.  The kernel writes its identity word at
  *   workspace + 16: generation << 28 | 1 << 15 (bias head) | d / 64. */
+/* Buffer contract -- workspace (pda_temp_pop_score_workspace_bytes): needs no initialisation -- every word the call reads it wrote before (the pre-
+ * filtered kernel's call clears the whole workspace, stream-ordered; the exact kernel's copies alpha to +64 and writes the identity word); afterwards a
+ * caller may read +16 (kernel identity); one workspace serves one call at a time. */
 size_t pda_temp_pop_score_workspace_bytes(int n_users_blk);
 int pda_temp_pop_score_topk_f32(const float* U, const float* I_shard, const void* prep, const float* alpha, const float* beta, const int32_t* users,
                                 int n_users_blk, int item_offset, int n_items_local, int d, const int64_t* hist_indptr, const int32_t* hist_indices,

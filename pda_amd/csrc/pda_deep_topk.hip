@@ -481,6 +481,9 @@ int deep_topk(const void* U, const void* I_shard, const float* pop_shard, const 
     const int cap = deep_cap(K), n_splits = deep_splits(n_users_blk, n_items_local, K);
     const int rows_pad = (n_users_blk + kUserTile - 1) / kUserTile * kUserTile;
     unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+    // the header: cleared here, stream-ordered, so that a caller hands over any memory (the identity word at +16 is written by the sweep; the
+    // other header words read as zero afterwards).  counts and lists are written by the sweep before the final kernel reads them.
+    if (hipMemsetAsync(ws, 0, kDeepHdr, s) != hipSuccess) return PDA_ERR_LAUNCH;
     int* counts = reinterpret_cast<int*>(ws + kDeepHdr);
     uint64_t* lists = reinterpret_cast<uint64_t*>(ws + kDeepHdr + align256((size_t)kDeepMaxSplits * rows_pad * sizeof(int)));
     DeepArgs a{U, I_shard, pop_shard, users, hist_indptr, hist_indices, lists, counts, reinterpret_cast<unsigned*>(ws + 16),

@@ -1859,7 +1859,10 @@ def recommend_topk_pc(U, I, users, pop, scale, alpha, beta, K=50, hist: Optional
         hist = None
     idx = torch.empty((nu, K), dtype=torch.int32, device=U.device)
     val = torch.empty((nu, K), dtype=torch.float32, device=U.device)
-    ws = torch.empty(lib.pda_pc_score_workspace_bytes(nu, n, d, K) + 256, dtype=torch.uint8, device=U.device)
+    nbytes = lib.pda_pc_score_workspace_bytes(nu, n, d, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=U.device)        # exactly the reported size (the caching allocator aligns to 512 bytes)
+    if ws.data_ptr() % 256:
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=U.device)
     off = (-ws.data_ptr()) % 256
     wsa = ws[off:]
     check(lib.pda_pc_score_topk_f32(ptr(U), ptr(I), ptr(pop), ptr(scale), ptr(users), nu, n, d, ptr(hist.indptr) if hist else None,
@@ -1948,7 +1951,6 @@ def recommend_topk_deep(U, I_shard, users, K, head=HEAD_RAW, pop_shard=None, his
         ws = None
         _DEEP_WS.pop(dev, None)            # (released before the larger one is taken)
         ws = _DEEP_WS[dev] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ws[:32].zero_()
     fn = lib.pda_deep_topk_bf16 if bf else lib.pda_deep_topk_f32
     for lo in range(0, nu, chunk):
         hi = min(nu, lo + chunk)
@@ -2209,8 +2211,9 @@ DICE_LOSS_TERMS = 6                       # loss_acc: loss, mf_loss, reg_loss, L
 
 
 def dice_rows_ws(B: int, device) -> torch.Tensor:
-    """The row-list workspace of one batch size (pda_dice_rows_ws_words): int32, private to one stream."""
-    return torch.zeros(int(_lib.load().pda_dice_rows_ws_words(int(B))), dtype=torch.int32, device=device)
+    """The row-list workspace of one batch size (pda_dice_rows_ws_words): int32, private to one stream.  Handed over as it comes: pda_dice_step_f32
+    clears the counts itself and lists a row before pda_dice_dis_f32 reads it."""
+    return torch.empty(int(_lib.load().pda_dice_rows_ws_words(int(B))), dtype=torch.int32, device=device)
 
 
 class DiceState:
@@ -2468,7 +2471,8 @@ class PccPop:
 
 def pcc_workspace(B: int, device):
     """(z_ws float32 [B], stat float64 [8]): the workspace of one batch size, private to one stream."""
-    return torch.zeros(int(B), dtype=torch.float32, device=device), torch.zeros(_lib.PCC_STAT_WORDS, dtype=torch.float64, device=device)
+    # (z_ws as it comes: the score pass of pda_pcc_stats_f32 writes every one of its B elements before the moments pass reads them)
+    return torch.empty(int(B), dtype=torch.float32, device=device), torch.zeros(_lib.PCC_STAT_WORDS, dtype=torch.float64, device=device)
 
 
 def _pcc_on(on: str) -> int:

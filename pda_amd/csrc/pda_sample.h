@@ -3,7 +3,8 @@
 // entry point checks on the host (sample_call_ok).  sample_one, the BPR triplet of a row, is composed of them; it is the body of
 // the stand-alone and the many-batches kernels (pda_aux.hip), of the train step that draws the NEXT batch in spare workgroups of
 // its own launch and of the looped trainer (pda_bpr_step.hip).  PNSM (pda_dice.hip) and the sampled-softmax sampler (pda_ssm.hip)
-// are the same pieces around their own negatives, the in-batch mask (pda_inbatch.hip) is the membership test: a row draws the
+// are the same pieces around their own negatives, the popularity proposal (pda_negpop.hip) is sample_row and sample_block_entry
+// around sample_negative_alias, the in-batch mask (pda_inbatch.hip) is the membership test: a row draws the
 // same user and positive under every method for one (seed, step, row), by construction.
 #pragma once
 #include "pda_common.h"
@@ -134,9 +135,29 @@ __device__ __forceinline__ int sample_negative(uint64_t seed, uint64_t step, int
     return n;
 }
 
-// one thread = one triplet r of the batch
-template <bool COH = false>
-__device__ __forceinline__ void sample_one(SampleArgs a, int r) {
+// The negative of row r under a popularity proposal (include/pda_hip_negpop.h): try k picks a slot of the alias table as
+// sample_negative picks an item, from the same draw, and a coin from draw 0x80000000 | (first_draw + k) keeps the slot or takes
+// its alias; a slot that is its own alias needs no coin, so a table of such slots draws what sample_negative draws, bit for bit.
+// The two hashes of a try do not depend on each other or on the table: both are issued ahead of the 8-byte load.
+constexpr uint32_t kCoinDraw = 0x80000000u;
+
+__device__ __forceinline__ int sample_negative_alias(uint64_t seed, uint64_t step, int r, uint32_t first_draw, uint32_t span, int neg_lo,
+                                                     const uint64_t* alias, const int32_t* indices, int64_t b, int64_t e) {
+    int n = 0;
+    for (uint32_t k = 0; k < kRejectTries; ++k) {
+        const uint32_t slot = bounded(draw(seed, step, r, first_draw + k), span);
+        const uint32_t coin = draw(seed, step, r, kCoinDraw | (first_draw + k));
+        const uint64_t t = alias[slot];
+        const uint32_t thr = (uint32_t)t, other = (uint32_t)(t >> 32);
+        n = neg_lo + (int)((other == slot || coin < thr) ? slot : other);
+        if (!train_row_has(indices, b, e, n)) break;
+    }
+    return n;
+}
+
+// one thread = one triplet r of the batch; negative_of(a, r, b, e): the negative of the row whose train items are indices[b, e)
+template <bool COH, typename NEG>
+__device__ __forceinline__ void sample_row(SampleArgs a, int r, NEG negative_of) {
     if (r >= a.B) return;
     a.step = sample_step(a.step, a.step_dev, a.step_next, r == 0);
     int u;
@@ -157,14 +178,59 @@ __device__ __forceinline__ void sample_one(SampleArgs a, int r) {
         p = a.indices[b + idx];
         slot = a.slots ? a.slots[b + idx] : 0;
     }
-    const int n = sample_negative(a.seed, a.step, r, kNegDraw, (uint32_t)(a.neg_hi - a.neg_lo), a.indices, b, e,
-                                  [&](uint32_t x) { return a.neg_lo + (int)x; });
+    const int n = negative_of(a, r, b, e);
     out_store<COH>(&a.pos[r], p);
     out_store<COH>(&a.neg[r], n);
     if (a.pop && a.pos_pop) {  // :402-403
         out_store<COH>(&a.pos_pop[r], a.pop[(size_t)p * a.n_slots + slot]);
         out_store<COH>(&a.neg_pop[r], a.pop[(size_t)n * a.n_slots + slot]);
     }
+}
+
+// the uniform triplet of row r
+template <bool COH = false>
+__device__ __forceinline__ void sample_one(SampleArgs a, int r) {
+    sample_row<COH>(a, r, [](const SampleArgs& a, int r, int64_t b, int64_t e) {
+        return sample_negative(a.seed, a.step, r, kNegDraw, (uint32_t)(a.neg_hi - a.neg_lo), a.indices, b, e,
+                               [&](uint32_t x) { return a.neg_lo + (int)x; });
+    });
+}
+
+// ---- the [B, N] block of negatives (pda_ssm.hip, pda_negpop.hip): one thread per (row r, negative j) ---------------------------
+struct SsmSampleArgs {
+    int32_t* users;
+    const int32_t* user_pool;
+    const int64_t* indptr;
+    const int32_t* indices;
+    int32_t* pos;
+    int32_t* negs;
+    uint64_t seed, step;
+    int B, N, n_pool, gen_users, neg_lo, neg_hi;
+    const uint64_t* step_dev;   // optional device-resident step counter added to `step`
+    uint64_t* step_next;        // optional: receives *step_dev + 1 (a DIFFERENT location)
+};
+
+// The pieces of sample_row without slots and popularities: every thread of a row finds the row's user, the thread of j == 0
+// writes it and the positive; negative j takes the tries [kNegDraw + kRejectTries j, + kRejectTries), so column 0 is the
+// triplet's negative.  negative_of(a, r, first_draw, b, e): the negative drawn from first_draw on.
+template <typename NEG>
+__device__ __forceinline__ void sample_block_entry(SsmSampleArgs a, size_t i, NEG negative_of) {
+    if (i >= (size_t)a.B * (size_t)a.N) return;
+    const int r = (int)(i / (size_t)a.N), j = (int)(i % (size_t)a.N);
+    a.step = sample_step(a.step, a.step_dev, a.step_next, i == 0);
+    int u;
+    if (a.gen_users) {
+        u = sample_user(a.seed, a.step, r, a.B, a.n_pool, a.user_pool);
+        if (j == 0) a.users[r] = u;
+    } else {
+        u = a.users[r];
+    }
+    const int64_t b = a.indptr[u], e = a.indptr[u + 1];
+    if (j == 0) {
+        const int len = (int)(e - b);
+        a.pos[r] = len == 0 ? 0 : a.indices[b + sample_pos_index(a.seed, a.step, r, len)];
+    }
+    a.negs[i] = negative_of(a, r, kNegDraw + kRejectTries * (uint32_t)j, b, e);
 }
 
 // (host) What every sampler entry point checks: the users, the train CSR and the two outputs every method has are there, users
@@ -182,6 +248,12 @@ inline bool triplet_sample_ok(const SampleArgs& a, bool counter) {
     if (!sample_call_ok(a.users, a.indptr, a.indices, a.pos, a.neg, a.gen_users, a.n_pool, counter, a.step_dev, a.step_next)) return false;
     if (a.B <= 0 || a.neg_hi <= a.neg_lo) return false;
     return !(a.pop && (!a.pos_pop || !a.neg_pop || a.n_slots <= 0));
+}
+
+// (host) a [B, N] block job as a whole: B <= 2^22 and N <= max_negs (PDA_SSM_MAX_NEGS) keep B N <= 2^30
+inline bool block_sample_ok(const SsmSampleArgs& a, bool counter, int max_negs) {
+    if (!sample_call_ok(a.users, a.indptr, a.indices, a.pos, a.negs, a.gen_users, a.n_pool, counter, a.step_dev, a.step_next)) return false;
+    return !(a.B <= 0 || a.B > (1 << 22) || a.neg_hi <= a.neg_lo || a.N < 1 || a.N > max_negs);
 }
 
 }  // namespace

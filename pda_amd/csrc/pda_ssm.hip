@@ -14,6 +14,7 @@
 #include "pda_train_common.h"
 #include "pda_sample.h"
 #include "pda_hip_ssm.h"
+#include "pda_hip_negpop.h"   // (the logQ entries of the step)
 
 namespace {
 
@@ -68,8 +69,25 @@ __device__ __forceinline__ float ssm_logit(f32x4 uq, f32x4 ie, float inv_tau, fl
 // item k of row t: the positive for k == 0, negative k - 1 otherwise; past N (the tail of the last round) the positive again, never used
 __device__ __forceinline__ int ssm_item(const int32_t* negs_row, int p, int k, int N) { return (k == 0 || k > N) ? p : negs_row[k - 1]; }
 
-template <int D, bool NORM>
-__device__ __forceinline__ void ssm_step_body(const SsmStepArgs& a) {
+// log q of a round's kChunk items, loaded with the round's gathers; without LOGQ it holds nothing and a logit passes through unchanged
+template <bool LOGQ>
+struct LogqChunk {
+    float v[kChunk];
+    __device__ __forceinline__ void load(const float* logq, const int (&id)[kChunk]) {
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) v[j] = logq[id[j]];
+    }
+    __device__ __forceinline__ float less(float s, int j) const { return s - v[j]; }
+};
+template <>
+struct LogqChunk<false> {
+    __device__ __forceinline__ void load(const float*, const int (&)[kChunk]) {}
+    __device__ __forceinline__ float less(float s, int) const { return s; }
+};
+
+// LOGQ: s_k takes - logq[item_k], the positive's own logit included (include/pda_hip_negpop.h); the value rides with the row's gather
+template <int D, bool NORM, bool LOGQ = false>
+__device__ __forceinline__ void ssm_step_body(const SsmStepArgs& a, const float* logq = nullptr) {
     constexpr int L = D / 4;        // lanes per row
     constexpr int TPB = 512 / L;    // rows per block
     __shared__ float red[2][8];
@@ -112,11 +130,13 @@ __device__ __forceinline__ void ssm_step_body(const SsmStepArgs& a) {
             for (int j = 0; j < kChunk; ++j) id[j] = ssm_item(negs_row, p, k0 + j, N);
 #pragma unroll
             for (int j = 0; j < kChunk; ++j) ie[j] = *reinterpret_cast<const f32x4*>(a.I + (size_t)id[j] * D + 4 * e);
+            LogqChunk<LOGQ> lq;
+            lq.load(logq, id);
 #pragma unroll
             for (int j = 0; j < kChunk; ++j) {
                 if (k0 + j > N) break;
                 float cs, inv_in;
-                const float s = ssm_logit<D, NORM>(uq, ie[j], a.inv_tau, cs, inv_in);
+                const float s = lq.less(ssm_logit<D, NORM>(uq, ie[j], a.inv_tau, cs, inv_in), j);
                 sq += dot4(ie[j], ie[j]);
                 if (k0 + j == 0) {
                     m = s, se = 1.f, s0 = s;
@@ -142,11 +162,13 @@ __device__ __forceinline__ void ssm_step_body(const SsmStepArgs& a) {
             for (int j = 0; j < kChunk; ++j) id[j] = ssm_item(negs_row, p, k0 + j, N);
 #pragma unroll
             for (int j = 0; j < kChunk; ++j) ie[j] = *reinterpret_cast<const f32x4*>(a.I + (size_t)id[j] * D + 4 * e);
+            LogqChunk<LOGQ> lq;
+            lq.load(logq, id);
 #pragma unroll
             for (int j = 0; j < kChunk; ++j) {
                 if (k0 + j > N) break;
                 float cs, inv_in;
-                const float s = ssm_logit<D, NORM>(uq, ie[j], a.inv_tau, cs, inv_in);
+                const float s = lq.less(ssm_logit<D, NORM>(uq, ie[j], a.inv_tau, cs, inv_in), j);
                 const float pk = expf(s - m) * inv_se;
                 const float c = (k0 + j == 0 ? pk - 1.f : pk) * cscale;
                 f32x4 die;
@@ -192,41 +214,22 @@ __global__ void __launch_bounds__(512) ssm_step_kernel(SsmStepArgs a) { ssm_step
 template <int D>
 __global__ void __launch_bounds__(512) ssm_step_norm_kernel(SsmStepArgs a) { ssm_step_body<D, true>(a); }
 
-// ---- the sampler: one thread per (row r, negative j) -----------------------------------------------------------------------------------------
-struct SsmSampleArgs {
-    int32_t* users;
-    const int32_t* user_pool;
-    const int64_t* indptr;
-    const int32_t* indices;
-    int32_t* pos;
-    int32_t* negs;
-    uint64_t seed, step;
-    int B, N, n_pool, gen_users, neg_lo, neg_hi;
-    const uint64_t* step_dev;   // optional device-resident step counter added to `step`
-    uint64_t* step_next;        // optional: receives *step_dev + 1 (a DIFFERENT location)
+struct SsmLogqArgs {
+    SsmStepArgs a;
+    const float* logq;      // f32 [n_items]
 };
+template <int D>
+__global__ void __launch_bounds__(512) ssm_step_logq_kernel(SsmLogqArgs q) { ssm_step_body<D, false, true>(q.a, q.logq); }
+template <int D>
+__global__ void __launch_bounds__(512) ssm_step_norm_logq_kernel(SsmLogqArgs q) { ssm_step_body<D, true, true>(q.a, q.logq); }
 
-// The pieces of sample_one (pda_sample.h) without slots and popularities: every thread of a row finds the row's user, the thread of j == 0
-// writes it and the positive; negative j takes the tries [kNegDraw + kRejectTries j, + kRejectTries), so column 0 is the triplet's negative.
+// ---- the sampler: one thread per (row r, negative j) -----------------------------------------------------------------------------------------
+// the pieces are pda_sample.h's (sample_block_entry); the negatives are uniform
 __global__ void __launch_bounds__(64) ssm_sample_kernel(SsmSampleArgs a) {
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= (size_t)a.B * (size_t)a.N) return;
-    const int r = (int)(i / (size_t)a.N), j = (int)(i % (size_t)a.N);
-    a.step = sample_step(a.step, a.step_dev, a.step_next, i == 0);
-    int u;
-    if (a.gen_users) {
-        u = sample_user(a.seed, a.step, r, a.B, a.n_pool, a.user_pool);
-        if (j == 0) a.users[r] = u;
-    } else {
-        u = a.users[r];
-    }
-    const int64_t b = a.indptr[u], e = a.indptr[u + 1];
-    if (j == 0) {
-        const int len = (int)(e - b);
-        a.pos[r] = len == 0 ? 0 : a.indices[b + sample_pos_index(a.seed, a.step, r, len)];
-    }
-    a.negs[i] = sample_negative(a.seed, a.step, r, kNegDraw + kRejectTries * (uint32_t)j, (uint32_t)(a.neg_hi - a.neg_lo), a.indices, b, e,
-                                [&](uint32_t x) { return a.neg_lo + (int)x; });
+    sample_block_entry(a, (size_t)blockIdx.x * 64 + threadIdx.x, [](const SsmSampleArgs& a, int r, uint32_t first_draw, int64_t b, int64_t e) {
+        return sample_negative(a.seed, a.step, r, first_draw, (uint32_t)(a.neg_hi - a.neg_lo), a.indices, b, e,
+                               [&](uint32_t x) { return a.neg_lo + (int)x; });
+    });
 }
 
 // ---- Y[r] = X[r] / max(|X[r]|, 1e-12): d/4 lanes per row, the sum of squares in float64 (order: include/pda_hip_ssm.h) ---------------------------
@@ -251,8 +254,15 @@ __global__ void __launch_bounds__(512) ssm_normalize_kernel(const float* X, size
 }
 
 // (arguments checked by the callers)
-int launch_step(const SsmStepArgs& a, int d, int norm, hipStream_t s) {
-    if (norm) {
+int launch_step(const SsmStepArgs& a, const float* logq, int d, int norm, hipStream_t s) {
+    if (logq) {
+        const SsmLogqArgs q{a, logq};
+        if (norm) {
+            PDA_STEP_LAUNCH(ssm_step_norm_logq_kernel, d, a.B, s, q)
+        } else {
+            PDA_STEP_LAUNCH(ssm_step_logq_kernel, d, a.B, s, q)
+        }
+    } else if (norm) {
         PDA_STEP_LAUNCH(ssm_step_norm_kernel, d, a.B, s, a)
     } else {
         PDA_STEP_LAUNCH(ssm_step_kernel, d, a.B, s, a)
@@ -283,10 +293,9 @@ SsmStepArgs step_args(const float* U, const float* I, size_t n_users, size_t n_i
 int ssm_sample(bool counter, int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, int N, const int64_t* train_indptr,
                const int32_t* train_indices, int neg_lo, int neg_hi, uint64_t seed, uint64_t step, const uint64_t* step_dev, uint64_t* step_next,
                int32_t* pos, int32_t* negs, void* stream) {
-    if (!sample_call_ok(users, train_indptr, train_indices, pos, negs, gen_users, n_pool, counter, step_dev, step_next)) return PDA_ERR_ARG;
-    if (B <= 0 || B > (1 << 22) || neg_hi <= neg_lo || N < 1 || N > PDA_SSM_MAX_NEGS) return PDA_ERR_ARG;
     const SsmSampleArgs a{users, user_pool, train_indptr, train_indices, pos, negs, seed, step, B, N, n_pool, gen_users, neg_lo, neg_hi,
                           step_dev, step_next};
+    if (!block_sample_ok(a, counter, PDA_SSM_MAX_NEGS)) return PDA_ERR_ARG;
     const size_t n = (size_t)B * (size_t)N;             // <= 2^30: B <= 2^22, N <= 256
     hipLaunchKernelGGL(ssm_sample_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
     PDA_CHECK_LAUNCH();
@@ -295,28 +304,44 @@ int ssm_sample(bool counter, int32_t* users, int gen_users, const int32_t* user_
 
 }  // namespace
 
+extern "C" int pda_ssm_step_logq_f32(const float* U, const float* I, size_t n_users, size_t n_items, const int32_t* users, const int32_t* pos,
+                                     const int32_t* negs, const float* logq, int B, int N, int d, float tau, int norm, float regs, float reg_div,
+                                     float* gU, float* gI, int32_t* tagU, int32_t* tagI, int step_tag, int flags, float* loss_acc, void* stream) {
+    const int rc = check_step(U, I, n_users, n_items, users, pos, negs, B, N, d, tau, norm, reg_div, gU, gI, tagU, tagI, step_tag, flags);
+    if (rc != PDA_OK) return rc;
+    return launch_step(step_args(U, I, n_users, n_items, users, pos, negs, B, N, tau, regs, reg_div, gU, gI, tagU, tagI, step_tag, flags, loss_acc),
+                       logq, d, norm, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int pda_ssm_step_f32(const float* U, const float* I, size_t n_users, size_t n_items, const int32_t* users, const int32_t* pos,
                                 const int32_t* negs, int B, int N, int d, float tau, int norm, float regs, float reg_div, float* gU, float* gI,
                                 int32_t* tagU, int32_t* tagI, int step_tag, int flags, float* loss_acc, void* stream) {
-    const int rc = check_step(U, I, n_users, n_items, users, pos, negs, B, N, d, tau, norm, reg_div, gU, gI, tagU, tagI, step_tag, flags);
+    return pda_ssm_step_logq_f32(U, I, n_users, n_items, users, pos, negs, nullptr, B, N, d, tau, norm, regs, reg_div, gU, gI, tagU, tagI, step_tag,
+                                 flags, loss_acc, stream);
+}
+
+extern "C" int pda_ssm_adam_step_logq_f32(float* U, float* mU, float* vU, float* gU, int32_t* tagU, size_t n_users, float* I, float* mI, float* vI,
+                                          float* gI, int32_t* tagI, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* negs,
+                                          const float* logq, int B, int N, int d, float tau, int norm, float regs, float reg_div, int step_tag,
+                                          float lr_t, float beta1, float beta2, float eps, int flags, int cache_policy, float* loss_acc,
+                                          void* stream) {
+    if (!mU || !vU || !mI || !vI) return PDA_ERR_ARG;
+    if (cache_policy < PDA_ADAM_CACHE_AUTO || cache_policy > PDA_ADAM_CACHE_STREAM) return PDA_ERR_ARG;
+    int rc = check_step(U, I, n_users, n_items, users, pos, negs, B, N, d, tau, norm, reg_div, gU, gI, tagU, tagI, step_tag, flags);
     if (rc != PDA_OK) return rc;
-    return launch_step(step_args(U, I, n_users, n_items, users, pos, negs, B, N, tau, regs, reg_div, gU, gI, tagU, tagI, step_tag, flags, loss_acc), d,
-                       norm, reinterpret_cast<hipStream_t>(stream));
+    rc = launch_step(step_args(U, I, n_users, n_items, users, pos, negs, B, N, tau, regs, reg_div, gU, gI, tagU, tagI, step_tag, flags, loss_acc),
+                     logq, d, norm, reinterpret_cast<hipStream_t>(stream));
+    if (rc != PDA_OK) return rc;
+    return pda_adam_dense_sweep4_f32(U, mU, vU, gU, n_users, tagU, I, mI, vI, gI, n_items, tagI, d, step_tag, lr_t, beta1, beta2, eps, cache_policy,
+                                     stream);
 }
 
 extern "C" int pda_ssm_adam_step_f32(float* U, float* mU, float* vU, float* gU, int32_t* tagU, size_t n_users, float* I, float* mI, float* vI,
                                      float* gI, int32_t* tagI, size_t n_items, const int32_t* users, const int32_t* pos, const int32_t* negs, int B,
                                      int N, int d, float tau, int norm, float regs, float reg_div, int step_tag, float lr_t, float beta1,
                                      float beta2, float eps, int flags, int cache_policy, float* loss_acc, void* stream) {
-    if (!mU || !vU || !mI || !vI) return PDA_ERR_ARG;
-    if (cache_policy < PDA_ADAM_CACHE_AUTO || cache_policy > PDA_ADAM_CACHE_STREAM) return PDA_ERR_ARG;
-    int rc = check_step(U, I, n_users, n_items, users, pos, negs, B, N, d, tau, norm, reg_div, gU, gI, tagU, tagI, step_tag, flags);
-    if (rc != PDA_OK) return rc;
-    rc = launch_step(step_args(U, I, n_users, n_items, users, pos, negs, B, N, tau, regs, reg_div, gU, gI, tagU, tagI, step_tag, flags, loss_acc), d,
-                     norm, reinterpret_cast<hipStream_t>(stream));
-    if (rc != PDA_OK) return rc;
-    return pda_adam_dense_sweep4_f32(U, mU, vU, gU, n_users, tagU, I, mI, vI, gI, n_items, tagI, d, step_tag, lr_t, beta1, beta2, eps, cache_policy,
-                                     stream);
+    return pda_ssm_adam_step_logq_f32(U, mU, vU, gU, tagU, n_users, I, mI, vI, gI, tagI, n_items, users, pos, negs, nullptr, B, N, d, tau, norm, regs,
+                                      reg_div, step_tag, lr_t, beta1, beta2, eps, flags, cache_policy, loss_acc, stream);
 }
 
 extern "C" int pda_ssm_sample(int32_t* users, int gen_users, const int32_t* user_pool, int n_pool, int B, int N, const int64_t* train_indptr,

@@ -855,10 +855,10 @@ def check_dns(args):
     """--neg_sampler dns: refuse, before anything is built, what dynamic negative sampling has no path for.  Every message names its flag.
     The sampler scores its candidates on the live fp32 tables of a BPRMF / PD model right before the step that trains on them."""
     mode = getattr(args, "neg_sampler", "uniform")
-    if mode == "uniform":
+    if mode in ("uniform", "pop"):      # (pop: check_negpop)
         return
     if mode != "dns":
-        raise ValueError("--neg_sampler must be uniform or dns, got %s" % (mode,))
+        raise ValueError("--neg_sampler must be uniform, dns or pop, got %s" % (mode,))
     train = getattr(args, "train", "normal")
     if train not in ("normal", "s_condition"):
         raise NotImplementedError("--train %s: --neg_sampler dns goes with --train normal (the raw head) and --train s_condition (the popularity "
@@ -884,6 +884,31 @@ def check_dns(args):
         raise ValueError("--dns_topn must be an integer in 1 .. --dns_candidates = %d, got %s" % (int(M), N))
 
 
+def check_negpop(args):
+    """--neg_sampler pop: refuse, before anything is built, what popularity-weighted negative sampling has no path for.  Every message names
+    its flag.  The batches have the layout of the uniform sampler's, so whatever trains on those goes through: the optimisers,
+    --deterministic 1 with --train normal | s_condition, LightGCN, bf16 tables."""
+    if getattr(args, "neg_sampler", "uniform") != "pop":
+        return
+    train = getattr(args, "train", "normal")
+    if train not in ("normal", "s_condition", "ssm"):
+        raise NotImplementedError("--train %s: --neg_sampler pop goes with --train normal, --train s_condition and --train ssm (--ssm_source sampled) "
+                                  "only" % (train,))
+    if train == "ssm" and getattr(args, "ssm_source", "sampled") != "sampled":
+        raise NotImplementedError("--ssm_source %s: nothing is sampled there, --neg_sampler pop goes with --ssm_source sampled" % (args.ssm_source,))
+    if getattr(args, "sampler", "device") != "device":
+        raise NotImplementedError("--sampler %s: --neg_sampler pop is the device sampler's (--sampler device)" % (args.sampler,))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --neg_sampler pop trains on one GPU (no item shards)" % (args.gpus,))
+    beta = getattr(args, "neg_pop_power", 0.75)
+    try:
+        ok = math.isfinite(float(beta)) and 0.0 <= float(beta) <= ops.NEGPOP_MAX_POWER
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("--neg_pop_power must be a finite number in [0, %g], got %s" % (ops.NEGPOP_MAX_POWER, beta))
+
+
 class SSMBPRMF(BPRMF):
     """BPR-MF tables trained with the sampled-softmax loss (include/pda_hip_ssm.h): one positive and --ssm_negs sampled negatives
     per row under a softmax with temperature --ssm_tau, on cosine similarity with --ssm_norm 1.  Fetchables and checkpoint layout are those of
@@ -895,7 +920,9 @@ class SSMBPRMF(BPRMF):
     set_train_graph before the first step.  Tables, lists and checkpoint layout are the same.
     --ssm_source all (include/pda_hip_fullsm.h): a row's negatives are ALL items the user has not interacted with
     (--ssm_mask_train 1; every item with 0), the loss the other two sources estimate; a step is pda_fullsm_adam_step_f32 on the train graph of
-    set_train_graph.  --ssm_negs and --ssm_logq play no part."""
+    set_train_graph.  --ssm_negs and --ssm_logq play no part.
+    --ssm_source sampled under --neg_sampler pop: the negatives come from a popularity proposal; with --ssm_logq 1 the step is
+    pda_ssm_adam_step_logq_f32 on the proposal's log q, which the trainer hands over with set_neg_logq before the first step."""
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
         check_ssm(args)
@@ -911,11 +938,23 @@ class SSMBPRMF(BPRMF):
         self._graph = None                   # (train_indptr, train_indices, user_pool) of --ssm_source batch
         self._inbatch = None                 # its workspace, mask and logq, allocated once
         self._fullsm = None                  # the workspace of --ssm_source all, allocated once
+        self.neg_sampler = str(getattr(args, "neg_sampler", "uniform"))
+        self.neg_pop_power = float(getattr(args, "neg_pop_power", 0.75))
+        self._neg_logq = None                # log q of the negatives' proposal (set_neg_logq)
 
     def set_train_graph(self, train_indptr, train_indices, user_pool=None):
         """--ssm_source batch | all: the train CSR on the device (int64 indptr, int32 item ids sorted inside a row) the mask is taken from, and
         (batch) the sampler's user pool the logQ table is computed for."""
         self._graph, self._inbatch, self._fullsm = (train_indptr, train_indices, user_pool), None, None
+
+    def wants_neg_logq(self) -> bool:
+        """Does a step subtract the proposal's log q?  The sampled source under --neg_sampler pop with --ssm_logq 1."""
+        return self.ssm_source == "sampled" and self.neg_sampler == "pop" and bool(self.ssm_logq)
+
+    def set_neg_logq(self, logq):
+        """--neg_sampler pop with --ssm_logq 1: float32 [n_items] on the tables' device, log q_i of the proposal the negatives are drawn from
+        (ops.NegPopTable.logq)."""
+        self._neg_logq = logq
 
     def _inbatch_buffers(self, B, U, I):
         if self._inbatch is None or self._inbatch["B"] != B:
@@ -976,9 +1015,15 @@ class SSMBPRMF(BPRMF):
                                  lr_t=ops.adam_lr_t(self.lr, self._t), train_indptr=indptr, train_indices=indices,
                                  users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
             return self._loss
+        logq = None
+        if self.wants_neg_logq():
+            if self._neg_logq is None:
+                raise ValueError("--neg_sampler pop with --ssm_logq 1 needs the proposal's log q: call set_neg_logq first")
+            logq = self._neg_logq
         ops.ssm_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, negs,
                           tau=self.ssm_tau, norm=self.ssm_norm, regs=self.decay, reg_div=self.batch_size, step=self._t,
-                          lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+                          lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss,
+                          logq=logq)
         return self._loss
 
     def state_dict(self):
@@ -988,6 +1033,8 @@ class SSMBPRMF(BPRMF):
             sd.update(ssm_source=self.ssm_source, ssm_logq=self.ssm_logq, ssm_mask_train=self.ssm_mask_train)
         elif self.ssm_source == "all":      # (no logQ on the exact softmax)
             sd.update(ssm_source=self.ssm_source, ssm_mask_train=self.ssm_mask_train)
+        elif self.neg_sampler == "pop":     # (a run under the popularity proposal: what it drew from and whether the logits were corrected)
+            sd.update(neg_sampler=self.neg_sampler, neg_pop_power=self.neg_pop_power, ssm_logq=self.ssm_logq)
         return sd
 
 

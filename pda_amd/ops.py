@@ -2887,6 +2887,13 @@ def _ssm_params(tau, norm):
     return tau, int(norm)
 
 
+def _ssm_logq(logq, I):
+    """logq of the sampled-softmax steps: None, or float32 [n_items] beside the tables."""
+    if logq is not None and (_need(logq, torch.float32, "logq").dim() != 1 or logq.numel() != I.shape[0] or logq.device != I.device):
+        raise ValueError(f"SSM logq: float32 [n_items] = [{I.shape[0]}] on the tables' device")
+    return logq
+
+
 def _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids: bool):
     """The tables and (users, pos) as every tagged step checks them, negs int32 [B, N] with 1 <= N <= SSM_MAX_NEGS -> (d, B, N)."""
     negs = _need(negs, torch.int32, "negs")
@@ -2902,35 +2909,50 @@ def _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids: bool):
 
 
 def ssm_step(U, I, users, pos, negs, gU, gI, tagU, tagI, *, tau: float, norm: int, regs: float, reg_div: float, step: int, grouped: bool = False,
-             users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+             users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True, logq: Optional[torch.Tensor] = None):
     """pda_ssm_step_f32: the batch's sampled-softmax gradient summed into gU / gI (rows tagged `step`), no update.  negs int32 [B, N].
-    loss_acc float32 [3] += (loss, mf_loss, reg_loss)."""
+    loss_acc float32 [3] += (loss, mf_loss, reg_loss).  logq float32 [n_items]: pda_ssm_step_logq_f32, every logit takes - logq[item]."""
     d, B, N = _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids)
+    logq = _ssm_logq(logq, I)
     tau, norm = _ssm_params(tau, norm)
     gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
     if gU.shape != U.shape or gI.shape != I.shape:
         raise ValueError("gU / gI have the shapes of the tables")
-    check(_lib.load().pda_ssm_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(negs), B, N, d, tau, norm, float(regs),
-                                       float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step), _ips_flags(grouped, users_distinct),
-                                       ptr(loss_acc), stream_ptr()), "pda_ssm_step_f32")
+    if logq is None:
+        check(_lib.load().pda_ssm_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(negs), B, N, d, tau, norm, float(regs),
+                                           float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step), _ips_flags(grouped, users_distinct),
+                                           ptr(loss_acc), stream_ptr()), "pda_ssm_step_f32")
+    else:
+        check(_lib.load().pda_ssm_step_logq_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(negs), ptr(logq), B, N, d, tau, norm,
+                                                float(regs), float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step),
+                                                _ips_flags(grouped, users_distinct), ptr(loss_acc), stream_ptr()), "pda_ssm_step_logq_f32")
     mark_modified(gU, gI)
 
 
 def ssm_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, negs, *, tau: float, norm: int, regs: float, reg_div: float, step: int,
                   lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False, users_distinct: bool = False,
-                  cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+                  cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False,
+                  logq: Optional[torch.Tensor] = None):
     """pda_ssm_adam_step_f32: one sampled-softmax train step (the gradients, TF-1.14 dense-decay Adam over both tables) in two launches;
-    graph-capturable.  The arguments of adam_step with negs int32 [B, N] in place of the negative and the popularities."""
+    graph-capturable.  The arguments of adam_step with negs int32 [B, N] in place of the negative and the popularities.  logq float32
+    [n_items]: pda_ssm_adam_step_logq_f32."""
     d, B, N = _ssm_check(U, I, users, pos, negs, tagU, tagI, loss_acc, check_ids)
+    logq = _ssm_logq(logq, I)
     tau, norm = _ssm_params(tau, norm)
     for t in (mU, vU, gU, mI, vI, gI):
         _need(t, torch.float32, "adam state")
     if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
         raise ValueError("the Adam state tables have the shapes of U and I")
-    check(_lib.load().pda_ssm_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI),
-                                            I.shape[0], ptr(users), ptr(pos), ptr(negs), B, N, d, tau, norm, float(regs), float(reg_div), int(step),
-                                            float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy), ptr(loss_acc),
-                                            stream_ptr()), "pda_ssm_adam_step_f32")
+    if logq is None:
+        check(_lib.load().pda_ssm_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI),
+                                                I.shape[0], ptr(users), ptr(pos), ptr(negs), B, N, d, tau, norm, float(regs), float(reg_div), int(step),
+                                                float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy), ptr(loss_acc),
+                                                stream_ptr()), "pda_ssm_adam_step_f32")
+    else:
+        check(_lib.load().pda_ssm_adam_step_logq_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI),
+                                                     ptr(tagI), I.shape[0], ptr(users), ptr(pos), ptr(negs), ptr(logq), B, N, d, tau, norm, float(regs),
+                                                     float(reg_div), int(step), float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct),
+                                                     int(cache_policy), ptr(loss_acc), stream_ptr()), "pda_ssm_adam_step_logq_f32")
     mark_modified(U, I)
 
 
@@ -3412,6 +3434,252 @@ def dns_sample_into(out, U, I, train_indptr, train_indices, *, n_cands: int, top
                                              ptr(train_indptr), ptr(train_indices), ptr(train_slots), ptr(pop_matrix), n_slots, lo, hi, M, int(topn),
                                              int(head), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(neg), ptr(pp), ptr(pn), ptr(cand),
                                              ptr(score), ptr(col), stream_ptr()), "pda_dns_sample_f32_dev")
+    return out
+
+
+# ---- popularity-weighted negative sampling (include/pda_hip_negpop.h) -------------------------------------------------------------------------
+NEGPOP_MAX_POWER = 4.0
+
+
+def negpop_weights(counts, power: float):
+    """w_i = (c_i + 1)^power in float64: the + 1 keeps an item without train pairs drawable, power 0 is exactly uniform (every w is 1.0)."""
+    import numpy as np
+    power = float(power)
+    if not (math.isfinite(power) and 0.0 <= power <= NEGPOP_MAX_POWER):
+        raise ValueError(f"negative sampler: the popularity power must be a finite number in [0, {NEGPOP_MAX_POWER:g}], got {power}")
+    return (np.asarray(counts, dtype=np.float64) + 1.0) ** power
+
+
+def negpop_alias(w):
+    """Vose's alias method on weights w > 0 (float64 [n]) -> (thr uint32 [n], alias uint32 [n]).  p = w n / sum(w); while both work lists
+    hold slots, a slot with p < 1 takes thr = min(rint(p 2^32), 2^32 - 1) and the slot with p >= 1 whose turn it is as its alias, which keeps
+    (p_large + p_small) - 1.  Whatever is left when one list runs dry is full: alias == slot (thr 2^32 - 1, never looked at)."""
+    import numpy as np
+    w = np.asarray(w, dtype=np.float64)
+    n = w.size
+    if n < 1 or not np.isfinite(w).all() or not (w > 0).all():
+        raise ValueError("negpop_alias: finite weights > 0, at least one")
+    p = w * n / w.sum()
+    thr = np.full(n, 2 ** 32 - 1, dtype=np.uint64)
+    alias = np.arange(n, dtype=np.uint64)
+    small = np.flatnonzero(p < 1.0).tolist()
+    large = np.flatnonzero(p >= 1.0).tolist()
+    p = p.tolist()
+    while small and large:
+        s, l = small.pop(), large.pop()
+        thr[s] = min(int(np.rint(p[s] * 4294967296.0)), 2 ** 32 - 1)
+        alias[s] = l
+        p[l] = (p[l] + p[s]) - 1.0
+        (large if p[l] >= 1.0 else small).append(l)
+    return thr.astype(np.uint32), alias.astype(np.uint32)
+
+
+class NegPopTable:
+    """The proposal of `--neg_sampler pop` over the sampler's range [neg_lo, neg_hi): q_i ~ (c_i + 1)^power, c_i the number of entries of the
+    train CSR that hold item i.  Built once per run on the host in float64.
+        table   uint64 [n] on `device` (held as int64): low word thr, high word alias (a slot of [0, n)); alias == slot: the slot is full
+        q       numpy float64 [n_items], zero outside the range
+        logq    numpy float32 [n_items]; an item with q = 0 takes the log of the smallest positive q (as inbatch_logq does)
+    from_slots builds one from hand-made (thr, alias).  Every table is refused unless alias < n: the kernels index with it."""
+
+    def __init__(self, train_indices, n_items: int, power: float, neg_range, device):
+        import numpy as np
+        idx = train_indices.cpu().numpy() if torch.is_tensor(train_indices) else np.asarray(train_indices)
+        n_items = int(n_items)
+        lo, hi = int(neg_range[0]), int(neg_range[1])
+        if not 0 <= lo < hi <= n_items:
+            raise ValueError(f"NegPopTable: neg_range = (lo, hi) with 0 <= lo < hi <= n_items = {n_items}, got ({lo}, {hi})")
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= n_items):
+            raise ValueError("NegPopTable: a train item lies outside [0, n_items)")
+        counts = np.bincount(idx.astype(np.int64), minlength=n_items)
+        w = negpop_weights(counts[lo:hi], power)
+        thr, alias = negpop_alias(w)
+        q = np.zeros(n_items, dtype=np.float64)
+        q[lo:hi] = w / w.sum()
+        self.power = float(power)
+        self._finish(thr, alias, lo, hi, n_items, q, device)
+
+    @classmethod
+    def from_slots(cls, thr, alias, neg_range, n_items: int, device, q=None):
+        """A table from its slots as they are (thr, alias: n integers below 2^32 each); q: its distribution where the caller has one."""
+        import numpy as np
+        self = cls.__new__(cls)
+        self.power = None
+        lo, hi = int(neg_range[0]), int(neg_range[1])
+        if not 0 <= lo < hi <= int(n_items):
+            raise ValueError(f"NegPopTable: neg_range = (lo, hi) with 0 <= lo < hi <= n_items = {n_items}, got ({lo}, {hi})")
+        thr, alias = np.asarray(thr, dtype=np.uint64), np.asarray(alias, dtype=np.uint64)
+        if (thr >= 2 ** 32).any():
+            raise ValueError("NegPopTable: a threshold does not fit 32 bits")
+        self._finish(thr, alias, lo, hi, int(n_items), None if q is None else np.asarray(q, dtype=np.float64), device)
+        return self
+
+    def _finish(self, thr, alias, lo, hi, n_items, q, device):
+        import numpy as np
+        n = hi - lo
+        if thr.shape != (n,) or alias.shape != (n,):
+            raise ValueError(f"NegPopTable: thr and alias hold one word per item of the range, {n}")
+        if (alias.astype(np.uint64) >= n).any():
+            raise ValueError(f"NegPopTable: an alias lies outside the table's slots [0, {n})")
+        self.neg_range, self.n, self.n_items = (lo, hi), n, n_items
+        self.thr, self.alias = thr.astype(np.uint32), alias.astype(np.uint32)
+        words = (self.alias.astype(np.uint64) << np.uint64(32)) | self.thr.astype(np.uint64)
+        self.table = torch.from_numpy(words.view(np.int64).copy()).to(device)
+        self.q = q
+        self.logq = None
+        if q is not None:
+            if q.shape != (n_items,) or not (q > 0).any():
+                raise ValueError("NegPopTable: q holds one float64 per item, some of them positive")
+            filled = np.where(q > 0, q, q[q > 0].min())
+            self.logq = np.log(filled).astype(np.float32)
+
+    def all_full(self) -> bool:
+        import numpy as np
+        return bool((self.alias == np.arange(self.n, dtype=np.uint32)).all())
+
+    def stats(self):
+        """-> (max q, entropy of q in nats, entropy of the uniform distribution over the range)."""
+        import numpy as np
+        q = self.q[self.q > 0]
+        return float(q.max()), float(-(q * np.log(q)).sum()), math.log(self.n)
+
+
+def _negpop_table(table, train_indptr, pop_matrix=None):
+    if not isinstance(table, NegPopTable):
+        raise ValueError("negative sampler: table is an ops.NegPopTable")
+    if table.table.device != train_indptr.device:
+        raise ValueError("negative sampler: the table lives on the device of the train CSR")
+    if pop_matrix is not None and (_need(pop_matrix, torch.float32, "pop_matrix").dim() != 2 or pop_matrix.shape[0] < table.neg_range[1]
+                                   or pop_matrix.shape[1] < 1):
+        raise ValueError("negative sampler: pop_matrix float32 [n_items, n_slots >= 1] covering the table's range")
+    return table.neg_range
+
+
+def negpop_sample_triplets(table, train_indptr, train_indices, B: int, *, seed: int, step: int, users=None, user_pool=None, n_pool: int = 0,
+                           train_slots=None, pop_matrix=None):
+    """pda_negpop_sample_triplets -> (users, pos, neg, pos_pop|None, neg_pop|None) on the device: sample_triplets with the negative drawn from
+    `table` (an ops.NegPopTable; its range is the neg_range).  The outputs are allocated zeroed -- the call writes every element, so this is
+    for the reader of a failed call only; the trainer's path is the _into calls on buffers of its own."""
+    lo, hi = _negpop_table(table, train_indptr, pop_matrix)
+    _need(train_indptr, torch.int64, "train_indptr"), _need(train_indices, torch.int32, "train_indices")
+    _need(train_slots, torch.int32, "train_slots", optional=True)
+    if int(B) < 1:
+        raise ValueError("negative sampler: B >= 1")
+    if user_pool is not None and _need(user_pool, torch.int32, "user_pool").numel() < int(n_pool):
+        raise ValueError("user_pool holds n_pool int32")
+    dev = train_indptr.device
+    gen = users is None
+    if gen:
+        if int(n_pool) < 1:
+            raise ValueError("negative sampler: drawing users needs n_pool >= 1")
+        users = torch.zeros(B, dtype=torch.int32, device=dev)
+    elif _need(users, torch.int32, "users").numel() != B:
+        raise ValueError("users holds B int32")
+    pos = torch.zeros(B, dtype=torch.int32, device=dev)
+    neg = torch.zeros(B, dtype=torch.int32, device=dev)
+    pp = pn = None
+    n_slots = 0
+    if pop_matrix is not None:
+        n_slots = pop_matrix.shape[1]
+        pp, pn = torch.zeros(B, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.float32, device=dev)
+    check(_lib.load().pda_negpop_sample_triplets(ptr(users), int(gen), ptr(user_pool), int(n_pool), int(B), ptr(train_indptr), ptr(train_indices),
+                                                 ptr(train_slots), lo, hi, ptr(table.table), ptr(pop_matrix), n_slots, seed & (2 ** 64 - 1),
+                                                 int(step) & (2 ** 64 - 1), ptr(pos), ptr(neg), ptr(pp), ptr(pn), stream_ptr()),
+          "pda_negpop_sample_triplets")
+    return users, pos, neg, pp, pn
+
+
+def _negpop_out(out, table, train_indptr, pop_matrix, dims: int):
+    """The (users, pos, neg, pos_pop|None, neg_pop|None) buffers of the _into calls, [B] (dims 1) or [n, B] (dims 2) each -> n_slots."""
+    users, pos, neg, pp, pn = out
+    users, pos, neg = _need(users, torch.int32, "users"), _need(pos, torch.int32, "pos"), _need(neg, torch.int32, "neg")
+    if users.dim() != dims or pos.shape != users.shape or neg.shape != users.shape or users.numel() < 1:
+        raise ValueError("negative sampler output: users, pos and neg of one shape")
+    if (pp is None) != (pn is None) or (pp is not None and pop_matrix is None):
+        raise ValueError("negative sampler output: pos_pop and neg_pop come together, and with a pop_matrix")
+    for t, name in ((pp, "pos_pop"), (pn, "neg_pop")):
+        if t is not None and _need(t, torch.float32, name).shape != users.shape:
+            raise ValueError(f"{name} has the shape of users")
+    if pop_matrix is not None and pp is None:
+        raise ValueError("negative sampler output: a pop_matrix needs pos_pop and neg_pop")
+    return pop_matrix.shape[1] if pop_matrix is not None else 0
+
+
+def negpop_sample_triplets_into(out, table, train_indptr, train_indices, *, seed: int, step_dev: torch.Tensor, parity: Optional[int] = None,
+                                user_pool=None, n_pool: int = 0, train_slots=None, pop_matrix=None):
+    """pda_negpop_sample_triplets_dev: one batch into out = (users, pos, neg, pos_pop|None, neg_pop|None), the step read from device memory
+    (graph-capturable; the users are drawn).  step_dev int64 [1]: read only; int64 [2] + parity p: slot p read, step + 1 stored to 1 - p."""
+    lo, hi = _negpop_table(table, train_indptr, pop_matrix)
+    n_slots = _negpop_out(out, table, train_indptr, pop_matrix, 1)
+    if int(n_pool) < 1:
+        raise ValueError("negative sampler: drawing users needs n_pool >= 1")
+    users, pos, neg, pp, pn = out
+    src, nxt = _step_slots(_need(step_dev, torch.int64, "step_dev"), parity)
+    check(_lib.load().pda_negpop_sample_triplets_dev(ptr(users), 1, ptr(user_pool), int(n_pool), users.numel(), ptr(train_indptr),
+                                                     ptr(train_indices), ptr(train_slots), lo, hi, ptr(table.table), ptr(pop_matrix), n_slots,
+                                                     seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(neg), ptr(pp), ptr(pn), stream_ptr()),
+          "pda_negpop_sample_triplets_dev")
+    return out
+
+
+def negpop_sample_batches_into(out, table, train_indptr, train_indices, *, seed: int, step_dev: torch.Tensor, parity: int, user_pool=None,
+                               n_pool: int = 0, train_slots=None, pop_matrix=None):
+    """pda_negpop_sample_batches_dev: sample_batches_into with the negatives drawn from `table`; out as [n, B] tensors, row j the batch of step
+    step_dev[parity] + j, step_dev[1 - parity] receives step + n."""
+    lo, hi = _negpop_table(table, train_indptr, pop_matrix)
+    n_slots = _negpop_out(out, table, train_indptr, pop_matrix, 2)
+    if _need(step_dev, torch.int64, "step_dev").numel() != 2 or parity not in (0, 1):
+        raise ValueError("negpop_sample_batches_into wants the two-slot step counter and parity 0 or 1")
+    if int(n_pool) < 1:
+        raise ValueError("negative sampler: drawing users needs n_pool >= 1")
+    users, pos, neg, pp, pn = out
+    n, B = users.shape
+    if not all(t is None or t.is_contiguous() for t in out):
+        raise ValueError("negative sampler output: contiguous [n, B] buffers")
+    check(_lib.load().pda_negpop_sample_batches_dev(ptr(users), 1, ptr(user_pool), int(n_pool), B, n, ptr(train_indptr), ptr(train_indices),
+                                                    ptr(train_slots), lo, hi, ptr(table.table), ptr(pop_matrix), n_slots, seed & (2 ** 64 - 1),
+                                                    ptr(step_dev[parity:parity + 1]), ptr(step_dev[1 - parity:2 - parity]), ptr(pos), ptr(neg),
+                                                    ptr(pp), ptr(pn), stream_ptr()), "pda_negpop_sample_batches_dev")
+    return out
+
+
+def negpop_ssm_sample(table, train_indptr, train_indices, B: int, N: int, *, seed: int, step: int, users=None, user_pool=None, n_pool: int = 0):
+    """pda_negpop_ssm_sample -> (users, pos, negs [B, N]) on the device: ssm_sample with the negatives drawn from `table`; column 0 is the
+    negative of negpop_sample_triplets."""
+    lo, hi = _negpop_table(table, train_indptr)
+    _ssm_sample_args(train_indptr, train_indices, B, N, (lo, hi), user_pool, n_pool)
+    dev = train_indptr.device
+    gen = users is None
+    if gen:
+        if int(n_pool) < 1:
+            raise ValueError("negative sampler: drawing users needs n_pool >= 1")
+        users = torch.zeros(B, dtype=torch.int32, device=dev)
+    elif _need(users, torch.int32, "users").numel() != B:
+        raise ValueError("users holds B int32")
+    pos = torch.zeros(B, dtype=torch.int32, device=dev)
+    negs = torch.zeros((B, N), dtype=torch.int32, device=dev)
+    check(_lib.load().pda_negpop_ssm_sample(ptr(users), int(gen), ptr(user_pool), int(n_pool), int(B), int(N), ptr(train_indptr), ptr(train_indices),
+                                            lo, hi, ptr(table.table), seed & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), ptr(pos), ptr(negs),
+                                            stream_ptr()), "pda_negpop_ssm_sample")
+    return users, pos, negs
+
+
+def negpop_ssm_sample_into(out, table, train_indptr, train_indices, *, seed: int, step_dev: torch.Tensor, parity: Optional[int] = None,
+                           user_pool=None, n_pool: int = 0):
+    """pda_negpop_ssm_sample_dev: one batch into out = (users [B], pos [B], negs [B, N]), the step read from device memory (ssm_sample_into)."""
+    lo, hi = _negpop_table(table, train_indptr)
+    users, pos, negs = out
+    users, pos, negs = _need(users, torch.int32, "users"), _need(pos, torch.int32, "pos"), _need(negs, torch.int32, "negs")
+    B = users.numel()
+    if pos.numel() != B or negs.dim() != 2 or negs.shape[0] != B:
+        raise ValueError("negative sampler output: users [B], pos [B], negs [B, N]")
+    _ssm_sample_args(train_indptr, train_indices, B, negs.shape[1], (lo, hi), user_pool, n_pool)
+    if int(n_pool) < 1:
+        raise ValueError("negative sampler: drawing users needs n_pool >= 1")
+    src, nxt = _step_slots(_need(step_dev, torch.int64, "step_dev"), parity)
+    check(_lib.load().pda_negpop_ssm_sample_dev(ptr(users), 1, ptr(user_pool), int(n_pool), B, int(negs.shape[1]), ptr(train_indptr),
+                                                ptr(train_indices), lo, hi, ptr(table.table), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos),
+                                                ptr(negs), stream_ptr()), "pda_negpop_ssm_sample_dev")
     return out
 
 

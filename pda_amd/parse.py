@@ -94,11 +94,12 @@ _EXTENSION_FLAGS = [
     ("dau_t", float, 2.0, "DirectAU: temperature t of the uniformity kernel exp(-t |x - y|^2) on the unit sphere, 0 < t <= 20"),
     ("dau_same", str, "keep", "DirectAU: pairs of batch rows that carry the same user (or the same item).  keep = they count, at distance 0 (a pairwise distance over the batch as it stands) | drop = they are left out of the uniformity mean"),
     ("dau_rank", str, "raw", "DirectAU: what the lists rank by.  raw = the dot product of the raw tables | cosine = of the row-normalised tables (the quantity the loss trained; the path --ssm_norm 1 takes)"),
-    ("neg_sampler", str, "uniform", "where a triplet's negative comes from: uniform = one uniform draw outside the user's train items (the reference) | dns = dynamic hard-negative sampling, DNS(M, N): one of the --dns_topn best-scoring of --dns_candidates uniform draws under the current tables (include/pda_hip_dns.h; --train normal | s_condition, fp32 tables, the device sampler, one GPU)"),
+    ("neg_sampler", str, "uniform", "where a triplet's negative comes from: uniform = one uniform draw outside the user's train items (the reference) | dns = dynamic hard-negative sampling, DNS(M, N): one of the --dns_topn best-scoring of --dns_candidates uniform draws under the current tables (include/pda_hip_dns.h; --train normal | s_condition, fp32 tables, the device sampler, one GPU) | pop = popularity-weighted negatives, q_i ~ (c_i + 1)^--neg_pop_power with c_i the item's train pairs, drawn through an alias table and rejected against the user's train items like the uniform draw (include/pda_hip_negpop.h; --train normal | s_condition | ssm with --ssm_source sampled, the device sampler, one GPU)"),
+    ("neg_pop_power", float, 0.75, "--neg_sampler pop: the power beta of q_i ~ (c_i + 1)^beta, 0 .. 4 (0: the uniform sampler's batches, bit for bit; 0.75: the unigram^0.75 of word2vec; 1: in proportion to popularity)"),
     ("dns_candidates", int, 16, "DNS (--neg_sampler dns): candidates M drawn and scored per triplet, 1 .. 256 (1: the uniform sampler's batches, bit for bit)"),
     ("dns_topn", int, 1, "DNS: the negative is drawn uniformly from the N best of the M candidates, 1 .. --dns_candidates (1: the best one, the classic DNS)"),
     ("ssm_source", str, "sampled", "SSM (--train ssm): where a row's negatives come from.  sampled = --ssm_negs uniform draws per row | batch = the other rows' positives (in-batch softmax, include/pda_hip_inbatch.h: --batch_size - 1 shared negatives per row, --batch_size in 2 .. 16384) | all = every item of the catalogue, no sampling (the exact softmax both estimate, include/pda_hip_fullsm.h: --batch_size in 1 .. 16384)"),
-    ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1; unused with --ssm_source all (nothing is sampled, so there is nothing to correct)"),
+    ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1; with --ssm_source sampled it acts under --neg_sampler pop (log q_i of the popularity proposal, the same convention) and is unused under --neg_sampler uniform, where the correction is a constant that cancels in the softmax; unused with --ssm_source all (nothing is sampled, so there is nothing to correct)"),
     ("ssm_mask_train", int, 1, "SSM with --ssm_source batch: 1 leaves a column out of a row's softmax when its item is a train item of the row's user (the sampled path rejects the same items when it draws); with --ssm_source all: 1 leaves the user's other train items out of the row's softmax over the catalogue, 0 keeps every item; 0 | 1"),
     ("ssm_negs", int, 64, "SSM (--train ssm): sampled negatives per row of the softmax, 1 .. 256; unused with --ssm_source batch and with --ssm_source all"),
     ("ssm_tau", float, 0.1, "SSM: the temperature tau of the logits, > 0"),

@@ -15,6 +15,8 @@ yielding, per step, a tuple of sequences of length batch_size -- (users, pos, ne
                      mode="ssm": the sampled-softmax batches (pda_ssm_sample_dev): (users, pos, negs [B, n_negs]).
                      mode="dns": the batches of mode="bpr" with the negative picked among the topn best-scoring of n_cands
                      uniform candidates under the model's live tables (pda_dns_sample_f32; set_tables).
+                     neg_table (mode="bpr" | "ssm"): an ops.NegPopTable; the negatives are drawn from its popularity proposal
+                     (pda_negpop_*) instead of uniformly, everything else about the batches stays.
     HostDiceSampler  PNSM in numpy, the debugging twin of mode="dice" (--sampler host): the same algorithm on the
                      host's random streams -- NOT draw for draw the device stream.
 """
@@ -107,11 +109,21 @@ class DeviceSampler:
     batch handed out is a row view of the queue and stays valid until `ahead` further batches have been taken."""
 
     def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0, mode: str = "bpr",
-                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0, n_cands: int = 0, topn: int = 1):
+                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0, n_cands: int = 0, topn: int = 1, neg_table=None):
         if mode not in ("bpr", "dice", "ssm", "dns"):
             raise ValueError("DeviceSampler mode must be 'bpr', 'dice', 'ssm' or 'dns', not %r" % (mode,))
         if mode == "dns":
             ops.check_dns_sizes(n_cands, topn, "mode='dns'")
+        if neg_table is not None:
+            if mode not in ("bpr", "ssm"):
+                raise ValueError("mode=%r draws its negatives its own way: a neg_table goes with mode='bpr' and mode='ssm' only" % (mode,))
+            if not isinstance(neg_table, ops.NegPopTable):
+                raise ValueError("neg_table is an ops.NegPopTable")
+            if neg_range is not None and tuple(int(x) for x in neg_range) != neg_table.neg_range:
+                raise ValueError("neg_range %r is not the range %r the neg_table was built for" % (tuple(neg_range), neg_table.neg_range))
+            if neg_range is None and neg_table.neg_range != (0, data.n_items):
+                raise ValueError("the neg_table covers %r, the sampler draws from (0, %d): pass the table's neg_range" % (neg_table.neg_range, data.n_items))
+        self.neg_table = neg_table
         self.n_cands, self.topn = int(n_cands), int(topn)
         self._tables = None           # mode="dns": set_tables
         if mode == "ssm":
@@ -172,16 +184,25 @@ class DeviceSampler:
         queue; bit for bit the batches of ops.ssm_sample(step = 1, 2, ..))."""
         self._next_queue([(torch.int32, ()), (torch.int32, ()), (torch.int32, (self.n_negs,))])
         for j in range(self.ahead):
-            ops.ssm_sample_into(tuple(q[j] for q in self._queue), self.indptr, self.indices, seed=self.seed, step_dev=self._ctr,
-                                parity=self._draws & 1, user_pool=self.pool, n_pool=self.pool.numel(), neg_range=self.neg_range)
+            if self.neg_table is not None:
+                ops.negpop_ssm_sample_into(tuple(q[j] for q in self._queue), self.neg_table, self.indptr, self.indices, seed=self.seed,
+                                           step_dev=self._ctr, parity=self._draws & 1, user_pool=self.pool, n_pool=self.pool.numel())
+            else:
+                ops.ssm_sample_into(tuple(q[j] for q in self._queue), self.indptr, self.indices, seed=self.seed, step_dev=self._ctr,
+                                    parity=self._draws & 1, user_pool=self.pool, n_pool=self.pool.numel(), neg_range=self.neg_range)
             self._draws += 1
 
     def _refill(self):
         pop_dt = torch.float32 if self.with_pop else None
         which = self._next_queue([(torch.int32, ())] * 3 + [(pop_dt, ())] * 2)
-        ops.sample_batches_into(self._queue, self.indptr, self.indices, seed=self.seed, step_dev=self._ctr, parity=which,
-                                user_pool=self.pool, n_pool=self.pool.numel(), train_slots=self.slots if self.with_pop else None,
-                                neg_range=self.neg_range, pop_matrix=self.pop)
+        if self.neg_table is not None:
+            ops.negpop_sample_batches_into(self._queue, self.neg_table, self.indptr, self.indices, seed=self.seed, step_dev=self._ctr,
+                                           parity=which, user_pool=self.pool, n_pool=self.pool.numel(),
+                                           train_slots=self.slots if self.with_pop else None, pop_matrix=self.pop)
+        else:
+            ops.sample_batches_into(self._queue, self.indptr, self.indices, seed=self.seed, step_dev=self._ctr, parity=which,
+                                    user_pool=self.pool, n_pool=self.pool.numel(), train_slots=self.slots if self.with_pop else None,
+                                    neg_range=self.neg_range, pop_matrix=self.pop)
         if self.with_plan:
             # the plans of the whole queue in ONE launch (one workgroup per batch), like the batches themselves
             if self._plans is None:
@@ -231,10 +252,15 @@ class DeviceSampler:
             self._left -= 1
             return tuple(q[j] for q in self._queue)
         if self.ahead == 1:
-            u, p, n, pp, pn = ops.sample_triplets(self.indptr, self.indices, self.data.batch_size, seed=self.seed,
-                                                  step=self.step, user_pool=self.pool, n_pool=self.pool.numel(),
-                                                  train_slots=self.slots if self.with_pop else None,
-                                                  neg_range=self.neg_range, pop_matrix=self.pop)
+            if self.neg_table is not None:
+                u, p, n, pp, pn = ops.negpop_sample_triplets(self.neg_table, self.indptr, self.indices, self.data.batch_size, seed=self.seed,
+                                                             step=self.step, user_pool=self.pool, n_pool=self.pool.numel(),
+                                                             train_slots=self.slots if self.with_pop else None, pop_matrix=self.pop)
+            else:
+                u, p, n, pp, pn = ops.sample_triplets(self.indptr, self.indices, self.data.batch_size, seed=self.seed,
+                                                      step=self.step, user_pool=self.pool, n_pool=self.pool.numel(),
+                                                      train_slots=self.slots if self.with_pop else None,
+                                                      neg_range=self.neg_range, pop_matrix=self.pop)
             self.plan = ops.triplet_plan(u, p, n)[0] if self.with_plan else None
             return (u, p, n, pp, pn) if self.with_pop else (u, p, n)
         if self._left == 0:

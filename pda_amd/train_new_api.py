@@ -31,7 +31,7 @@ from .exposure import BiasReport, EvalResult
 from .rank_report import RankReport
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
 from .model_api import (BPRMF, DAUMF, DICE, IALSMF, IPSBPRMF, MACRBPRMF, PCCBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dau, check_dice,
-                        check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_pcc, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
+                        check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_negpop, check_pcc, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
@@ -169,6 +169,9 @@ class DatasetApi_Model:
             #  the train mask and the logQ table come from the sampler's graph; a model that only ranks (export_topk) has no sampler
             if self.Recommender.ssm_source in ("batch", "all") and hasattr(generator_sampler, "indptr"):
                 self.Recommender.set_train_graph(generator_sampler.indptr, generator_sampler.indices, generator_sampler.pool)
+            #  the logQ table of a popularity proposal comes from the sampler's table
+            if self.Recommender.wants_neg_logq() and getattr(generator_sampler, "neg_table", None) is not None:
+                self.Recommender.set_neg_logq(torch.from_numpy(generator_sampler.neg_table.logq).to(self.device))
         elif args.train == "ials":
             # iALS: the tables of a BPRMF solved row by row; no batches, the trainer calls train_epoch()
             self.input_type = "without_pop"
@@ -596,6 +599,7 @@ def main(argv=None):
     elif args.model != "mf":
         raise NotImplementedError("--model %s: mf | lightgcn" % args.model)
     check_dns(args)                        # (--neg_sampler dns)
+    check_negpop(args)                     # (--neg_sampler pop)
     check_ials(args)                       # (--train ials | --test ials)
     if args.train == "dice":
         check_dice(args)
@@ -702,6 +706,10 @@ def main(argv=None):
     else:
         raise NotImplementedError("do not implement this method")               # :1008
 
+    neg_table = None
+    if getattr(args, "neg_sampler", "uniform") == "pop":         # (check_negpop has refused everything but the device sampler of normal | s_condition | ssm sampled)
+        neg_table = ops.NegPopTable(data.train_csr("cpu")[1], data.n_items, args.neg_pop_power, (0, data.n_items), device)
+        print("||--- neg_sampler pop power=%g max_q=%.6g entropy=%.5f (uniform: %.5f)" % ((neg_table.power,) + neg_table.stats()))
     if args.train == "ials":               # no sampler: every epoch is two half-sweeps over all pairs
         sampler = None
     elif args.train == "temp_pop":
@@ -720,11 +728,11 @@ def main(argv=None):
         if args.ssm_source in ("batch", "all"):    # in-batch negatives / the whole catalogue: the triplet sampler without popularity columns; its negative is ignored
             sampler = DeviceSampler(data, device, False)
         else:
-            sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs)
+            sampler = DeviceSampler(data, device, False, mode="ssm", n_negs=args.ssm_negs, neg_table=neg_table)
     elif getattr(args, "neg_sampler", "uniform") == "dns":       # (check_dns has refused everything but --train normal | s_condition on the device sampler)
         sampler = DeviceSampler(data, device, with_pop, mode="dns", n_cands=args.dns_candidates, topn=args.dns_topn)
     elif args.sampler == "device":
-        sampler = DeviceSampler(data, device, with_pop)
+        sampler = DeviceSampler(data, device, with_pop, neg_table=neg_table)
     else:
         sampler = (lambda: host_generator(data, with_pop))
     model = DatasetApi_Model(args, config, test_batch_size, sampler, device)

@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h, pda_hip_dau.h and pda_hip_negpop.h).
+pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h, pda_hip_dau.h, pda_hip_negpop.h and pda_hip_ialspp.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -335,6 +335,15 @@ NEGPOP_SIGNATURES = {
                                         _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_ialspp.h (iALS++: `--train ials --ials_solver block`)
+IALSPP_SIGNATURES = {
+    "pda_ialspp_predict_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _i, _vp, _vp]),
+    "pda_ialspp_block_pass_f32": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                       _vp, _sz, _vp]),
+    "pda_ialspp_gram_f32": (_i, [_vp, _sz, _i, _vp, _vp, _sz, _vp]),
+    "pda_ialspp_loss_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -357,7 +366,7 @@ def load():
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
             list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()) + \
             list(FULLSM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PCC_SIGNATURES.items()) + \
-            list(DAU_SIGNATURES.items()) + list(NEGPOP_SIGNATURES.items()):
+            list(DAU_SIGNATURES.items()) + list(NEGPOP_SIGNATURES.items()) + list(IALSPP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1480,6 +1480,7 @@ class ConditionalLightGCN(LightGCN):
 
 # ---- iALS (include/pda_hip_ials.h) ------------------------------------------------------------------------------------------------
 IALS_EMBED_SIZES = ops.IALS_EMBED_SIZES     # --embed_size of an iALS model: a d x d fp32 matrix has to fit the LDS (256 does not)
+IALS_SOLVERS = ("exact", "block")           # --ials_solver: the row-wise exact solve | iALS++ block steps (any of ops.IALSPP_EMBED_SIZES)
 
 
 def check_ials(args):
@@ -1500,7 +1501,18 @@ def check_ials(args):
     if getattr(args, "neg_sampler", "uniform") != "uniform":
         raise NotImplementedError("--neg_sampler %s: --train ials has no sampled negatives (every unobserved pair is weighed by --ials_alpha0)"
                                   % (args.neg_sampler,))
-    if int(args.embed_size) not in IALS_EMBED_SIZES:
+    solver = getattr(args, "ials_solver", "exact")
+    if solver not in IALS_SOLVERS:
+        raise ValueError("--ials_solver must be one of %s, got %s" % (" | ".join(IALS_SOLVERS), solver))
+    if solver == "block":
+        if int(args.embed_size) not in ops.IALSPP_EMBED_SIZES:
+            raise NotImplementedError("--embed_size %s: --train ials --ials_solver block takes one of %s" % (args.embed_size, ops.IALSPP_EMBED_SIZES))
+        k = int(getattr(args, "ials_block", 32))
+        if k not in ops.IALSPP_BLOCK_SIZES:
+            raise ValueError("--ials_block must be one of %s, got %s" % (ops.IALSPP_BLOCK_SIZES, args.ials_block))
+        if int(args.embed_size) % k:
+            raise ValueError("--ials_block %d does not divide --embed_size %s" % (k, args.embed_size))
+    elif int(args.embed_size) not in IALS_EMBED_SIZES:
         raise NotImplementedError("--embed_size %s: --train ials takes one of %s (a d x d fp32 matrix per row has to fit the LDS)"
                                   % (args.embed_size, IALS_EMBED_SIZES))
     if getattr(args, "test", "normal") not in ("normal", "ials"):
@@ -1523,7 +1535,9 @@ class IALSMF(BPRMF):
     evaluation and checkpoint are those of BPRMF (model "mf", no optimiser state): the two differ only in how they were trained.  There is no
     step: train_epoch() is the user half-sweep, the item half-sweep and the objective.  data_config["gcn_train_pairs"] = (users, items), or
     set_train_pairs: the train pairs -- rebuilt from the data, never stored in a checkpoint; a model that is only restored and evaluated
-    needs none."""
+    needs none.  --ials_solver block (iALS++, DESIGN.md 5v, include/pda_hip_ialspp.h) replaces the two half-sweeps by one exact step per block
+    of --ials_block coordinates, users then items, at --embed_size up to 256; the tables keep their usual initialisation, which matters there
+    (a block step starts from x), and the prediction cache is rebuilt every epoch and never checkpointed."""
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
         check_ials(args)
@@ -1536,6 +1550,8 @@ class IALSMF(BPRMF):
         self.adam_exact_lazy = False
         self.ials_alpha0 = float(getattr(args, "ials_alpha0", 0.1))
         self.ials_nu = float(getattr(args, "ials_nu", 1.0))
+        self.ials_solver = getattr(args, "ials_solver", "exact")
+        self.ials_block = int(getattr(args, "ials_block", 32))
         self.graph = None
         if data_config.get("gcn_train_pairs") is not None:
             self.set_train_pairs(*data_config["gcn_train_pairs"])
@@ -1553,15 +1569,21 @@ class IALSMF(BPRMF):
         if g is None:
             raise ValueError("IALSMF needs the train pairs before it trains (data_config['gcn_train_pairs'] or set_train_pairs)")
         X, Y = self.weights["user_embedding"], self.weights["item_embedding"]
+        if self.ials_solver == "block":     # iALS++: block steps from the tables as they stand -- their initialisation matters here
+            return ops.ialspp_epoch(g, X, Y, self.ials_block) / max(1, g.nnz)
         ops.ials_half_sweep(g, "user", Y, X)
         ops.ials_half_sweep(g, "item", X, Y)
         return ops.ials_loss(g, X, Y) / max(1, g.nnz)
 
     def failed_pivots(self) -> torch.Tensor:
         """The device int32 [1] count of rows written as NaN by a failed pivot since the model was built (0 on finite tables)."""
+        if self.ials_solver == "block":
+            return ops.ialspp_buffers(self.graph, self.emb_dim)["fail"]
         return self.graph.buffers(self.emb_dim)["fail"]
 
     def state_dict(self):
         sd = super().state_dict()
         sd.update(optimizer="ials", ials_alpha0=self.ials_alpha0, ials_nu=self.ials_nu)
+        if self.ials_solver == "block":     # (an exact-solver run's state dict stays as it was)
+            sd.update(ials_solver="block", ials_block=self.ials_block)
         return sd

@@ -3795,6 +3795,21 @@ class IalsGraph:
             raise ValueError(f"iALS: side must be 'user' or 'item', got {side!r}")
         return self.user if side == "user" else self.item
 
+    # the block solver's state (include/pda_hip_ialspp.h), built on first use: an exact-solver run never touches it
+    @property
+    def pair_perm(self):
+        """int64 [nnz] on the device: position in the item CSR -> position of the same pair in the user CSR."""
+        return ialspp_pair_perm(self)
+
+    @property
+    def e(self):
+        """The prediction cache of the block solver, float32 [nnz] in the user CSR's pair order."""
+        return ialspp_cache(self)
+
+    def blocks(self, d: int, k: int):
+        """The first coordinates of the d / k blocks, ascending."""
+        return ialspp_blocks(d, k)
+
     def buffers(self, d: int) -> dict:
         if d not in self._bufs:
             gram_slots = -(-max(self.n_users, self.n_items) // IALS_GRAM_ROWS)
@@ -3889,6 +3904,201 @@ def ials_loss(graph: IalsGraph, X, Y, *, G=None):
     fit = t[0] + graph.alpha0 * t[1]
     reg = t[2] + reg_items
     return torch.stack([fit + reg, fit, reg])
+
+
+# ---- iALS++ (include/pda_hip_ialspp.h): the block-wise solver of the same objective, on the same IalsGraph ------------------------------------------
+IALSPP_EMBED_SIZES = (32, 64, 128, 256)
+IALSPP_BLOCK_SIZES = (32, 64, 128)
+
+
+def ials_pair_perm(user_indptr, user_indices, item_indptr, item_indices):
+    """pair_perm int64 [nnz] on the host: position q of the item CSR -> position of the same pair in the user CSR (both CSRs hold the distinct
+    pairs, column ids ascending within a row, so the user CSR's keys u * n_items + i are ascending)."""
+    import numpy as np
+    n_users, n_items = len(user_indptr) - 1, len(item_indptr) - 1
+    ukey = np.repeat(np.arange(n_users, dtype=np.int64), np.diff(user_indptr)) * n_items + np.asarray(user_indices, dtype=np.int64)
+    ikey = np.asarray(item_indices, dtype=np.int64) * n_items + np.repeat(np.arange(n_items, dtype=np.int64), np.diff(item_indptr))
+    perm = np.searchsorted(ukey, ikey).astype(np.int64)
+    if perm.size and not (perm.max() < ukey.size and np.array_equal(ukey[perm], ikey)):
+        raise ValueError("iALS++: the two CSRs do not hold the same pairs")
+    return perm
+
+
+def ialspp_blocks(d: int, k: int):
+    """The first coordinates p0 of the d / k blocks of an iALS++ epoch, ascending."""
+    d, k = int(d), int(k)
+    if d not in IALSPP_EMBED_SIZES:
+        raise ValueError(f"iALS++: the embedding size is one of {IALSPP_EMBED_SIZES}, got {d}")
+    if k not in IALSPP_BLOCK_SIZES:
+        raise ValueError(f"iALS++: the block size is one of {IALSPP_BLOCK_SIZES}, got {k}")
+    if d % k:
+        raise ValueError(f"iALS++: the block size {k} does not divide the embedding size {d}")
+    return list(range(0, d, k))
+
+
+def _ialspp_state(graph: IalsGraph) -> dict:
+    """What the block solver keeps on an IalsGraph besides the exact solver's buffers, built on first use (an exact-solver run never comes
+    here): pair_perm, the prediction cache e and, per width, the Gram matrix, its workspace, the loss rows, the slots and the delta buffer.
+    Every buffer is a torch.zeros: none needs it (the kernels write what they read), and tests/test_gpu_ialspp.py proves that."""
+    st = graph.__dict__.get("_pp")
+    if st is None:
+        h = graph.host
+        perm = ials_pair_perm(h["user"]["indptr"], h["user"]["indices"], h["item"]["indptr"], h["item"]["indices"])
+        st = graph.__dict__["_pp"] = dict(pair_perm=torch.from_numpy(perm).to(graph.device), host_pair_perm=perm,
+                                          e=torch.zeros(max(1, graph.nnz), dtype=torch.float32, device=graph.device)[:graph.nnz],
+                                          fail=torch.zeros(1, dtype=torch.int32, device=graph.device))
+    return st
+
+
+def ialspp_pair_perm(graph: IalsGraph):
+    return _ialspp_state(graph)["pair_perm"]
+
+
+def ialspp_cache(graph: IalsGraph):
+    """The graph's prediction cache e, float32 [nnz] in the user CSR's pair order."""
+    return _ialspp_state(graph)["e"]
+
+
+def ialspp_buffers(graph: IalsGraph, d: int, k: Optional[int] = None) -> dict:
+    st = _ialspp_state(graph)
+    if ("d", d) not in st:
+        n = max(graph.n_users, graph.n_items)
+        st[("d", d)] = dict(G=torch.zeros((d, d), dtype=torch.float32, device=graph.device),
+                            gram_ws=torch.zeros(-(-n // IALS_GRAM_ROWS) * (d * d + d), dtype=torch.float32, device=graph.device),
+                            rows=torch.zeros((graph.n_users, 3), dtype=torch.float32, device=graph.device))
+    out = dict(st[("d", d)], fail=st["fail"], e=st["e"], pair_perm=st["pair_perm"])
+    if k is not None:
+        if ("k", k) not in st:
+            slots = max(1, graph.user.all_rows.n_slots, graph.item.all_rows.n_slots)
+            st[("k", k)] = dict(slots=torch.zeros(slots * (k * k + k), dtype=torch.float32, device=graph.device),
+                                delta=torch.zeros(slots * k, dtype=torch.float32, device=graph.device))
+        out.update(st[("k", k)])
+    return out
+
+
+def _ialspp_table(t, n_rows: int, what: str):
+    t = _need(t, torch.float32, what)
+    if t.dim() != 2 or t.shape[0] != n_rows or t.shape[1] not in IALSPP_EMBED_SIZES:
+        raise ValueError(f"iALS++: {what} is float32 [{n_rows}, d] with d one of {IALSPP_EMBED_SIZES}, got {tuple(t.shape)}")
+    return t
+
+
+def ialspp_gram(Z, G=None, workspace=None):
+    """pda_ialspp_gram_f32: G = Z^T Z, float32 [d, d], at the four embedding sizes; workspace float32 of one slot of d * d + d per block of
+    IALS_GRAM_ROWS rows."""
+    Z = _need(Z, torch.float32, "Z")
+    if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] not in IALSPP_EMBED_SIZES:
+        raise ValueError(f"iALS++: Z is float32 [n >= 1, d] with d one of {IALSPP_EMBED_SIZES}, got {tuple(Z.shape)}")
+    n, d = Z.shape
+    if G is None:
+        G = torch.zeros((d, d), dtype=torch.float32, device=Z.device)
+    if _need(G, torch.float32, "G").shape != (d, d):
+        raise ValueError("iALS++: G is float32 [d, d]")
+    need = -(-n // IALS_GRAM_ROWS) * (d * d + d)
+    if workspace is None:
+        workspace = torch.zeros(need, dtype=torch.float32, device=Z.device)
+    if _need(workspace, torch.float32, "workspace").numel() < need:
+        raise ValueError(f"iALS++: the Gram workspace holds {need} floats")
+    check(_lib.load().pda_ialspp_gram_f32(ptr(Z), n, d, ptr(G), ptr(workspace), workspace.numel(), stream_ptr()), "pda_ialspp_gram_f32")
+    return G
+
+
+def ialspp_predict(graph: IalsGraph, X, Y, e=None):
+    """pda_ialspp_predict_f32: e[p] = x_u(p) . y_i(p) for every pair of the user CSR (default: into the graph's own cache).  Returns e."""
+    X, Y = _ialspp_table(X, graph.n_users, "X"), _ialspp_table(Y, graph.n_items, "Y")
+    d = X.shape[1]
+    if Y.shape[1] != d:
+        raise ValueError("iALS++: X and Y share the embedding width")
+    e = ialspp_cache(graph) if e is None else _need(e, torch.float32, "e")
+    if e.dim() != 1 or e.numel() != graph.nnz:
+        raise ValueError(f"iALS++: e is float32 [{graph.nnz}]")
+    s = graph.user
+    check(_lib.load().pda_ialspp_predict_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(X), ptr(Y), graph.n_items, d,
+                                             ptr(e) if s.nnz else None, stream_ptr()), "pda_ialspp_predict_f32")
+    return e
+
+
+def ialspp_block_pass(graph: IalsGraph, side: str, Z, X, block: int, k: int, *, G=None, e=None, work: Optional[IalsWork] = None, dbg=None,
+                      fail_count=None, slots=None, delta_ws=None):
+    """pda_ialspp_block_pass_f32: one pass of the coordinate block [block * k, (block + 1) * k) over the rows of `work` (default: every row of
+    the side): x_{r,pi} <- the exact minimiser over the block, in place in X, and the rows' entries of the prediction cache e follow.  Z is the
+    other table, held fixed; G: Z^T Z (computed here when missing); e: the cache (default: the graph's own, which ialspp_predict fills).
+    dbg float32 [n_rows, k * k + k] receives (H, g) as they enter the factorisation.  slots / delta_ws: float32 scratch of n_slots * (k * k + k)
+    and n_slots * k floats (default: the graph's own).  Returns X."""
+    s = graph.side(side)
+    Z = _ialspp_table(Z, s.n_other, "Z (the table held fixed)")
+    X = _ialspp_table(X, s.n_rows, "X")
+    d = Z.shape[1]
+    if X.shape[1] != d or X.data_ptr() == Z.data_ptr():
+        raise ValueError("iALS++: X and Z are two tables of one width")
+    p0s = ialspp_blocks(d, k)
+    block = int(block)
+    if not 0 <= block < len(p0s):
+        raise ValueError(f"iALS++: block {block} is outside the {len(p0s)} blocks of d = {d}, k = {k}")
+    b = ialspp_buffers(graph, d, k)
+    if G is None:
+        G = ialspp_gram(Z, b["G"], b["gram_ws"])
+    if _need(G, torch.float32, "G").shape != (d, d):
+        raise ValueError("iALS++: G is float32 [d, d]")
+    e = b["e"] if e is None else _need(e, torch.float32, "e")
+    if e.dim() != 1 or e.numel() != graph.nnz:
+        raise ValueError(f"iALS++: e is float32 [{graph.nnz}]")
+    w = s.all_rows if work is None else work
+    if not isinstance(w, IalsWork):
+        raise TypeError("iALS++: work is an IalsWork of this side (IalsSide.sub_list)")
+    if dbg is not None and tuple(_need(dbg, torch.float32, "dbg").shape) != (s.n_rows, k * k + k):
+        raise ValueError(f"iALS++: dbg is float32 [{s.n_rows}, {k * k + k}]")
+    fail = b["fail"] if fail_count is None else _need(fail_count, torch.int32, "fail_count")
+    if fail.numel() < 1:
+        raise ValueError("iALS++: fail_count holds one int32")
+    slots = b["slots"] if slots is None else _need(slots, torch.float32, "slots")
+    delta_ws = b["delta"] if delta_ws is None else _need(delta_ws, torch.float32, "delta_ws")
+    if slots.numel() < w.n_slots * (k * k + k) or delta_ws.numel() < w.n_slots * k:
+        raise ValueError(f"iALS++: {w.n_slots} slots need {w.n_slots * (k * k + k)} and {w.n_slots * k} floats")
+    perm = b["pair_perm"] if side == "item" else None
+    check(_lib.load().pda_ialspp_block_pass_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, ptr(perm), s.n_rows, s.nnz, ptr(w.work), w.n_work,
+                                                ptr(w.long_rows) if w.n_long else None, w.n_long, w.n_slots, ptr(Z), s.n_other, ptr(G), d, k,
+                                                p0s[block], float(graph.alpha0), ptr(s.lam_row), ptr(X), ptr(e) if s.nnz else None, ptr(fail),
+                                                ptr(dbg), ptr(slots) if w.n_slots else None, slots.numel() if w.n_slots else 0,
+                                                ptr(delta_ws) if w.n_slots else None, delta_ws.numel() if w.n_slots else 0, stream_ptr()),
+          "pda_ialspp_block_pass_f32")
+    mark_modified(X)
+    return X
+
+
+def ialspp_loss(graph: IalsGraph, X, Y, *, G=None, rows=None):
+    """ials_loss at the four embedding sizes (pda_ialspp_loss_f32): float64 [3] on the device, (L, fit, reg), the predictions taken fresh from
+    the tables.  rows float32 [n_users, 3]: the per-row terms (default: the graph's own buffer)."""
+    X, Y = _ialspp_table(X, graph.n_users, "X"), _ialspp_table(Y, graph.n_items, "Y")
+    d = X.shape[1]
+    if Y.shape[1] != d:
+        raise ValueError("iALS++: X and Y share the embedding width")
+    b = ialspp_buffers(graph, d)
+    if G is None:
+        G = ialspp_gram(Y, b["G"], b["gram_ws"])
+    rows = b["rows"] if rows is None else _need(rows, torch.float32, "rows")
+    if tuple(rows.shape) != (graph.n_users, 3):
+        raise ValueError(f"iALS++: rows is float32 [{graph.n_users}, 3]")
+    s = graph.user
+    check(_lib.load().pda_ialspp_loss_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(X), ptr(Y), graph.n_items, ptr(G), d,
+                                          ptr(s.lam_row), ptr(rows), stream_ptr()), "pda_ialspp_loss_f32")
+    t = rows.double().sum(0)
+    reg_items = (graph.item.lam_row.double() * Y.double().square().sum(1)).sum()
+    fit = t[0] + graph.alpha0 * t[1]
+    reg = t[2] + reg_items
+    return torch.stack([fit + reg, fit, reg])
+
+
+def ialspp_epoch(graph: IalsGraph, X, Y, k: int):
+    """One iALS++ epoch on the tables (X, Y), in place: the prediction cache recomputed from the tables, then for each block in ascending
+    order the user pass (G = Y^T Y) and the item pass (G = X^T X), then the objective from the tables -> float64 [3] (L, fit, reg)."""
+    d = X.shape[1]
+    p0s = ialspp_blocks(d, k)
+    ialspp_predict(graph, X, Y)
+    for blk in range(len(p0s)):
+        ialspp_block_pass(graph, "user", Y, X, blk, k)
+        ialspp_block_pass(graph, "item", X, Y, blk, k)
+    return ialspp_loss(graph, X, Y)
 
 
 # ---- exact ranks of held-out items (include/pda_hip_rank.h) ---------------------------------------------------------------------------------

@@ -2113,6 +2113,114 @@ def xquad_rerank(cand_idx, cand_val, item_is_head, lam, K=50, variant="smooth", 
     return idx, val
 
 
+# ---- calibrated popularity (include/pda_hip_calib.h) ------------------------------------------------------------------------------------
+CALIB_MAX_G = _lib.CALIB_MAX_G
+CALIB_MAX_K = _lib.CALIB_MAX_K
+CALIB_MAX_N = _lib.CALIB_MAX_N
+CALIB_MAX_KS = _lib.CALIB_MAX_KS
+CALIB_DIVERGENCES = {"js": _lib.CALIB_JS, "kl": _lib.CALIB_KL}
+
+
+def _calib_groups(item_group, G, like=None):
+    item_group = _need(item_group, torch.uint8, "item_group")
+    if item_group.dim() != 1 or item_group.numel() < 1:
+        raise ValueError("item_group holds one byte per item of the catalogue")
+    if like is not None and item_group.device != like.device:
+        raise ValueError("item_group must live on the device of the lists")
+    if int(G) != G or not 2 <= int(G) <= CALIB_MAX_G:
+        raise ValueError(f"calibration takes 2 .. {CALIB_MAX_G} popularity groups, got {G}")
+    return item_group, int(G)
+
+
+def calib_profile(item_group, G, n_rows, users=None, hist: Optional[HistoryCSR] = None) -> torch.Tensor:
+    """pda_calib_profile -> int32 [n_rows, G]: the distinct history entries of each row per popularity group.  item_group uint8 [n_items]
+    (0 = the most popular; a byte >= G: no group).  hist by user id: `users` int32 [n_rows] is needed; by block row: row r of the CSR is row r;
+    None (or an empty history): all zeros."""
+    lib = _lib.load()
+    item_group, G = _calib_groups(item_group, G)
+    users = _need(users, torch.int32, "users", optional=True)
+    n_rows = int(n_rows)
+    if n_rows < 1:
+        raise ValueError("empty user block")
+    if users is not None and users.numel() != n_rows:
+        raise ValueError("users holds one id per row")
+    if hist is not None and hist.indices.numel() == 0:
+        hist = None
+    if hist is not None:
+        if hist.mode == HIST_BY_USER_ID and users is None:
+            raise ValueError("a history by user id needs `users`")
+        if hist.mode == HIST_BY_BLOCK_ROW and hist.indptr.numel() < n_rows + 1:
+            raise ValueError("a history by block row holds one row per profile row")
+    prof = torch.zeros((n_rows, G), dtype=torch.int32, device=item_group.device)
+    check(lib.pda_calib_profile(ptr(users), ptr(hist.indptr) if hist else None, ptr(hist.indices) if hist else None, hist.mode if hist else 0,
+                                n_rows, ptr(item_group), item_group.numel(), G, ptr(prof), stream_ptr()), "pda_calib_profile")
+    return prof
+
+
+def calib_ks(Ks, K) -> Tuple[int, ...]:
+    """The cut-offs of pda_calib_list_counts, checked: 1 .. CALIB_MAX_KS integers, strictly ascending inside 1 .. K."""
+    ks = tuple(int(k) for k in Ks)
+    if not 1 <= len(ks) <= CALIB_MAX_KS:
+        raise ValueError(f"list counts take 1 .. {CALIB_MAX_KS} cut-offs, got {len(ks)}")
+    if ks[0] < 1 or ks[-1] > int(K) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"the cut-offs must ascend strictly inside 1 .. {int(K)} (the columns of the lists), got {list(ks)}")
+    return ks
+
+
+def calib_list_counts(idx, item_group, G, Ks) -> torch.Tensor:
+    """pda_calib_list_counts -> int32 [n_rows, len(Ks), G]: the entries of each group among the first Ks[j] columns of idx int32 [n_rows, K]
+    (an empty slot, an id outside the catalogue and an item of no group count nowhere)."""
+    lib = _lib.load()
+    idx = _need(idx, torch.int32, "idx")
+    if idx.dim() != 2 or idx.shape[0] < 1 or not 1 <= idx.shape[1] <= CALIB_MAX_N:
+        raise ValueError(f"idx must be int32 [n_rows >= 1, 1 .. {CALIB_MAX_N}], got {tuple(idx.shape)}")
+    item_group, G = _calib_groups(item_group, G, idx)
+    ks = calib_ks(Ks, idx.shape[1])
+    cnt = torch.zeros((idx.shape[0], len(ks), G), dtype=torch.int32, device=idx.device)
+    check(lib.pda_calib_list_counts(ptr(idx), idx.shape[0], idx.shape[1], ptr(item_group), item_group.numel(), G, (C.c_int32 * len(ks))(*ks),
+                                    len(ks), ptr(cnt), stream_ptr()), "pda_calib_list_counts")
+    return cnt
+
+
+def calib_rerank(cand_idx, cand_val, prof, item_group, G, lam, K=50, div="js", alpha=0.01):
+    """pda_calib_rerank: the calibrated greedy selection of K out of each row's N candidates -> (idx int32 [Bu, K], val float32 [Bu, K] = x at
+    the pick, div float32 [Bu, K] = the divergence of the list's first t + 1 items from the profile, on the 2^-20 grid).  cand_idx int32
+    [Bu, N], cand_val float32 [Bu, N]: what every recommend_* call returns (best first; -1 / -inf behind a short row).  prof int32 [Bu, G]:
+    calib_profile (all zeros: the candidates' order stays).  div: 'js' (log2) or 'kl' (the list smoothed by alpha)."""
+    lib = _lib.load()
+    cand_idx = _need(cand_idx, torch.int32, "cand_idx")
+    cand_val = _need(cand_val, torch.float32, "cand_val")
+    prof = _need(prof, torch.int32, "prof")
+    if cand_idx.dim() != 2 or cand_idx.shape != cand_val.shape:
+        raise ValueError("cand_idx and cand_val must be [Bu, N], the same shape")
+    item_group, G = _calib_groups(item_group, G, cand_idx)
+    if cand_val.device != cand_idx.device or prof.device != cand_idx.device:
+        raise ValueError("cand_idx, cand_val, prof and item_group must live on one device")
+    nu, N = cand_idx.shape
+    K = int(K)
+    if nu < 1:
+        raise ValueError("empty user block")
+    if tuple(prof.shape) != (nu, G):
+        raise ValueError(f"prof must be int32 [Bu = {nu}, G = {G}], got {tuple(prof.shape)}")
+    if not 1 <= N <= CALIB_MAX_N:
+        raise ValueError(f"calibration takes 1 .. {CALIB_MAX_N} candidates per user, got {N}")
+    if not 1 <= K <= min(CALIB_MAX_K, N):
+        raise ValueError(f"calibration needs 1 <= K <= min({CALIB_MAX_K}, N = {N}), got {K}")
+    lam, alpha = float(lam), float(alpha)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda must lie in [0, 1], got {lam}")
+    if div not in CALIB_DIVERGENCES:
+        raise ValueError(f"div must be 'js' or 'kl', not {div!r}")
+    if div == "kl" and not 0.0 < alpha < 1.0:
+        raise ValueError(f"alpha must lie strictly inside 0 .. 1, got {alpha}")
+    idx = torch.full((nu, K), -1, dtype=torch.int32, device=cand_idx.device)
+    val = torch.full((nu, K), float("-inf"), dtype=torch.float32, device=cand_idx.device)
+    dv = torch.full((nu, K), float("-inf"), dtype=torch.float32, device=cand_idx.device)
+    check(lib.pda_calib_rerank(ptr(cand_idx), ptr(cand_val), nu, N, ptr(prof), ptr(item_group), item_group.numel(), G, lam,
+                               CALIB_DIVERGENCES[div], alpha, K, ptr(idx), ptr(val), ptr(dv), stream_ptr()), "pda_calib_rerank")
+    return idx, val, dv
+
+
 # ---- item exposure of the lists (include/pda_hip_exposure.h) ------------------------------------------------------------------------------
 EXPOSURE_MAX_KS = _lib.EXPOSURE_MAX_KS
 EXPOSURE_MAX_COLS = _lib.EXPOSURE_MAX_COLS

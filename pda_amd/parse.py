@@ -79,6 +79,11 @@ _EXTENSION_FLAGS = [
     ("xq_candidates", int, 1000, "xQuAD: candidates per user the re-ranking selects from, max(Ks) .. 1024 (above 54 they come from the deep path)"),
     ("xq_head_share", float, 0.8, "xQuAD: the short head is the most popular items that hold this share of the train interactions, strictly inside 0 .. 1"),
     ("xq_variant", str, "smooth", "xQuAD: smooth | binary"),
+    ("cp_lambda", float, 0.5, "calibrated popularity (python -m pda_amd.calib): weight lambda of the divergence between the list's and the user's popularity mix, 0 .. 1 (0 leaves the ranking it re-ranks)"),
+    ("cp_candidates", int, 1000, "calibrated popularity: candidates per user the re-ranking selects from, max(Ks) .. 1024, cut to the catalogue's size (above 54 they come from the deep path)"),
+    ("cp_cuts", str, "[0.2,0.8]", "calibrated popularity: the popularity groups, a list literal of up to 7 strictly increasing cuts inside 0 .. 1 -- shares of the train interactions, the items taken from the most popular down (the default: head, mid and tail)"),
+    ("cp_div", str, "js", "calibrated popularity: js = Jensen-Shannon divergence, log2 (Abdollahpouri et al., UMAP 2021) | kl = KL divergence from the list smoothed by --cp_alpha (Steck, RecSys 2018)"),
+    ("cp_alpha", float, 0.01, "calibrated popularity (--cp_div kl): the share alpha of the profile mixed into the list's distribution, strictly inside 0 .. 1"),
     ("bias_report", int, 0, "1: after every metrics line, `||--- bias@K` lines on what the lists do to popularity bias -- recommendation rate, hit share and recall per popularity group, ARP, coverage, Gini, APLT (pda_amd/exposure.py; the head of APLT is --xq_head_share); one GPU; 0 | 1"),
     ("bias_groups", int, 10, "--bias_report: popularity groups of the items, 1 .. 64 (group 0 = the most popular)"),
     ("bias_group_by", str, "interactions", "--bias_report: interactions = groups of equal train interactions | items = groups of equal item counts"),

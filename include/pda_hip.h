@@ -454,7 +454,10 @@ int pda_adam_step_f32(float* U, float* mU, float* vU, float* gU, int32_t* tagU, 
 /* ------------------------------------------------------------------------------------------------
  * Ranking metrics (A8; replaces get_performance + the Pool(5) reduction, MF/used_metric.py:4-80,
  * MF/train_new_api.py:741-778).   topk i32 [n_rows, k_cols]; targets as CSR by block row;
- * Ks i32 [n_ks] (device);  sums f64 [4, n_ks] = precision, recall, ndcg, hit -- ADDED to (not divided).
+ * Ks i32 [n_ks] (device), every one >= 1 (not checked: check them on the host), in any order, repeats allowed;
+ * sums f64 [4, n_ks] = precision, recall, ndcg, hit -- ADDED to (not divided).  k_cols 1 .. 64.
+ * Where the reference is undefined: a K beyond k_cols is cut to k_cols (in the divisor of precision and in the ideal
+ * DCG too), and a row without targets adds zero to all four sums.  tests/metrics_ref.py states both and why.
  * ------------------------------------------------------------------------------------------------ */
 int pda_metrics(const int32_t* topk, int n_rows, int k_cols, const int64_t* tgt_indptr, const int32_t* tgt_indices,
                 const int32_t* Ks, int n_ks, double* sums, void* stream);

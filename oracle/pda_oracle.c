@@ -152,17 +152,20 @@ void oracle_scores_chain(const float* U, const float* I, const int32_t* users, i
 }
 
 /* Ranking metrics from a top-K matrix and a target CSR: MF/used_metric.py:4-80 and the
- * reduction of MF/train_new_api.py:741-778.  sums[4][nK] = precision, recall, ndcg, hit (NOT yet /tot_user). */
+ * reduction of MF/train_new_api.py:741-778.  sums[4][nK] = precision, recall, ndcg, hit (NOT yet /tot_user).
+ * Where the reference is undefined this follows the kernels (tests/metrics_ref.py): a K beyond Kcols is cut to Kcols, in the divisor of
+ * precision and in the ideal DCG too, and a row without targets adds zero to all four. */
 void oracle_metrics(const int32_t* topk, int n_rows, int Kcols, const int64_t* tgt_indptr, const int32_t* tgt_indices,
                     const int32_t* Ks, int nK, double* sums) {
     for (int i = 0; i < 4 * nK; ++i) sums[i] = 0.0;
     for (int r = 0; r < n_rows; ++r) {
         int64_t b = tgt_indptr[r], e = tgt_indptr[r + 1];
         int npos = (int)(e - b);
+        if (npos == 0) continue;
         for (int q = 0; q < nK; ++q) {
-            int K = Ks[q];
+            int K = Ks[q] < Kcols ? Ks[q] : Kcols;
             double hits = 0, dcg = 0, idcg = 0;
-            for (int k = 0; k < K && k < Kcols; ++k) {
+            for (int k = 0; k < K; ++k) {
                 int it = topk[(size_t)r * Kcols + k], h = 0;
                 for (int64_t p = b; p < e; ++p) if (tgt_indices[p] == it) { h = 1; break; }
                 hits += h;

@@ -268,21 +268,22 @@ def get_performance(user_pos_test, r, Ks):
     hit vector = isin(r, target) (used_metric.py:65-67); precision = mean(hit[:K]) (:4-18);
     recall = sum(hit[:K])/len(target) (:55-57); ndcg = sum(hit[:K]/log2(2..K+1)) /
     sum_{j<min(len(target),K)} 1/log2(j+2), 0 when the ideal is 0 (:39-52);
-    hit = min(1, sum(hit[:K])) (:60-62).  len(target)==0 divides by zero like the reference.
+    hit = min(1, sum(hit[:K])) (:60-62).  Where the reference is undefined this follows the kernels (tests/metrics_ref.py):
+    K > len(r) is cut to len(r), in the ideal DCG too (the reference raises there), and len(target) == 0 gives zeros (the
+    reference: recall 0/0).
     """
     hit = np.isin(np.asarray(r), np.asarray(list(user_pos_test))).astype(np.float64)
     n_pos = len(user_pos_test)
     prec, rec, ndcg, hr = [], [], [], []
-    with np.errstate(divide="ignore", invalid="ignore"):
-        for K in Ks:
-            assert K >= 1
-            h = hit[:K]
-            prec.append(np.mean(h))
-            rec.append(np.sum(h) / n_pos)
-            tp = 1.0 / np.log2(np.arange(2, K + 2))
-            dcg_max = tp[:min(n_pos, K)].sum()
-            ndcg.append(0.0 if not dcg_max else (h * tp[:h.size]).sum() / dcg_max)
-            hr.append(min(1.0, np.sum(h)))
+    for K in Ks:
+        assert K >= 1
+        h = hit[:K]
+        prec.append(np.mean(h))
+        rec.append(np.sum(h) / n_pos if n_pos else 0.0)
+        tp = 1.0 / np.log2(np.arange(2, h.size + 2))
+        dcg_max = tp[:n_pos].sum()
+        ndcg.append(0.0 if not dcg_max else (h * tp).sum() / dcg_max)
+        hr.append(min(1.0, np.sum(h)))
     return {"recall": np.array(rec), "precision": np.array(prec),
             "ndcg": np.array(ndcg), "hit_ratio": np.array(hr)}
 

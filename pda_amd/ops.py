@@ -1401,12 +1401,28 @@ def adam_lazy_sync(st: LazyAdamState, U, mU, vU, I, mI, vI, t: int):
     st.synced = t
 
 
+def _metrics_targets(tgt_indices):
+    """The target entries of a metrics call.  A block in which no row has a target is an empty tensor, whose null pointer the library refuses:
+    it gets one entry that no row reads, and the kernel adds the zeros such rows add."""
+    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    return tgt_indices if tgt_indices.numel() else tgt_indices.new_zeros(1)
+
+
+def metrics_route(k_cols: int, ordered: bool = False):
+    """The entry point that reduces lists of k_cols columns: pda_metrics keeps a 64-bit hit mask, so up to _lib.MAX_K columns go to
+    metrics_sums / metrics_sums_ordered and longer lists (--topk_max) to the deep pair."""
+    if k_cols > _lib.MAX_K:
+        return metrics_sums_deep_ordered if ordered else metrics_sums_deep
+    return metrics_sums_ordered if ordered else metrics_sums
+
+
 def metrics_sums(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """pda_metrics: float64 [4, len(Ks)] sums of precision, recall, ndcg, hit over the rows (added to `sums`)."""
+    """pda_metrics: float64 [4, len(Ks)] sums of precision, recall, ndcg, hit over the rows (added to `sums`).  Ks: int32 on the device, every
+    one >= 1 (used_metric.check_ks checks them while they are a host list: the kernel divides by min(K, columns))."""
     lib = _lib.load()
     topk = _need(topk, torch.int32, "topk")
     tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
-    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    tgt_indices = _metrics_targets(tgt_indices)
     Ks = _need(Ks, torch.int32, "Ks")
     if sums is None:
         sums = torch.zeros((4, Ks.numel()), dtype=torch.float64, device=topk.device)
@@ -1423,7 +1439,7 @@ def metrics_sums_ordered(topk, tgt_indptr, tgt_indices, Ks, sums: Optional[torch
     lib = _lib.load()
     topk = _need(topk, torch.int32, "topk")
     tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
-    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    tgt_indices = _metrics_targets(tgt_indices)
     Ks = _need(Ks, torch.int32, "Ks")
     if sums is None:
         sums = torch.zeros((4, Ks.numel()), dtype=torch.float64, device=topk.device)
@@ -2034,7 +2050,7 @@ def _metrics_deep(topk, tgt_indptr, tgt_indices, Ks, sums, ordered: bool):
     lib = _lib.load()
     topk = _need(topk, torch.int32, "topk")
     tgt_indptr = _need(tgt_indptr, torch.int64, "tgt_indptr")
-    tgt_indices = _need(tgt_indices, torch.int32, "tgt_indices")
+    tgt_indices = _metrics_targets(tgt_indices)
     Ks = _need(Ks, torch.int32, "Ks")
     if not 1 <= topk.shape[1] <= DEEP_MAX_K:
         raise ValueError(f"deep metrics take lists of 1 .. {DEEP_MAX_K} columns, got {topk.shape[1]}")

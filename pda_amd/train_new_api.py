@@ -33,6 +33,7 @@ from .load_data import Data, Data2, get_popularity_from_load, load_popularity
 from .model_api import (BPRMF, DAUMF, DICE, IALSMF, IPSBPRMF, MACRBPRMF, PCCBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dau, check_dice,
                         check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_negpop, check_pcc, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
+from .used_metric import check_ks
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
 
 # module-level singletons of the reference (MF/batch_test.py:6-19), filled by configure()/main()
@@ -424,7 +425,7 @@ class DatasetApi_Model:
 class evaluation:
     def __init__(self, data_=None, Ks_=None, device=None, block=None):
         self.data = data_ if data_ is not None else data
-        self.Ks = list(Ks_ if Ks_ is not None else Ks)
+        self.Ks = check_ks(Ks_ if Ks_ is not None else Ks)     # (a K < 1 would divide by zero in the metrics kernels)
         self.device = torch.device(device if device is not None else "cuda")
         self.batch_size = block or (getattr(args, "eval_block", 262144) if args is not None else 262144)
         self.testing_popularity = None
@@ -510,10 +511,7 @@ class evaluation:
             tptr = torch.from_numpy(tp - tp[0]).to(self.device)
             # --deterministic 1: the ordered reduction -- recall decides the early stop and the best checkpoint with `>=`
             det = int(getattr(args, "deterministic", 0) or 0)
-            if idx.shape[1] > ops._lib.MAX_K:   # (--topk_max: pda_metrics keeps a 64-bit hit mask)
-                reduce = ops.metrics_sums_deep_ordered if det else ops.metrics_sums_deep
-            else:
-                reduce = ops.metrics_sums_ordered if det else ops.metrics_sums
+            reduce = ops.metrics_route(idx.shape[1], ordered=bool(det))   # (--topk_max: lists beyond 64 columns go to the deep pair)
             tgt = self.tgt_indices[int(tp[0]):int(tp[-1])]
             reduce(idx, tptr, tgt, ks, sums)
             if acc is not None:

@@ -352,20 +352,26 @@ def test_a_batch_with_a_user_twice_is_rejected_and_nothing_moves(dev, B, call):
 # ---- 7. metrics ----------------------------------------------------------------------------------------------------------------------
 def test_ordered_metrics_meet_the_reference_vectors(dev):
     from pda_amd import ops
-    cases = [c for c in json.load(open(os.path.join(G, "metrics.json"))) if len(c["r"]) == 50]
-    assert len(cases) >= 10
-    for Ks in ([20, 50], [1, 5, 10, 50]):
-        sub = [c for c in cases if c["Ks"] == Ks]
-        assert sub
+    cases = json.load(open(os.path.join(G, "metrics.json")))
+    assert len(cases) >= 11
+    groups = sorted({(len(c["r"]), tuple(c["Ks"])) for c in cases})           # every list length: one call per (length, cut-offs)
+    assert {(50, (20, 50)), (50, (1, 5, 10, 50))} < set(groups)
+    done = 0
+    for k_cols, Ks in groups:
+        sub = [c for c in cases if len(c["r"]) == k_cols and tuple(c["Ks"]) == Ks]
+        done += len(sub)
         topk = torch.tensor([c["r"] for c in sub], dtype=torch.int32, device=dev)
         indptr = np.zeros(len(sub) + 1, np.int64)
         indptr[1:] = np.cumsum([len(c["target"]) for c in sub])
         flat = np.concatenate([np.asarray(c["target"], np.int32) for c in sub])
-        sums = ops.metrics_sums_ordered(topk, torch.from_numpy(indptr).to(dev), torch.from_numpy(flat).to(dev),
-                                        torch.tensor(Ks, dtype=torch.int32, device=dev)).cpu().numpy()
+        reduce = ops.metrics_route(k_cols, ordered=True)                      # (lists beyond 64 columns: the deep kernel's ordered sums)
+        assert reduce is (ops.metrics_sums_ordered if k_cols <= 64 else ops.metrics_sums_deep_ordered)
+        sums = reduce(topk, torch.from_numpy(indptr).to(dev), torch.from_numpy(flat).to(dev),
+                      torch.tensor(Ks, dtype=torch.int32, device=dev)).cpu().numpy()
         for row, k in enumerate(("precision", "recall", "ndcg", "hit_ratio")):
             ref = np.sum([c["out"][k] for c in sub], axis=0)
             np.testing.assert_allclose(sums[row], ref, rtol=1e-12, err_msg=k)
+    assert done == len(cases)
 
 
 def test_ordered_metrics_equal_the_atomic_ones_and_repeat_bit_for_bit(dev):
@@ -373,7 +379,7 @@ def test_ordered_metrics_equal_the_atomic_ones_and_repeat_bit_for_bit(dev):
     rng = np.random.default_rng(4)
     n, K, nI = 100000, 50, 1000
     topk = torch.from_numpy(np.argsort(rng.random((n, 64)), axis=1)[:, :K].astype(np.int32) * 15 + rng.integers(0, 15, (n, 1)).astype(np.int32)).to(dev)
-    lens = rng.integers(0, 11, n)                                   # (users without targets count as zero, like the reference)
+    lens = rng.integers(0, 11, n)                                   # (users without targets add zero: tests/metrics_ref.py; the reference's recall there is 0/0)
     indptr = np.zeros(n + 1, np.int64)
     indptr[1:] = np.cumsum(lens)
     flat = rng.integers(0, nI, int(indptr[-1])).astype(np.int32)

@@ -23,20 +23,25 @@ G = os.path.join(os.path.dirname(__file__), "golden")
 
 def test_reference_metric_vectors_through_the_device_kernel(dev):
     from pda_amd import ops
-    cases = [c for c in json.load(open(os.path.join(G, "metrics.json"))) if len(c["r"]) == 50]
-    assert len(cases) >= 10
-    for Ks in ([20, 50], [1, 5, 10, 50]):
-        sub = [c for c in cases if c["Ks"] == Ks]
-        assert sub
+    cases = json.load(open(os.path.join(G, "metrics.json")))
+    assert len(cases) >= 11
+    groups = sorted({(len(c["r"]), tuple(c["Ks"])) for c in cases})           # every list length: one call per (length, cut-offs)
+    assert {(50, (20, 50)), (50, (1, 5, 10, 50))} < set(groups)
+    done = 0
+    for k_cols, Ks in groups:
+        sub = [c for c in cases if len(c["r"]) == k_cols and tuple(c["Ks"]) == Ks]
+        done += len(sub)
         topk = torch.tensor([c["r"] for c in sub], dtype=torch.int32, device=dev)
         indptr = np.zeros(len(sub) + 1, np.int64)
         indptr[1:] = np.cumsum([len(c["target"]) for c in sub])
         flat = np.concatenate([np.asarray(c["target"], np.int32) for c in sub])
-        sums = ops.metrics_sums(topk, torch.from_numpy(indptr).to(dev), torch.from_numpy(flat).to(dev),
-                                torch.tensor(Ks, dtype=torch.int32, device=dev)).cpu().numpy()
+        assert ops.metrics_route(k_cols) is (ops.metrics_sums if k_cols <= 64 else ops.metrics_sums_deep)   # (longer lists: the deep kernel)
+        sums = ops.metrics_route(k_cols)(topk, torch.from_numpy(indptr).to(dev), torch.from_numpy(flat).to(dev),
+                                         torch.tensor(Ks, dtype=torch.int32, device=dev)).cpu().numpy()
         for row, k in enumerate(("precision", "recall", "ndcg", "hit_ratio")):
             ref = np.sum([c["out"][k] for c in sub], axis=0)
             np.testing.assert_allclose(sums[row], ref, rtol=1e-12, err_msg=k)
+    assert done == len(cases)
 
 
 def gapped_case(seed, nU, nI, d, K, head, gap=1e-4):

@@ -32,9 +32,11 @@ def test_get_performance_matches_reference_golden(impl):
 
 
 def test_c_metrics_match_reference_golden():
-    cases = [c for c in jload("metrics.json") if len(c["r"]) == 50]
-    for Ks in ([20, 50], [1, 5, 10, 50]):
-        sub = [c for c in cases if c["Ks"] == Ks]
+    cases = jload("metrics.json")
+    groups = sorted({(len(c["r"]), tuple(c["Ks"])) for c in cases})           # every list length: one call per (length, cut-offs)
+    assert {(50, (20, 50)), (50, (1, 5, 10, 50))} < set(groups)
+    for k_cols, Ks in groups:
+        sub = [c for c in cases if len(c["r"]) == k_cols and tuple(c["Ks"]) == Ks]
         topk = np.array([c["r"] for c in sub], dtype=np.int32)
         indptr = np.zeros(len(sub) + 1, np.int64)
         indptr[1:] = np.cumsum([len(c["target"]) for c in sub])

@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h, pda_hip_dau.h, pda_hip_negpop.h, pda_hip_ialspp.h and pda_hip_calib.h).
+pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h, pda_hip_dau.h, pda_hip_negpop.h, pda_hip_ialspp.h, pda_hip_calib.h and pda_hip_warp.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -356,6 +356,16 @@ CALIB_SIGNATURES = {
     "pda_calib_rerank": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_warp.h (the WARP loss: `--train warp`)
+WARP_MAX_TRIALS = 256
+_warp_head = [_vp, _vp, _sz, _sz, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _u64]
+WARP_SIGNATURES = {
+    "pda_warp_sample_f32": (_i, _warp_head + [_u64] + [_vp] * 11),
+    "pda_warp_sample_f32_dev": (_i, _warp_head + [_vp, _vp] + [_vp] * 11),
+    "pda_warp_step_f32": (_i, [_vp, _vp, _sz, _sz] + [_vp] * 4 + [_f, _i, _i, _f, _f] + [_vp] * 4 + [_i, _i, _vp, _vp]),
+    "pda_warp_adam_step_f32": (_i, [_vp] * 5 + [_sz] + [_vp] * 5 + [_sz] + [_vp] * 4 + [_f, _i, _i, _f, _f, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -378,7 +388,8 @@ def load():
             list(IPS_SIGNATURES.items()) + list(MACR_SIGNATURES.items()) + list(GCN_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) + \
             list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()) + \
             list(FULLSM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PCC_SIGNATURES.items()) + \
-            list(DAU_SIGNATURES.items()) + list(NEGPOP_SIGNATURES.items()) + list(IALSPP_SIGNATURES.items()) + list(CALIB_SIGNATURES.items()):
+            list(DAU_SIGNATURES.items()) + list(NEGPOP_SIGNATURES.items()) + list(IALSPP_SIGNATURES.items()) + list(CALIB_SIGNATURES.items()) + \
+            list(WARP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

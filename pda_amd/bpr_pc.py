@@ -179,8 +179,8 @@ def main(argv=None):
     load_popularity(args)                                                        # the reference reads it first (:1243)
 
     regs_pretain = args.regs
-    if args.model == "mf" and args.train in ("normal", "dice", "ips", "ssm", "ials", "pcc", "dau"):    # :1272-1284 (a DICE, IPS or SSM checkpoint ranks by the raw head too)
-        args.saveID += "pop_exp-{:.2f}".format(popularity_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau"}.get(args.train, "")
+    if args.model == "mf" and args.train in ("normal", "dice", "ips", "ssm", "ials", "pcc", "dau", "warp"):    # :1272-1284 (a DICE, IPS or SSM checkpoint ranks by the raw head too)
+        args.saveID += "pop_exp-{:.2f}".format(popularity_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau", "warp": "warp"}.get(args.train, "")
         print("normal MF... ")
         args.regs = args.fregs
     else:

@@ -225,7 +225,7 @@ def main(argv=None):
     from . import train_new_api as t
     t.configure(argv)
     args, data = t.args, t.data
-    if not (args.model == "mf" and args.train in ("normal", "dice", "ips", "ssm", "ials", "pcc", "dau")):
+    if not (args.model == "mf" and args.train in ("normal", "dice", "ips", "ssm", "ials", "pcc", "dau", "warp")):
         raise NotImplementedError("Not implement this training method.....")
     K, cuts = check_flags(args, t.Ks)
     t.check_topk_max(args)
@@ -238,7 +238,7 @@ def main(argv=None):
         torch.cuda.set_device(int(args.cuda))
     device = torch.device("cuda")
     config = {"n_users": data.n_users, "n_items": data.n_items}
-    args.saveID += "pop_exp-{:.2f}".format(args.pop_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau"}.get(args.train, "")   # train_new_api.main: the directory name
+    args.saveID += "pop_exp-{:.2f}".format(args.pop_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau", "warp": "warp"}.get(args.train, "")   # train_new_api.main: the directory name
     args.wd = args.regs
     path = checkpoint_dir(args) + "best_ckpt.ckpt"
     if not os.path.exists(path):

@@ -37,8 +37,8 @@ def restore(argv=None):
     random.seed(2020)
     np.random.seed(2020)
     torch.manual_seed(2021)
-    if args.model != "mf" or args.train not in ("normal", "s_condition", "dice", "ips", "ssm", "ials", "pcc", "dau"):
-        raise NotImplementedError("export_topk restores a --train normal, --train dice, --train ips, --train ssm, --train ials, --train pcc, --train dau or --train s_condition run, not %r" % (args.train,))
+    if args.model != "mf" or args.train not in ("normal", "s_condition", "dice", "ips", "ssm", "ials", "pcc", "dau", "warp"):
+        raise NotImplementedError("export_topk restores a --train normal, --train dice, --train ips, --train ssm, --train ials, --train pcc, --train dau, --train warp or --train s_condition run, not %r" % (args.train,))
     if torch.cuda.device_count() > 1 and str(args.cuda).isdigit() and int(args.cuda) < torch.cuda.device_count():
         torch.cuda.set_device(int(args.cuda))
     device = torch.device("cuda")
@@ -50,7 +50,7 @@ def restore(argv=None):
         data.add_expo_popularity(np.power(get_popularity_from_load(pop_item_all), args.pop_exp))
         rec_type, popularity = "condition", np.power(pop_item_all[:, -2], args.pop_exp)
     else:
-        args.saveID += "pop_exp-{:.2f}".format(args.pop_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau"}.get(args.train, "")
+        args.saveID += "pop_exp-{:.2f}".format(args.pop_exp) + {"ips": "ips", "ssm": "ssm", "ials": "ials", "pcc": "pcc", "dau": "dau", "warp": "warp"}.get(args.train, "")
         rec_type, popularity = "main_branch", None
     args.wd = args.regs
     path = checkpoint_dir(args) + "best_ckpt.ckpt"

@@ -10,6 +10,7 @@
     SSMBPRMF           SSM                 (no reference code: DESIGN.md 5l)   a BPRMF trained with the sampled-softmax loss; Adam sweep only
     MACRBPRMF          MACR                MF/model_api.py:613-651, :627-628 (never driven by the reference's trainer: DESIGN.md 5h); Adam sweep only
     LightGCN           the LightGCN backbone (no reference code: DESIGN.md 5j)  ego tables propagated over the train graph; ConditionalLightGCN: PD/PDA on it
+    WARPBPRMF          WARP                (no reference code: DESIGN.md 5x)   a BPRMF trained with the rank-weighted hinge on the first violating candidate; Adam sweep only
     IALSMF             iALS                (no reference code: DESIGN.md 5o)   the tables of a BPRMF solved row by row (implicit ALS); no step, train_epoch()
 
 A TF-1 graph exposes *fetchables* (`opt`, `loss`, `mf_loss`, `reg_loss`, `batch_ratings`, ...) that the
@@ -720,6 +721,87 @@ class IPSBPRMF(BPRMF):
     def state_dict(self):
         sd = super().state_dict()
         sd.update(ips_clip=self.ips_clip, ips_norm=self.ips_norm)
+        return sd
+
+
+def check_warp(args):
+    """--train warp: refuse, before anything is built, what the WARP sampler and step have no path for.  Every message names its flag.  The
+    sampler scores its candidates on the live fp32 tables of a BPRMF right before the step that trains on them (check_dns has the reasons)."""
+    if getattr(args, "model", "mf") != "mf":
+        raise NotImplementedError("--model %s: --train warp scores candidates on the embedding tables themselves, a LightGCN's scores live on the "
+                                  "propagated tables (--model mf)" % (args.model,))
+    if int(getattr(args, "deterministic", 0) or 0):
+        raise NotImplementedError("--deterministic 1: --train warp sums its gradients with float atomics (no planned gradient; the draw alone is "
+                                  "bit-reproducible)")
+    if getattr(args, "table_dtype", "f32") != "f32":
+        raise NotImplementedError("--table_dtype %s: --train warp scores and trains fp32 tables only" % (args.table_dtype,))
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise NotImplementedError("--optimizer %s: --train warp runs the reference's dense-decay Adam only (--optimizer adam)" % (args.optimizer,))
+    if getattr(args, "adam_sweep", "auto") not in ("auto", "sweep"):
+        raise NotImplementedError("--adam_sweep %s: --train warp reads whole tables before every step, a replayed table's idle rows are stale then "
+                                  "(--adam_sweep auto | sweep)" % (args.adam_sweep,))
+    if getattr(args, "adam_exact_lazy", None):
+        raise NotImplementedError("adam_exact_lazy: --train warp reads whole tables before every step, a lazy table's idle rows are stale then")
+    if getattr(args, "sampler", "device") != "device":
+        raise NotImplementedError("--sampler %s: --train warp draws and scores its candidates with the device sampler only (--sampler device)"
+                                  % (args.sampler,))
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise NotImplementedError("--gpus %s: --train warp trains on one GPU (no item shards)" % (args.gpus,))
+    if getattr(args, "neg_sampler", "uniform") != "uniform":
+        raise NotImplementedError("--neg_sampler %s: --train warp draws its own negatives, the first violator among uniform candidates "
+                                  "(--neg_sampler uniform)" % (args.neg_sampler,))
+    if getattr(args, "test", "normal") not in ("normal", "warp"):
+        raise NotImplementedError("--test %s: --train warp goes with --test normal (the raw head and the gamma search of a BPRMF) or --test warp"
+                                  % (args.test,))
+    margin = getattr(args, "warp_margin", 1.0)
+    if not math.isfinite(float(margin)):
+        raise ValueError("--warp_margin must be a finite number, got %s" % (margin,))
+    T = getattr(args, "warp_max_trials", 64)
+    if int(T) != T or not 1 <= int(T) <= ops.WARP_MAX_TRIALS:
+        raise ValueError("--warp_max_trials must be an integer in 1 .. %d, got %s" % (ops.WARP_MAX_TRIALS, T))
+    if getattr(args, "warp_weight", "harmonic") not in ops.WARP_WEIGHT_KINDS:
+        raise ValueError("--warp_weight must be harmonic, log or none, got %s" % (args.warp_weight,))
+
+
+class WARPBPRMF(BPRMF):
+    """BPR-MF trained with the WARP loss: the hinge margin - (u.p - u.n) on the first of --warp_max_trials uniform candidates that
+    violates --warp_margin, weighted by the rank estimate of --warp_weight.  Fetchables, tables, evaluation and checkpoint are those of BPRMF --
+    the two differ only in how they were trained; a step is pda_warp_adam_step_f32 on the (users, pos, neg, coef) batches of
+    DeviceSampler(mode="warp")."""
+
+    def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
+        check_warp(args)
+        super().__init__(args, data_config, use_dataset_api, users_api, pos_items_api, neg_items_api, **kw)
+        self.adam_exact_lazy = False
+        self.warp_margin = float(getattr(args, "warp_margin", 1.0))
+        self.warp_max_trials = int(getattr(args, "warp_max_trials", 64))
+        self.warp_weight = getattr(args, "warp_weight", "harmonic")
+
+    def train_step(self, users, pos, neg, coef=None, neg_pop=None, plan=None) -> torch.Tensor:
+        """One WARP step; returns the float32 [3] device tensor (loss, mf_loss, reg_loss) of this step, as BPRMF.train_step does."""
+        if coef is None or neg_pop is not None:
+            raise ValueError("WARPBPRMF trains on (users, pos, neg, coef) batches: the coefficient column of DeviceSampler(mode='warp')")
+        U, I = self.weights["user_embedding"], self.weights["item_embedding"]
+        rows = getattr(self, "_loss_rows", None)
+        if rows is not None and self._loss_row_i < rows.shape[0]:
+            self._loss = rows[self._loss_row_i]
+            self._loss_row_i += 1
+        else:
+            self._loss_i = (self._loss_i + 1) & 15
+            self._loss = self._loss_ring[self._loss_i]
+            self._loss.zero_()
+        st = self._opt_state()
+        if "tagU" not in st:
+            st["tagU"], st["tagI"] = ops.adam_row_tags(U.shape[0], I.shape[0], U.device)
+        self._t += 1
+        ops.warp_adam_step(U, st["mU"], st["vU"], st["gU"], st["tagU"], I, st["mI"], st["vI"], st["gI"], st["tagI"], users, pos, neg, coef,
+                           margin=self.warp_margin, regs=self.decay, reg_div=self.batch_size, step=self._t,
+                           lr_t=ops.adam_lr_t(self.lr, self._t), users_distinct=bool(getattr(self, "users_distinct", False)), loss_acc=self._loss)
+        return self._loss
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd.update(warp_margin=self.warp_margin, warp_max_trials=self.warp_max_trials, warp_weight=self.warp_weight)
         return sd
 
 

@@ -3561,6 +3561,204 @@ def dns_sample_into(out, U, I, train_indptr, train_indices, *, n_cands: int, top
     return out
 
 
+# ---- the WARP loss (include/pda_hip_warp.h) ------------------------------------------------------------------------------------------------------
+WARP_MAX_TRIALS = _lib.WARP_MAX_TRIALS
+WARP_EMBED_SIZES = (32, 64, 128, 256)
+WARP_WEIGHT_KINDS = ("harmonic", "log", "none")
+
+
+def check_warp_sizes(max_trials, margin, what: str = "WARP"):
+    """1 <= max_trials <= WARP_MAX_TRIALS, a whole number; margin not NaN (+-inf are the library's to take: +inf makes every candidate a violator)."""
+    if int(max_trials) != max_trials or not 1 <= int(max_trials) <= WARP_MAX_TRIALS:
+        raise ValueError(f"{what}: max_trials, the candidates a row may try, must be an integer in 1 .. {WARP_MAX_TRIALS}, got {max_trials}")
+    if float(margin) != float(margin):
+        raise ValueError(f"{what}: the margin is NaN")
+
+
+class WarpWeights:
+    """wtab of pda_warp_sample_f32: the weight of a triplet whose first violator was its N-th candidate, N = 1 .. T, built on the host in float64
+    and rounded once to fp32.  rank(N) = floor((n_eligible - 1) / N) estimates the positive's rank among the n_eligible = neg_hi - neg_lo items
+    the candidates are drawn from.  kind "harmonic": sum_{k = 1 .. rank} 1 / k (WSABIE) | "log": log(max(1, rank)) (LightFM's form: its weight
+    is 0 at rank 1, so a triplet whose estimated rank is 1 -- or 0 -- does not train) | "none": 1 (the plain hinge on the first violator).
+    wtab[0] = 0: a row without a violator.  table64: the float64 values, wtab: float32 [T + 1] on `device`."""
+
+    def __init__(self, table64, kind, n_eligible, device):
+        import numpy as np
+        self.kind, self.n_eligible, self.T = kind, int(n_eligible), len(table64) - 1
+        self.table64 = np.asarray(table64, dtype=np.float64)
+        self.wtab = torch.from_numpy(self.table64.astype(np.float32)).to(device)
+        self.max_weight = float(self.table64.astype(np.float32).max())
+
+    @classmethod
+    def build(cls, n_eligible, T, kind="harmonic", device="cpu"):
+        import numpy as np
+        if kind not in WARP_WEIGHT_KINDS:
+            raise ValueError(f"WARP weights: kind must be one of {WARP_WEIGHT_KINDS}, got {kind!r}")
+        if int(n_eligible) != n_eligible or int(n_eligible) < 1:
+            raise ValueError(f"WARP weights: n_eligible, the items a candidate is drawn from, must be an integer >= 1, got {n_eligible}")
+        if int(T) != T or not 1 <= int(T) <= WARP_MAX_TRIALS:
+            raise ValueError(f"WARP weights: T must be an integer in 1 .. {WARP_MAX_TRIALS}, got {T}")
+        n, T = int(n_eligible), int(T)
+        rank = (n - 1) // np.arange(1, T + 1, dtype=np.int64)
+        tab = np.zeros(T + 1, dtype=np.float64)
+        if kind == "harmonic":
+            h = np.concatenate([[0.0], np.cumsum(1.0 / np.arange(1, max(n, 2), dtype=np.float64))])      # h[k] = 1 + 1/2 + .. + 1/k
+            tab[1:] = h[rank]
+        elif kind == "log":
+            tab[1:] = np.log(np.maximum(1, rank).astype(np.float64))
+        else:
+            tab[1:] = 1.0
+        return cls(tab, kind, n, device)
+
+
+def _warp_args(U, I, train_indptr, train_indices, train_slots, B, T, margin, wtab, neg_range, pop_matrix, user_pool, n_pool):
+    """The host-side checks of both WARP sampler front-ends -> (n_slots, lo, hi)."""
+    U, I = _need(U, torch.float32, "U"), _need(I, torch.float32, "I")
+    if U.dim() != 2 or I.dim() != 2 or U.shape[1] != I.shape[1] or U.shape[1] not in WARP_EMBED_SIZES or U.shape[0] < 1 or I.shape[0] < 1:
+        raise ValueError(f"WARP sampler: U float32 [n_users, d], I float32 [n_items, d], d one of {WARP_EMBED_SIZES}, got {tuple(U.shape)}, {tuple(I.shape)}")
+    check_warp_sizes(T, margin, "WARP sampler")
+    if _need(wtab, torch.float32, "wtab").numel() != int(T) + 1:
+        raise ValueError(f"WARP sampler: wtab holds max_trials + 1 = {int(T) + 1} float32, got {wtab.numel()}")
+    if int(B) < 1 or int(B) > (1 << 22):
+        raise ValueError("WARP sampler: B in 1 .. 2^22")
+    lo, hi = int(neg_range[0]), int(neg_range[1])
+    if not 0 <= lo < hi <= I.shape[0]:
+        raise ValueError(f"WARP sampler: neg_range = (lo, hi) with 0 <= lo < hi <= n_items = {I.shape[0]}, got ({lo}, {hi})")
+    _need(train_indptr, torch.int64, "train_indptr"), _need(train_indices, torch.int32, "train_indices")
+    if train_indptr.numel() != U.shape[0] + 1:
+        raise ValueError("WARP sampler: train_indptr holds n_users + 1 offsets")
+    _need(train_slots, torch.int32, "train_slots", optional=True)
+    if user_pool is not None and _need(user_pool, torch.int32, "user_pool").numel() < int(n_pool):
+        raise ValueError("user_pool holds n_pool int32")
+    n_slots = 0
+    if pop_matrix is not None:
+        pop_matrix = _need(pop_matrix, torch.float32, "pop_matrix")
+        if pop_matrix.dim() != 2 or pop_matrix.shape[0] != I.shape[0] or pop_matrix.shape[1] < 1:
+            raise ValueError("WARP sampler: pop_matrix float32 [n_items, n_slots >= 1]")
+        n_slots = pop_matrix.shape[1]
+    return n_slots, lo, hi
+
+
+def warp_sample(U, I, train_indptr, train_indices, B: int, *, max_trials: int, margin: float, wtab, seed: int, step: int, neg_range, users=None,
+                user_pool=None, n_pool: int = 0, train_slots=None, pop_matrix=None, want_cands: bool = False, stat=None, check_ids: bool = True):
+    """pda_warp_sample_f32 -> (users, pos, neg, coef, trials, pos_pop|None, neg_pop|None) on the device: the users, positives and slots of
+    sample_triplets(seed, step); neg is the first of the max_trials candidates a row draws as ssm_sample draws its columns that violates the
+    margin on the tables as they are NOW (margin - (u.pos - u.cand) > 0), trials its 1-based column (0: none, neg is the last candidate) and
+    coef = wtab[trials].  want_cands: (.., cand i32 [B, T], cand_score f32 [B, T], pos_score f32 [B]) behind the seven.  stat int64 [2] +=
+    (sum of trials over the rows with a violator, rows without one).  users given: they are kept (check_ids: refused unless all lie in
+    [0, n_users); costs a host sync).  The outputs of a call are rows of one zeroed block (one fill per call, no uninitialised memory)."""
+    n_slots, lo, hi = _warp_args(U, I, train_indptr, train_indices, train_slots, B, max_trials, margin, wtab, neg_range, pop_matrix, user_pool, n_pool)
+    dev = U.device
+    gen = users is None
+    if gen:
+        if int(n_pool) < 1:
+            raise ValueError("WARP sampler: drawing users needs n_pool >= 1")
+    else:
+        if _need(users, torch.int32, "users").numel() != B:
+            raise ValueError("users holds B int32")
+        if check_ids and B > 0 and not bool(((users >= 0) & (users < U.shape[0])).all()):
+            raise ValueError("WARP sampler: a user id lies outside [0, n_users)")
+    if stat is not None and _need(stat, torch.int64, "stat").numel() < 2:
+        raise ValueError("WARP sampler: stat holds two int64")
+    T = int(max_trials)
+    block = torch.zeros((7, int(B)), dtype=torch.int32, device=dev)      # users, pos, neg, trials | coef, pos_pop, neg_pop (as float32)
+    pos, neg, trials, coef = block[1], block[2], block[3], block[4].view(torch.float32)
+    if gen:
+        users = block[0]
+    pp = pn = cand = score = ps = None
+    if pop_matrix is not None:
+        pp, pn = block[5].view(torch.float32), block[6].view(torch.float32)
+    if want_cands:
+        wide = torch.zeros((2 * T + 1, int(B)), dtype=torch.int32, device=dev)
+        cand, score = wide[:T].view(int(B), T), wide[T:2 * T].view(torch.float32).view(int(B), T)
+        ps = wide[2 * T].view(torch.float32)
+    check(_lib.load().pda_warp_sample_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], U.shape[1], ptr(users), int(gen), ptr(user_pool), int(n_pool), int(B),
+                                          ptr(train_indptr), ptr(train_indices), ptr(train_slots), ptr(pop_matrix), n_slots, lo, hi, T, float(margin),
+                                          ptr(wtab), seed & (2 ** 64 - 1), int(step), ptr(pos), ptr(neg), ptr(trials), ptr(coef), ptr(pp), ptr(pn),
+                                          ptr(cand), ptr(score), ptr(ps), ptr(stat), stream_ptr()), "pda_warp_sample_f32")
+    return (users, pos, neg, coef, trials, pp, pn) + ((cand, score, ps) if want_cands else ())
+
+
+def warp_sample_into(out, U, I, train_indptr, train_indices, *, max_trials: int, margin: float, wtab, seed: int, step_dev: torch.Tensor, neg_range,
+                     parity: Optional[int] = None, user_pool=None, n_pool: int = 0, train_slots=None, pop_matrix=None, cands=None, stat=None):
+    """pda_warp_sample_f32_dev: one batch into out = (users, pos, neg, coef, trials, pos_pop|None, neg_pop|None), the step read from device memory
+    (graph-capturable; the users are drawn).  step_dev int64 [1]: read only.  step_dev int64 [2] + parity p: read from slot p, step + 1 stored
+    to slot 1 - p (sample_triplets_into).  cands: optional (cand i32 [B, T], cand_score f32 [B, T], pos_score f32 [B]) to fill as well."""
+    users, pos, neg, coef, trials, pp, pn = out
+    users, pos, neg, trials = (_need(t, torch.int32, n) for t, n in ((users, "users"), (pos, "pos"), (neg, "neg"), (trials, "trials")))
+    coef = _need(coef, torch.float32, "coef")
+    B, T = users.numel(), int(max_trials)
+    if pos.numel() != B or neg.numel() != B or trials.numel() != B or coef.numel() != B:
+        raise ValueError("WARP sampler output: users [B], pos [B], neg [B], coef [B], trials [B]")
+    n_slots, lo, hi = _warp_args(U, I, train_indptr, train_indices, train_slots, B, max_trials, margin, wtab, neg_range, pop_matrix, user_pool, n_pool)
+    if int(n_pool) < 1:
+        raise ValueError("WARP sampler: drawing users needs n_pool >= 1")
+    if (pp is None) != (pn is None) or (pp is not None and pop_matrix is None):
+        raise ValueError("WARP sampler output: pos_pop and neg_pop come together, and with a pop_matrix")
+    for t, name in ((pp, "pos_pop"), (pn, "neg_pop")):
+        if t is not None and _need(t, torch.float32, name).numel() != B:
+            raise ValueError(f"{name} holds B float32")
+    cand = score = ps = None
+    if cands is not None:
+        cand, score, ps = cands
+        cand, score, ps = _need(cand, torch.int32, "cand"), _need(score, torch.float32, "cand_score"), _need(ps, torch.float32, "pos_score")
+        if tuple(cand.shape) != (B, T) or tuple(score.shape) != (B, T) or ps.numel() != B:
+            raise ValueError("WARP sampler output: cand [B, T], cand_score [B, T], pos_score [B]")
+    if stat is not None and _need(stat, torch.int64, "stat").numel() < 2:
+        raise ValueError("WARP sampler: stat holds two int64")
+    src, nxt = _step_slots(_need(step_dev, torch.int64, "step_dev"), parity)
+    check(_lib.load().pda_warp_sample_f32_dev(ptr(U), ptr(I), U.shape[0], I.shape[0], U.shape[1], ptr(users), 1, ptr(user_pool), int(n_pool), B,
+                                              ptr(train_indptr), ptr(train_indices), ptr(train_slots), ptr(pop_matrix), n_slots, lo, hi, T,
+                                              float(margin), ptr(wtab), seed & (2 ** 64 - 1), ptr(src), ptr(nxt), ptr(pos), ptr(neg), ptr(trials),
+                                              ptr(coef), ptr(pp), ptr(pn), ptr(cand), ptr(score), ptr(ps), ptr(stat), stream_ptr()),
+          "pda_warp_sample_f32_dev")
+    return out
+
+
+def _warp_check(U, I, users, pos, neg, coef, margin, tagU, tagI, loss_acc, check_ids: bool):
+    d, B = _triplet_shapes("WARP", "U [n_users, d] and I [n_items, d]", WARP_EMBED_SIZES, U, I, users, pos, neg)
+    if _need(coef, torch.float32, "coef").numel() != B:
+        raise ValueError("coef holds one float32 per triplet")
+    if float(margin) != float(margin):
+        raise ValueError("WARP: the margin is NaN")
+    if _need(tagU, torch.int32, "tagU").numel() != U.shape[0] or _need(tagI, torch.int32, "tagI").numel() != I.shape[0]:
+        raise ValueError("tagU / tagI hold one int32 per table row")
+    if _need(loss_acc, torch.float32, "loss_acc", optional=True) is not None and loss_acc.numel() < 3:
+        raise ValueError("WARP loss_acc holds three float32")
+    _triplet_ids("WARP", U, I, users, pos, neg, check_ids)
+    return d, B
+
+
+def warp_step(U, I, users, pos, neg, coef, gU, gI, tagU, tagI, *, margin: float, regs: float, reg_div: float, step: int, grouped: bool = False,
+              users_distinct: bool = False, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = True):
+    """pda_warp_step_f32: the batch's gradient of (1 / B) sum coef_t max(0, margin - (u.p - u.n)) over the triplets with coef_t > 0, plus the L2
+    term of every valid triplet, summed into gU / gI (rows tagged `step`), no update.  loss_acc float32 [3] += (loss, mf_loss, reg_loss)."""
+    d, B = _warp_check(U, I, users, pos, neg, coef, margin, tagU, tagI, loss_acc, check_ids)
+    gU, gI = _need(gU, torch.float32, "gU"), _need(gI, torch.float32, "gI")
+    if gU.shape != U.shape or gI.shape != I.shape:
+        raise ValueError("gU / gI have the shapes of the tables")
+    check(_lib.load().pda_warp_step_f32(ptr(U), ptr(I), U.shape[0], I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(coef), float(margin), B, d,
+                                        float(regs), float(reg_div), ptr(gU), ptr(gI), ptr(tagU), ptr(tagI), int(step),
+                                        _ips_flags(grouped, users_distinct), ptr(loss_acc), stream_ptr()), "pda_warp_step_f32")
+
+
+def warp_adam_step(U, mU, vU, gU, tagU, I, mI, vI, gI, tagI, users, pos, neg, coef, *, margin: float, regs: float, reg_div: float, step: int,
+                   lr_t: float, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS, grouped: bool = False, users_distinct: bool = False,
+                   cache_policy: int = ADAM_CACHE_AUTO, loss_acc: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """pda_warp_adam_step_f32: one WARP train step (the weighted hinge gradients, TF-1.14 dense-decay Adam over both tables) in two launches;
+    graph-capturable.  The arguments of adam_step with coef float32 [B] and the margin in place of the popularities."""
+    d, B = _warp_check(U, I, users, pos, neg, coef, margin, tagU, tagI, loss_acc, check_ids)
+    for t in (mU, vU, gU, mI, vI, gI):
+        _need(t, torch.float32, "adam state")
+    if not (mU.shape == vU.shape == gU.shape == U.shape and mI.shape == vI.shape == gI.shape == I.shape):
+        raise ValueError("the Adam state tables have the shapes of U and I")
+    check(_lib.load().pda_warp_adam_step_f32(ptr(U), ptr(mU), ptr(vU), ptr(gU), ptr(tagU), U.shape[0], ptr(I), ptr(mI), ptr(vI), ptr(gI), ptr(tagI),
+                                             I.shape[0], ptr(users), ptr(pos), ptr(neg), ptr(coef), float(margin), B, d, float(regs), float(reg_div),
+                                             int(step), float(lr_t), beta1, beta2, eps, _ips_flags(grouped, users_distinct), int(cache_policy),
+                                             ptr(loss_acc), stream_ptr()), "pda_warp_adam_step_f32")
+    mark_modified(U, I)
+
+
 # ---- popularity-weighted negative sampling (include/pda_hip_negpop.h) -------------------------------------------------------------------------
 NEGPOP_MAX_POWER = 4.0
 

@@ -13,7 +13,7 @@ _REFERENCE_FLAGS = [
     ("data_path", None, "./data/", "root directory that holds <dataset>/"),
     ("dataset", None, "kwai", "dataset directory name"),
     ("source", None, "normal", "(unused)"),
-    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm) | ials (implicit ALS, --ials_alpha0 / --ials_nu; no sampler, no optimiser) | pcc (BPR plus the popularity-correlation regulariser, --pcc_gamma / --pcc_on / --pcc_pop) | dau (the DirectAU alignment + uniformity loss, --dau_gamma / --dau_t / --dau_same / --dau_rank; no negatives)"),
+    ("train", None, "normal", "normal (BPRMF) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the sampled-softmax loss, --ssm_negs / --ssm_tau / --ssm_norm) | ials (implicit ALS, --ials_alpha0 / --ials_nu; no sampler, no optimiser) | pcc (BPR plus the popularity-correlation regulariser, --pcc_gamma / --pcc_on / --pcc_pop) | dau (the DirectAU alignment + uniformity loss, --dau_gamma / --dau_t / --dau_same / --dau_rank; no negatives) | warp (the WARP loss: the rank-weighted hinge on the first of --warp_max_trials uniform candidates that violates --warp_margin, --warp_weight; fp32 tables, the device sampler, one GPU)"),
     ("test", None, "normal", "normal (BPRMF/BPRMF-A) | s_condition (PD/PDA) | temp_pop | dice | ips | macr | ssm (the raw head of an SSM model alone) | ials (the raw head of an iALS model alone) | pcc (the raw head of a PCC model alone) | dau (the main head of a DirectAU model alone)"),
     ("valid_set", None, "test", "test | valid"),
     ("save_dir", None, "/data/zyang/save_model/", "checkpoint root"),
@@ -105,6 +105,9 @@ _EXTENSION_FLAGS = [
     ("neg_pop_power", float, 0.75, "--neg_sampler pop: the power beta of q_i ~ (c_i + 1)^beta, 0 .. 4 (0: the uniform sampler's batches, bit for bit; 0.75: the unigram^0.75 of word2vec; 1: in proportion to popularity)"),
     ("dns_candidates", int, 16, "DNS (--neg_sampler dns): candidates M drawn and scored per triplet, 1 .. 256 (1: the uniform sampler's batches, bit for bit)"),
     ("dns_topn", int, 1, "DNS: the negative is drawn uniformly from the N best of the M candidates, 1 .. --dns_candidates (1: the best one, the classic DNS)"),
+    ("warp_max_trials", int, 64, "WARP (--train warp, include/pda_hip_warp.h): the uniform candidates T a triplet may try, 1 .. 256; its negative is the first one that violates the margin, the number of tries N estimates the positive's rank, floor((n_items - 1) / N)"),
+    ("warp_margin", float, 1.0, "WARP: the margin of the hinge, margin - (u.pos - u.neg); a candidate violates when that is > 0.  A finite number.  The default is UNTUNED: nothing here has the data sets"),
+    ("warp_weight", str, "harmonic", "WARP: the weight of a triplet as a function of the estimated rank.  harmonic = 1 + 1/2 + .. + 1/rank (WSABIE) | log = log(max(1, rank)) (LightFM's form; 0 at rank 1) | none = 1 (the plain hinge on the first violator)"),
     ("ssm_source", str, "sampled", "SSM (--train ssm): where a row's negatives come from.  sampled = --ssm_negs uniform draws per row | batch = the other rows' positives (in-batch softmax, include/pda_hip_inbatch.h: --batch_size - 1 shared negatives per row, --batch_size in 2 .. 16384) | all = every item of the catalogue, no sampling (the exact softmax both estimate, include/pda_hip_fullsm.h: --batch_size in 1 .. 16384)"),
     ("ssm_logq", int, 1, "SSM with --ssm_source batch: 1 subtracts log q_i, the log-probability that item i sits in a column of the batch, from every logit of column item i, the positive's own included (logQ correction of the popularity-skewed in-batch negatives); 0 | 1; with --ssm_source sampled it acts under --neg_sampler pop (log q_i of the popularity proposal, the same convention) and is unused under --neg_sampler uniform, where the correction is a constant that cancels in the softmax; unused with --ssm_source all (nothing is sampled, so there is nothing to correct)"),
     ("ssm_mask_train", int, 1, "SSM with --ssm_source batch: 1 leaves a column out of a row's softmax when its item is a train item of the row's user (the sampled path rejects the same items when it draws); with --ssm_source all: 1 leaves the user's other train items out of the row's softmax over the catalogue, 0 keeps every item; 0 | 1"),

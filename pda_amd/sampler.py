@@ -15,6 +15,9 @@ yielding, per step, a tuple of sequences of length batch_size -- (users, pos, ne
                      mode="ssm": the sampled-softmax batches (pda_ssm_sample_dev): (users, pos, negs [B, n_negs]).
                      mode="dns": the batches of mode="bpr" with the negative picked among the topn best-scoring of n_cands
                      uniform candidates under the model's live tables (pda_dns_sample_f32; set_tables).
+                     mode="warp": the batches of mode="bpr" with the negative the FIRST of max_trials uniform candidates that violates
+                     the margin under the model's live tables (pda_warp_sample_f32; set_tables): (users, pos, neg, coef), coef the
+                     rank weight wtab[trials] the WARP step scales the triplet by.
                      neg_table (mode="bpr" | "ssm"): an ops.NegPopTable; the negatives are drawn from its popularity proposal
                      (pda_negpop_*) instead of uniformly, everything else about the batches stays.
     HostDiceSampler  PNSM in numpy, the debugging twin of mode="dice" (--sampler host): the same algorithm on the
@@ -109,9 +112,20 @@ class DeviceSampler:
     batch handed out is a row view of the queue and stays valid until `ahead` further batches have been taken."""
 
     def __init__(self, data, device, with_pop: bool, seed: int = 2020, neg_range=None, ahead: int = 32, temp_slots: int = 0, mode: str = "bpr",
-                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0, n_cands: int = 0, topn: int = 1, neg_table=None):
-        if mode not in ("bpr", "dice", "ssm", "dns"):
-            raise ValueError("DeviceSampler mode must be 'bpr', 'dice', 'ssm' or 'dns', not %r" % (mode,))
+                 margin: float = 40.0, margin_decay: float = 0.9, n_negs: int = 0, n_cands: int = 0, topn: int = 1, neg_table=None,
+                 max_trials: int = 0, wtab=None):
+        if mode not in ("bpr", "dice", "ssm", "dns", "warp"):
+            raise ValueError("DeviceSampler mode must be 'bpr', 'dice', 'ssm', 'dns' or 'warp', not %r" % (mode,))
+        if mode == "warp":
+            # (margin: the hinge's margin here, PNSM's popularity margin under mode="dice")
+            ops.check_warp_sizes(max_trials, margin, "mode='warp'")
+            if with_pop or temp_slots > 0:
+                raise ValueError("mode='warp' draws (users, pos, neg, coef) for the raw head: no popularity columns (with_pop), no time slots (temp_slots)")
+            if not isinstance(wtab, ops.WarpWeights) or wtab.T != int(max_trials):
+                raise ValueError("mode='warp': wtab is an ops.WarpWeights built for max_trials = %r" % (max_trials,))
+        self.max_trials, self.warp_weights = int(max_trials), wtab
+        self._warp_rows = 0
+        self.warp_stat = None         # mode="warp": int64 [2] += (sum of trials over rows with a violator, rows without one); take_warp_stat
         if mode == "dns":
             ops.check_dns_sizes(n_cands, topn, "mode='dns'")
         if neg_table is not None:
@@ -125,7 +139,7 @@ class DeviceSampler:
                 raise ValueError("the neg_table covers %r, the sampler draws from (0, %d): pass the table's neg_range" % (neg_table.neg_range, data.n_items))
         self.neg_table = neg_table
         self.n_cands, self.topn = int(n_cands), int(topn)
-        self._tables = None           # mode="dns": set_tables
+        self._tables = None           # mode="dns" | "warp": set_tables
         if mode == "ssm":
             if with_pop or temp_slots > 0:
                 raise ValueError("mode='ssm' draws (users, pos, negs): no popularity columns (with_pop), no time slots (temp_slots)")
@@ -217,7 +231,7 @@ class DeviceSampler:
         return self.margin
 
     def set_tables(self, fn):
-        """mode="dns": fn() -> (U, I), the LIVE fp32 tables the candidates are scored on (the trainer hands it over once the Recommender
+        """mode="dns" | "warp": fn() -> (U, I), the LIVE fp32 tables the candidates are scored on (the trainer hands it over once the Recommender
         exists; called at every batch, so it may return new tensors)."""
         self._tables = fn
 
@@ -234,10 +248,40 @@ class DeviceSampler:
         self.plan = ops.triplet_plan(u, p, n)[0] if self.with_plan else None
         return (u, p, n, pp, pn) if self.with_pop else (u, p, n)
 
+    def _batch_warp(self):
+        """One pda_warp_sample_f32 launch on the tables as they stand: no look-ahead queue, the tables move between steps.  The coefficient
+        column travels with the batch; the trial counts go into warp_stat on the device (no host read)."""
+        if self._tables is None:
+            raise ValueError("mode='warp' scores its candidates on the model's tables: call set_tables(fn) before the first batch")
+        U, I = self._tables()
+        if self.warp_stat is None:
+            self.warp_stat = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if self.warp_weights.wtab.device != U.device:
+            self.warp_weights.wtab = self.warp_weights.wtab.to(U.device)
+        u, p, n, coef = ops.warp_sample(U, I, self.indptr, self.indices, self.data.batch_size, max_trials=self.max_trials, margin=self.margin,
+                                        wtab=self.warp_weights.wtab, seed=self.seed, step=self.step, neg_range=self.neg_range,
+                                        user_pool=self.pool, n_pool=self.pool.numel(), stat=self.warp_stat)[:4]
+        self._warp_rows += self.data.batch_size
+        self.plan = None
+        return (u, p, n, coef)
+
+    def take_warp_stat(self):
+        """mode="warp": (mean trials over the rows with a violator, share of rows without one) since the last call (one host read), and a
+        fresh count."""
+        if self.warp_stat is None:
+            return 0.0, 0.0
+        total, none = (int(x) for x in self.warp_stat.tolist())
+        rows = self._warp_rows
+        self.warp_stat.zero_()
+        self._warp_rows = 0
+        return total / max(rows - none, 1), none / max(rows, 1)
+
     def batch(self):
         self.step += 1
         if self.mode == "dns":
             return self._batch_dns()
+        if self.mode == "warp":
+            return self._batch_warp()
         if self.mode == "dice":     # one pda_dice_sample launch per step; the margin travels by value
             self.plan = None
             return ops.dice_sample(self.indptr, self.indices, self.dice_pop, self.data.batch_size, margin=self.margin, seed=self.seed,

@@ -30,8 +30,8 @@ from . import ops
 from .exposure import BiasReport, EvalResult
 from .rank_report import RankReport
 from .load_data import Data, Data2, get_popularity_from_load, load_popularity
-from .model_api import (BPRMF, DAUMF, DICE, IALSMF, IPSBPRMF, MACRBPRMF, PCCBPRMF, SSMBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dau, check_dice,
-                        check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_negpop, check_pcc, check_ssm, gcn_train_pairs, ips_item_counts, macr_c_grid)
+from .model_api import (BPRMF, DAUMF, DICE, IALSMF, IPSBPRMF, MACRBPRMF, PCCBPRMF, SSMBPRMF, WARPBPRMF, BPRMFTempPop, ConditionalBPRMF, ConditionalLightGCN, Fetch, LightGCN, check_dau, check_dice,
+                        check_dns, check_ials, check_ips, check_lightgcn, check_macr, check_negpop, check_pcc, check_ssm, check_warp, gcn_train_pairs, ips_item_counts, macr_c_grid)
 from .parse import parse_args
 from .used_metric import check_ks
 from .sampler import DeviceSampler, HostDiceSampler, host_generator, host_generator_with_temp, to_device_batch
@@ -162,6 +162,11 @@ class DatasetApi_Model:
             self.input_type = "without_pop"
             print("dataset api without pop")
             self.Recommender = DAUMF(args, data_config, use_dataset_api=True, device=self.device)
+        elif args.train == "warp":
+            # WARP: a BPRMF under the rank-weighted hinge on the first violating candidate; batches carry the sampler's coefficient
+            self.input_type = "without_pop"
+            print("dataset api without pop")
+            self.Recommender = WARPBPRMF(args, data_config, use_dataset_api=True, device=self.device)
         elif args.train == "ssm":
             # SSM: a BPRMF under the sampled-softmax loss; batches carry a [B, N] block of negatives, the lists read score_tables()
             self.input_type = "without_pop"
@@ -188,6 +193,10 @@ class DatasetApi_Model:
         # the device sampler draws a batch's users without replacement (like the reference, :380-381): the fused SGD step may
         # then store its user rows plainly (PDA_UPD_USERS_DISTINCT)
         self.Recommender.users_distinct = bool(getattr(generator_sampler, "distinct_users", False))
+        if getattr(generator_sampler, "mode", None) == "warp":
+            #  the WARP sampler scores its candidates on the live tables, as the DNS sampler below does
+            rec = self.Recommender
+            generator_sampler.set_tables(lambda: (rec.weights["user_embedding"], rec.weights["item_embedding"]))
         if getattr(generator_sampler, "mode", None) == "dns":
             #  the DNS sampler scores its candidates on the live tables: the reverse of the set_train_graph hand-over above.  A
             # deferred Adam would leave idle rows stale under the sampler, so the dense sweep is the update whatever the size of the tables
@@ -618,6 +627,8 @@ def main(argv=None):
         if args.test not in ("normal", "dau"):
             raise NotImplementedError("--train dau goes with --test normal (the raw head and the gamma search of a BPRMF) or --test dau, not --test "
                                       + str(args.test))
+    if args.train == "warp":
+        check_warp(args)                   # (--test outside normal | warp included)
     if args.train == "ssm":
         check_ssm(args)
         if args.test not in ("normal", "ssm"):
@@ -653,11 +664,11 @@ def main(argv=None):
         args.saveID += "gcn_layers-{}".format(args.gcn_layers)
     if args.train == "ials":               # the pairs reach the model the way a LightGCN's edges do
         config["gcn_train_pairs"] = gcn_train_pairs(data.train_user_list)
-    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr", "ssm", "ials", "pcc", "dau"):   # :963-970 (DICE, IPS, SSM, PCC and DirectAU are evaluated like a BPRMF: --test normal)
+    if args.model in ("mf", "lightgcn") and args.train in ("normal", "dice", "ips", "macr", "ssm", "ials", "pcc", "dau", "warp"):   # :963-970 (DICE, IPS, SSM, PCC, DirectAU and WARP are evaluated like a BPRMF: --test normal)
         args.saveID += "pop_exp-{:.2f}".format(popularity_exp)
         print({"normal": "normal MF... ", "dice": "-------    running DICE  ----------------", "macr": "-------    running MACR  ----------------",
                "ssm": "-------    running SSM  ----------------", "ials": "-------    running iALS  ----------------",
-               "pcc": "-------    running PCC  ----------------", "dau": "-------    running DirectAU  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
+               "pcc": "-------    running PCC  ----------------", "dau": "-------    running DirectAU  ----------------", "warp": "-------    running WARP  ----------------"}.get(args.train, "-------    running IPS  ----------------"))
         if args.train == "macr":
             args.saveID += "macr"
         if args.train == "ssm":
@@ -666,6 +677,8 @@ def main(argv=None):
             args.saveID += "ials"
         if args.train == "dau":
             args.saveID += "dau"
+        if args.train == "warp":
+            args.saveID += "warp"
         if args.train == "ips":
             args.saveID += "ips"
             config["ips_item_counts"] = ips_item_counts(data.train_user_list, data.n_items)
@@ -722,6 +735,9 @@ def main(argv=None):
             sampler = HostDiceSampler(data, args.dice_margin, args.dice_margin_decay)
     elif args.train == "dau":              # (check_dau has refused --sampler host) the triplet sampler without popularity columns; its negative is ignored
         sampler = DeviceSampler(data, device, False)
+    elif args.train == "warp":             # (check_warp has refused --sampler host and --neg_sampler dns | pop)
+        sampler = DeviceSampler(data, device, False, mode="warp", max_trials=args.warp_max_trials, margin=args.warp_margin,
+                                wtab=ops.WarpWeights.build(data.n_items, args.warp_max_trials, args.warp_weight, device))
     elif args.train == "ssm":              # (check_ssm has refused --sampler host)
         if args.ssm_source in ("batch", "all"):    # in-batch negatives / the whole catalogue: the triplet sampler without popularity columns; its negative is ignored
             sampler = DeviceSampler(data, device, False)
@@ -804,6 +820,8 @@ def main(argv=None):
             perf_str += "\n||--- pcc r=%.5f r2=%.5f (gamma=%g, on=%s, pop=%s)" % (rec.take_pcc() + (rec.pcc_gamma, rec.pcc_on, rec.pcc_pop))
         if args.train == "dau":            # the epoch's mean alignment and uniformity terms over its steps: one more host read beside the loss
             perf_str += "\n||--- dau align=%.5f uni_u=%.5f uni_i=%.5f (gamma=%g, t=%g, same=%s)" % (rec.take_dau() + (rec.dau_gamma, rec.dau_t, rec.dau_same))
+        if args.train == "warp":           # the epoch's trial counts, summed on the device by the sampler: one more host read beside the loss
+            perf_str += "\n||--- warp trials=%.3f none=%.4f" % sampler.take_warp_stat()
         if epoch % args.log_interval != 0:
             if args.verbose > 0 and epoch % args.verbose == 0:
                 print(perf_str)
@@ -828,7 +846,7 @@ def main(argv=None):
             print("||------------PDA/PDGA injecting linear predicted popularity testing : time: ", int(time() - ttt1))
             _print_result(ret2)
             ret = ret1
-        elif args.test in ("temp_pop", "dice", "ips", "ssm", "ials", "pcc", "dau"):     # :1192-1200 (--test dice / ips / ssm / ials / pcc / dau: the main_branch head alone)
+        elif args.test in ("temp_pop", "dice", "ips", "ssm", "ials", "pcc", "dau", "warp"):     # :1192-1200 (--test dice / ips / ssm / ials / pcc / dau / warp: the main_branch head alone)
             print(perf_str)
             ttt1 = time()
             evaluation_model.set_testing_popularity(None)
@@ -959,11 +977,11 @@ def main(argv=None):
         ret = evaluation_model.eval(model, sess, rec_type="macr")
         print("---- MACR result with the best c of the validation (c = {:.6f}):".format(rec.best_c))
         _print_result(ret)
-    elif args.test in ("temp_pop", "dice", "ips", "ssm", "ials", "pcc", "dau"):  # :1310-1314
+    elif args.test in ("temp_pop", "dice", "ips", "ssm", "ials", "pcc", "dau", "warp"):  # :1310-1314
         evaluation_model.set_testing_popularity(None)
         ret = evaluation_model.eval(model, sess, rec_type="main_branch")
         print({"temp_pop": "---- result with last pop bias for temp_pop model:", "dice": "---- DICE result (interest + conformity):"}
-              .get(args.test, {"ssm": "---- SSM result:", "ials": "---- iALS result:", "pcc": "---- PCC result:", "dau": "---- DirectAU result:"}.get(args.test, "---- IPS result:")))
+              .get(args.test, {"ssm": "---- SSM result:", "ials": "---- iALS result:", "pcc": "---- PCC result:", "dau": "---- DirectAU result:", "warp": "---- WARP result:"}.get(args.test, "---- IPS result:")))
         _print_result(ret)
     print("training and testing end!!!!")
     print("|||  ------------------------ best performance for model selected by PD/PDG/BPRMF ------------------- |||")

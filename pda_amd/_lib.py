@@ -1,6 +1,6 @@
 """ctypes binding of libpda_hip.so (the C ABI declared in include/pda_hip.h, pda_hip_experimental.h, pda_hip_temp_pop.h, pda_hip_pc.h, pda_hip_det.h,
 pda_hip_deep.h, pda_hip_xquad.h, pda_hip_dice.h, pda_hip_ips.h, pda_hip_macr.h, pda_hip_gcn.h, pda_hip_exposure.h, pda_hip_ssm.h,
-pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h, pda_hip_dau.h, pda_hip_negpop.h, pda_hip_ialspp.h, pda_hip_calib.h and pda_hip_warp.h).
+pda_hip_inbatch.h, pda_hip_dns.h, pda_hip_ials.h, pda_hip_fullsm.h, pda_hip_rank.h, pda_hip_pcc.h, pda_hip_dau.h, pda_hip_negpop.h, pda_hip_ialspp.h, pda_hip_calib.h, pda_hip_warp.h and pda_hip_ials_itemw.h).
 
 There is NO CPU fallback: if the shared object is missing or a symbol is absent this module raises.
 Device pointers come from torch ROCm tensors (``tensor.data_ptr()``); the launch stream is torch's
@@ -344,6 +344,15 @@ IALSPP_SIGNATURES = {
     "pda_ialspp_loss_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); exactly the declarations of include/pda_hip_ials_itemw.h (item-weighted iALS: `--train ials --ials_item_power`)
+IALS_ITEMW_SIGNATURES = {
+    "pda_ials_gram_scaled_f32": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
+    "pda_ialspp_gram256_scaled_f32": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "pda_ials_half_sweep_rowalpha_f32": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pda_ialspp_block_pass_rowalpha_f32": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _sz, _vp, _sz, _vp]),
+}
+
 # name -> (restype, argtypes); exactly the declarations of include/pda_hip_calib.h (calibrated-popularity re-ranking, `python -m pda_amd.calib`)
 CALIB_MAX_G = 8
 CALIB_MAX_K = 64
@@ -389,7 +398,7 @@ def load():
             list(SSM_SIGNATURES.items()) + list(INBATCH_SIGNATURES.items()) + list(DNS_SIGNATURES.items()) + list(IALS_SIGNATURES.items()) + \
             list(FULLSM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PCC_SIGNATURES.items()) + \
             list(DAU_SIGNATURES.items()) + list(NEGPOP_SIGNATURES.items()) + list(IALSPP_SIGNATURES.items()) + list(CALIB_SIGNATURES.items()) + \
-            list(WARP_SIGNATURES.items()):
+            list(WARP_SIGNATURES.items()) + list(IALS_ITEMW_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

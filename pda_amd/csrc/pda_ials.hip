@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "pda_common.h"
 #include "pda_hip_ials.h"
+#include "pda_hip_ials_itemw.h"
 
 namespace {
 
@@ -54,9 +55,11 @@ __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // sum z z^T (symmetric, stride LD) and sum z over the rows k0 .. k1 of the list (GATHER: Z[idx[k]]; otherwise Z[k] itself), into sm as
-// sA [D, LD] and sb [D].  Every lane of the workgroup calls it; it ends behind a barrier.
-template <int D, bool GATHER>
-__device__ __forceinline__ void ials_accumulate(const int32_t* idx, const float* Z, unsigned n_z, int64_t k0, int64_t k1, float* sm) {
+// sA [D, LD] and sb [D].  Every lane of the workgroup calls it; it ends behind a barrier.  SCALED (pda_hip_ials_itemw.h): the row c enters as
+// fl(scale[c] z_c[j]), the product fused into the row fetch -- one more 4-byte load and four multiplications per lane, no scaled copy of Z.
+template <int D, bool GATHER, bool SCALED = false>
+__device__ __forceinline__ void ials_accumulate(const int32_t* idx, const float* Z, unsigned n_z, int64_t k0, int64_t k1, float* sm,
+                                                const float* scale = nullptr) {
     using C = Cfg<D>;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i = lane & 31, h = lane >> 5;
     const int e = tid % C::G, rr = tid / C::G;
@@ -82,7 +85,10 @@ __device__ __forceinline__ void ials_accumulate(const int32_t* idx, const float*
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (kk < k1) {
                 const unsigned c = GATHER ? (unsigned)idx[kk] : (unsigned)kk;
-                if (c < n_z) v = ld4(Z + (size_t)c * D + 4 * e);
+                if (c < n_z) {
+                    v = ld4(Z + (size_t)c * D + 4 * e);
+                    if constexpr (SCALED) v = v * scale[c];
+                }
             }
             pre[p] = v;
         }
@@ -125,9 +131,11 @@ __device__ __forceinline__ void ials_accumulate(const int32_t* idx, const float*
     __syncthreads();
 }
 
-// The tail of a row whose sums stand in sm: A += alpha0 G + lambda_r I, A = L L^T in place, L y = b, L^T x = y, the 16-byte store.
-template <int D>
-__device__ __forceinline__ void ials_finish_solve(const IalsArgs& a, int64_t row, float* sm) {
+// The tail of a row whose sums stand in sm: A += alpha G + lambda_r I, A = L L^T in place, L y = b, L^T x = y, the 16-byte store.  alpha is
+// a.alpha0, or with
+// ROWALPHA the row's own alpha_row[row] (pda_hip_ials_itemw.h).
+template <int D, bool ROWALPHA = false>
+__device__ __forceinline__ void ials_finish_solve(const IalsArgs& a, int64_t row, float* sm, const float* alpha_row = nullptr) {
     using C = Cfg<D>;
     const int tid = threadIdx.x;
     float* sA = sm;
@@ -136,11 +144,13 @@ __device__ __forceinline__ void ials_finish_solve(const IalsArgs& a, int64_t row
     float* sx = sy + D;
     int* sflag = reinterpret_cast<int*>(sx + D);
     const float lam = a.lam_row[row];
+    float ar = 0.f;
+    if constexpr (ROWALPHA) ar = alpha_row[row];
     float* dbg = a.dbg != nullptr ? a.dbg + (size_t)row * C::SLOT : nullptr;
     if (tid == 0) *sflag = 0;
     for (int q = tid; q < D * D; q += C::NT) {
         const int i = q / D, j = q % D;
-        float v = sA[i * C::LD + j] + a.alpha0 * a.G[q];
+        float v = sA[i * C::LD + j] + (ROWALPHA ? ar : a.alpha0) * a.G[q];
         if (i == j) v = v + lam;
         sA[i * C::LD + j] = v;
         if (dbg != nullptr) dbg[q] = v;
@@ -230,6 +240,57 @@ __global__ __launch_bounds__(Cfg<D>::NT) void ials_long_rows_kernel(IalsArgs a) 
     ials_finish_solve<D>(a, row, sm);
 }
 
+// The same two kernels with alpha_row (pda_ials_half_sweep_rowalpha_f32): their text is that of the two above with the tail's ROWALPHA flag
+// set.  They are kernels of their own, with their own argument struct, so that the two above keep their argument layout and their
+// instructions (a body shared through a function of both reordered the instructions of ials_rows_kernel); a.alpha0 is not read here.
+struct IalsRowAlphaArgs {
+    IalsArgs a;
+    const float* alpha_row;     // [n_rows]
+};
+
+template <int D>
+__global__ __launch_bounds__(Cfg<D>::NT) void ials_rows_rowalpha_kernel(IalsRowAlphaArgs ra) {
+    using C = Cfg<D>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ials_smem[];
+    float* sm = reinterpret_cast<float*>(ials_smem);
+    const IalsArgs& a = ra.a;
+    const int64_t* wk = a.work + 4 * (size_t)blockIdx.x;
+    const int64_t row = wk[0], k0 = wk[1], k1 = wk[2], slot = wk[3];
+    if (row < 0 || (uint64_t)row >= a.n_rows || k0 < 0 || k1 < k0 || (uint64_t)k1 > a.nnz || slot >= (int64_t)a.n_slots) return;   // (uniform)
+    ials_accumulate<D, true>(a.indices, a.Z, a.n_z, k0, k1, sm);
+    if (slot >= 0) {
+        float* dst = a.partials + (size_t)slot * C::SLOT;
+        for (int q = threadIdx.x; q < D * D; q += C::NT) dst[q] = sm[(q / D) * C::LD + q % D];
+        if (threadIdx.x < D) dst[D * D + threadIdx.x] = sm[D * C::LD + threadIdx.x];
+        return;
+    }
+    ials_finish_solve<D, true>(a, row, sm, ra.alpha_row);
+}
+
+template <int D>
+__global__ __launch_bounds__(Cfg<D>::NT) void ials_long_rows_rowalpha_kernel(IalsRowAlphaArgs ra) {
+    using C = Cfg<D>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ials_smem[];
+    float* sm = reinterpret_cast<float*>(ials_smem);
+    const IalsArgs& a = ra.a;
+    const int64_t* lr = a.long_rows + 3 * (size_t)blockIdx.x;
+    const int64_t row = lr[0], s0 = lr[1], n = lr[2];
+    if (row < 0 || (uint64_t)row >= a.n_rows || s0 < 0 || n < 0 || (uint64_t)s0 + (uint64_t)n > a.n_slots) return;   // (uniform)
+    const float* src = a.partials + (size_t)s0 * C::SLOT;
+    for (int q = threadIdx.x; q < D * D; q += C::NT) {
+        float v = 0.f;
+        for (int64_t j = 0; j < n; ++j) v = v + src[(size_t)j * C::SLOT + q];
+        sm[(q / D) * C::LD + q % D] = v;
+    }
+    if (threadIdx.x < D) {
+        float v = 0.f;
+        for (int64_t j = 0; j < n; ++j) v = v + src[(size_t)j * C::SLOT + D * D + threadIdx.x];
+        sm[D * C::LD + threadIdx.x] = v;
+    }
+    __syncthreads();
+    ials_finish_solve<D, true>(a, row, sm, ra.alpha_row);
+}
+
 struct GramArgs {
     const float* Z;
     float* G;
@@ -245,6 +306,26 @@ __global__ __launch_bounds__(Cfg<D>::NT) void ials_gram_blocks_kernel(GramArgs a
     const int64_t k0 = (int64_t)blockIdx.x * PDA_IALS_GRAM_ROWS;
     const int64_t k1 = k0 + PDA_IALS_GRAM_ROWS < (int64_t)a.n_rows ? k0 + PDA_IALS_GRAM_ROWS : (int64_t)a.n_rows;
     ials_accumulate<D, false>(nullptr, a.Z, (unsigned)a.n_rows, k0, k1, sm);
+    float* dst = a.partials + (size_t)blockIdx.x * C::SLOT;
+    for (int q = threadIdx.x; q < D * D; q += C::NT) dst[q] = sm[(q / D) * C::LD + q % D];
+}
+
+// G_w = sum_c (s_c z_c)(s_c z_c)^T: the same blocks with the scale fused into the row fetch (pda_ials_gram_scaled_f32); the blocks are added by
+// ials_gram_sum_kernel as they are.
+struct GramScaledArgs {
+    GramArgs g;
+    const float* scale;     // [n_rows]
+};
+
+template <int D>
+__global__ __launch_bounds__(Cfg<D>::NT) void ials_gram_scaled_blocks_kernel(GramScaledArgs sa) {
+    using C = Cfg<D>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ials_smem[];
+    float* sm = reinterpret_cast<float*>(ials_smem);
+    const GramArgs& a = sa.g;
+    const int64_t k0 = (int64_t)blockIdx.x * PDA_IALS_GRAM_ROWS;
+    const int64_t k1 = k0 + PDA_IALS_GRAM_ROWS < (int64_t)a.n_rows ? k0 + PDA_IALS_GRAM_ROWS : (int64_t)a.n_rows;
+    ials_accumulate<D, false, true>(nullptr, a.Z, (unsigned)a.n_rows, k0, k1, sm, sa.scale);
     float* dst = a.partials + (size_t)blockIdx.x * C::SLOT;
     for (int q = threadIdx.x; q < D * D; q += C::NT) dst[q] = sm[(q / D) * C::LD + q % D];
 }
@@ -336,6 +417,29 @@ int launch_half_sweep(const IalsArgs& a, size_t n_work, size_t n_long, hipStream
 }
 
 template <int D>
+int launch_half_sweep_rowalpha(const IalsRowAlphaArgs& ra, size_t n_work, size_t n_long, hipStream_t s) {
+    using C = Cfg<D>;
+    static int set_rows = 0, set_long = 0;
+    if (!ials_lds(&ials_rows_rowalpha_kernel<D>, C::LDS_BYTES, &set_rows) || !ials_lds(&ials_long_rows_rowalpha_kernel<D>, C::LDS_BYTES, &set_long))
+        return PDA_ERR_LAUNCH;
+    hipLaunchKernelGGL(ials_rows_rowalpha_kernel<D>, dim3((unsigned)n_work), dim3(C::NT), C::LDS_BYTES, s, ra);
+    if (n_long != 0) hipLaunchKernelGGL(ials_long_rows_rowalpha_kernel<D>, dim3((unsigned)n_long), dim3(C::NT), C::LDS_BYTES, s, ra);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
+template <int D>
+int launch_gram_scaled(const GramScaledArgs& sa, hipStream_t s) {
+    using C = Cfg<D>;
+    static int set_gram = 0;
+    if (!ials_lds(&ials_gram_scaled_blocks_kernel<D>, C::LDS_BYTES, &set_gram)) return PDA_ERR_LAUNCH;
+    hipLaunchKernelGGL(ials_gram_scaled_blocks_kernel<D>, dim3((unsigned)sa.g.n_blocks), dim3(C::NT), C::LDS_BYTES, s, sa);
+    hipLaunchKernelGGL(ials_gram_sum_kernel<D>, dim3((unsigned)((D * D + 255) / 256)), dim3(256), 0, s, sa.g);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
+template <int D>
 int launch_gram(const GramArgs& a, hipStream_t s) {
     using C = Cfg<D>;
     static int set_gram = 0;
@@ -389,6 +493,48 @@ extern "C" int pda_ials_half_sweep_f32(const int64_t* indptr, const int32_t* ind
         case 32: return launch_half_sweep<32>(a, n_work, n_long, s);
         case 64: return launch_half_sweep<64>(a, n_work, n_long, s);
         default: return launch_half_sweep<128>(a, n_work, n_long, s);
+    }
+}
+
+extern "C" int pda_ials_gram_scaled_f32(const float* Z, const float* scale_row, size_t n_rows, int d, float* G, float* workspace,
+                                        size_t workspace_floats, void* stream) {
+    if (!Z || !scale_row || !G || !workspace) return PDA_ERR_ARG;
+    if (n_rows == 0 || n_rows > 0x7FFFFFFFu) return PDA_ERR_ARG;
+    if (G == Z || G == scale_row) return PDA_ERR_ARG;
+    if (!ials_d_ok(d) && d != 256) return PDA_ERR_UNSUPPORTED;
+    const size_t n_blocks = (n_rows + PDA_IALS_GRAM_ROWS - 1) / PDA_IALS_GRAM_ROWS;
+    if (workspace_floats < n_blocks * ((size_t)d * d + d)) return PDA_ERR_ARG;
+    if (d == 256) return pda_ialspp_gram256_scaled_f32(Z, scale_row, n_rows, G, workspace, workspace_floats, stream);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const GramScaledArgs sa{GramArgs{Z, G, workspace, n_rows, n_blocks}, scale_row};
+    switch (d) {
+        case 32: return launch_gram_scaled<32>(sa, s);
+        case 64: return launch_gram_scaled<64>(sa, s);
+        default: return launch_gram_scaled<128>(sa, s);
+    }
+}
+
+extern "C" int pda_ials_half_sweep_rowalpha_f32(const int64_t* indptr, const int32_t* indices, size_t n_rows, size_t nnz, const int64_t* work,
+                                                size_t n_work, const int64_t* long_rows, size_t n_long, size_t n_slots, const float* Z, size_t n_z,
+                                                const float* G, int d, const float* alpha_row, const float* lam_row, float* X_out,
+                                                int32_t* fail_count, float* dbg_normal, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!indptr || !work || !Z || !G || !alpha_row || !lam_row || !X_out || !fail_count) return PDA_ERR_ARG;
+    if (nnz != 0 && !indices) return PDA_ERR_ARG;
+    if (n_rows == 0 || n_rows > 0x7FFFFFFFu || n_z == 0 || n_z > 0x7FFFFFFFu || nnz > ((size_t)1 << 40)) return PDA_ERR_ARG;
+    if (n_work == 0 || n_work > 0x7FFFFFFFu) return PDA_ERR_ARG;
+    if (X_out == Z || X_out == G || X_out == alpha_row) return PDA_ERR_ARG;
+    if (n_long > n_rows || (n_long != 0 && (!long_rows || n_slots < 2 * n_long)) || (n_long == 0 && n_slots != 0)) return PDA_ERR_ARG;
+    if (n_work < n_slots || n_slots > 0x7FFFFFFFu) return PDA_ERR_ARG;      // one entry per chunk of a cut row, at least
+    if (!ials_d_ok(d)) return PDA_ERR_UNSUPPORTED;
+    if (n_slots != 0 && (!workspace || workspace_bytes < pda_ials_workspace_bytes(n_slots, d))) return PDA_ERR_ARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const IalsRowAlphaArgs ra{IalsArgs{indptr, indices, work, long_rows, Z, G, lam_row, X_out, fail_count, dbg_normal,
+                                       reinterpret_cast<float*>(workspace), n_rows, nnz, n_slots, (unsigned)n_z, 0.f},
+                              alpha_row};
+    switch (d) {
+        case 32: return launch_half_sweep_rowalpha<32>(ra, n_work, n_long, s);
+        case 64: return launch_half_sweep_rowalpha<64>(ra, n_work, n_long, s);
+        default: return launch_half_sweep_rowalpha<128>(ra, n_work, n_long, s);
     }
 }
 

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "pda_common.h"
 #include "pda_hip_ialspp.h"
+#include "pda_hip_ials_itemw.h"
 
 namespace {
 
@@ -171,19 +172,22 @@ __device__ __forceinline__ void pp_accumulate(const PpArgs& a, int64_t k0, int64
 }
 
 // The tail of a row whose sums stand in sm: the G and lam_row terms, H = L L^T in place, the two substitutions, x_{r,pi} -= delta.
-// Leaves delta in sx (NaN after a failed pivot), behind a barrier.
-template <int K>
-__device__ __forceinline__ void pp_finish_solve(const PpArgs& a, int64_t row, float* sm) {
+// Leaves delta in sx (NaN after a failed pivot), behind a barrier.  alpha is a.alpha0, or with ROWALPHA the row's own alpha_row[row]
+// (pda_hip_ials_itemw.h).
+template <int K, bool ROWALPHA = false>
+__device__ __forceinline__ void pp_finish_solve(const PpArgs& a, int64_t row, float* sm, const float* alpha_row = nullptr) {
     using C = Cfg<K>;
     const Lds<K> L(sm);
     const int tid = threadIdx.x, d = a.d, p0 = a.p0;
     const float lam = a.lam_row[row];
+    float ar = 0.f;
+    if constexpr (ROWALPHA) ar = alpha_row[row];
     float* dbg = a.dbg != nullptr ? a.dbg + (size_t)row * C::SLOT : nullptr;
     if (tid == 0) *L.sflag = 0;
     for (int q = tid; q < d; q += C::NT) L.sxr[q] = a.X[(size_t)row * d + q];
     for (int q = tid; q < K * K; q += C::NT) {
         const int i = q / K, j = q % K;
-        float v = L.sA[i * C::LD + j] + a.alpha0 * a.G[(size_t)(p0 + i) * d + p0 + j];
+        float v = L.sA[i * C::LD + j] + (ROWALPHA ? ar : a.alpha0) * a.G[(size_t)(p0 + i) * d + p0 + j];
         if (i == j) v = v + lam;
         L.sA[i * C::LD + j] = v;
         if (dbg != nullptr) dbg[q] = v;
@@ -200,7 +204,7 @@ __device__ __forceinline__ void pp_finish_solve(const PpArgs& a, int64_t row, fl
         float t = 0.f;
 #pragma unroll
         for (int q = 0; q < C::Q; ++q) t = t + L.sp[q * K + tid];
-        const float g = (L.sb[tid] + a.alpha0 * t) + lam * L.sxr[p0 + tid];
+        const float g = (L.sb[tid] + (ROWALPHA ? ar : a.alpha0) * t) + lam * L.sxr[p0 + tid];
         L.sb[tid] = g;
         if (dbg != nullptr) dbg[K * K + tid] = g;
     }
@@ -320,6 +324,63 @@ __global__ __launch_bounds__(Cfg<K>::NT) void pp_long_rows_kernel(PpArgs a) {
     }
 }
 
+// The same two kernels with alpha_row (pda_ialspp_block_pass_rowalpha_f32): their text is that of the two above with the tail's ROWALPHA flag
+// set.  They are kernels of their own, with their own argument struct, so that the two above keep their argument layout and their
+// instructions (a body shared through a function of both reordered theirs); a.alpha0 is not read here.  pp_chunk_update_kernel reads no
+// alpha: it serves both.
+struct PpRowAlphaArgs {
+    PpArgs a;
+    const float* alpha_row;     // [n_rows]
+};
+
+template <int K>
+__global__ __launch_bounds__(Cfg<K>::NT) void pp_rows_rowalpha_kernel(PpRowAlphaArgs ra) {
+    using C = Cfg<K>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char pp_smem[];
+    float* sm = reinterpret_cast<float*>(pp_smem);
+    const PpArgs& a = ra.a;
+    const int64_t* wk = a.work + 4 * (size_t)blockIdx.x;
+    const int64_t row = wk[0], k0 = wk[1], k1 = wk[2], slot = wk[3];
+    if (!pp_entry_ok(a, row, k0, k1, slot)) return;     // (uniform)
+    pp_accumulate<K>(a, k0, k1, sm);
+    if (slot >= 0) {
+        float* dst = a.slots + (size_t)slot * C::SLOT;
+        for (int q = threadIdx.x; q < K * K; q += C::NT) dst[q] = sm[(q / K) * C::LD + q % K];
+        if (threadIdx.x < K) dst[K * K + threadIdx.x] = sm[K * C::LD + threadIdx.x];
+        return;
+    }
+    pp_finish_solve<K, true>(a, row, sm, ra.alpha_row);
+    pp_update_e<K>(a, k0, k1, Lds<K>(sm).sx);
+}
+
+template <int K>
+__global__ __launch_bounds__(Cfg<K>::NT) void pp_long_rows_rowalpha_kernel(PpRowAlphaArgs ra) {
+    using C = Cfg<K>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char pp_smem[];
+    float* sm = reinterpret_cast<float*>(pp_smem);
+    const PpArgs& a = ra.a;
+    const int64_t* lr = a.long_rows + 3 * (size_t)blockIdx.x;
+    const int64_t row = lr[0], s0 = lr[1], n = lr[2];
+    if (row < 0 || (uint64_t)row >= a.n_rows || s0 < 0 || n < 0 || (uint64_t)s0 + (uint64_t)n > a.n_slots) return;   // (uniform)
+    const float* src = a.slots + (size_t)s0 * C::SLOT;
+    for (int q = threadIdx.x; q < K * K; q += C::NT) {
+        float v = 0.f;
+        for (int64_t j = 0; j < n; ++j) v = v + src[(size_t)j * C::SLOT + q];
+        sm[(q / K) * C::LD + q % K] = v;
+    }
+    if (threadIdx.x < K) {
+        float v = 0.f;
+        for (int64_t j = 0; j < n; ++j) v = v + src[(size_t)j * C::SLOT + K * K + threadIdx.x];
+        sm[K * C::LD + threadIdx.x] = v;
+    }
+    __syncthreads();
+    pp_finish_solve<K, true>(a, row, sm, ra.alpha_row);
+    if (threadIdx.x < K) {
+        const float dl = Lds<K>(sm).sx[threadIdx.x];
+        for (int64_t j = 0; j < n; ++j) a.delta_ws[(size_t)(s0 + j) * K + threadIdx.x] = dl;
+    }
+}
+
 // the chunks of the cut rows once more: their e
 template <int K>
 __global__ __launch_bounds__(Cfg<K>::NT) void pp_chunk_update_kernel(PpArgs a) {
@@ -388,6 +449,46 @@ __global__ __launch_bounds__(64) void pp_gram_tiles_kernel(GramArgs a) {
         if (r < a.n_rows) {
             av = a.Z[r * D + 32 * ti + i];
             bv = a.Z[r * D + 32 * tj + i];
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+    }
+    float* dst = a.partials + (size_t)blockIdx.x * SLOT;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int r = acc_row(reg, h);
+        dst[(size_t)(32 * ti + r) * D + 32 * tj + i] = acc[reg];
+        if (ti != tj) dst[(size_t)(32 * tj + i) * D + 32 * ti + r] = acc[reg];
+    }
+}
+
+// pda_ials_gram_scaled_f32 at d = 256 (pda_hip_ials_itemw.h): the kernel above with the row r entering as fl(scale[r] z_r[j]), one more
+// 4-byte load per row fetch.  A kernel of its own for the reason given at pp_rows_rowalpha_kernel.
+struct GramScaledArgs {
+    GramArgs g;
+    const float* scale;     // [n_rows]
+};
+
+template <int D>
+__global__ __launch_bounds__(64) void pp_gram_tiles_scaled_kernel(GramScaledArgs sa) {
+    constexpr size_t SLOT = (size_t)D * D + D;
+    const GramArgs& a = sa.g;
+    const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
+    const int t = blockIdx.y;
+    int ti = 0;
+    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    const int tj = t - ti * (ti + 1) / 2;
+    const size_t r0 = (size_t)blockIdx.x * PDA_IALS_GRAM_ROWS;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll 8
+    for (int kp = 0; kp < PDA_IALS_GRAM_ROWS / 2; ++kp) {
+        const size_t r = r0 + 2 * kp + h;
+        float av = 0.f, bv = 0.f;
+        if (r < a.n_rows) {
+            const float sc = sa.scale[r];
+            av = a.Z[r * D + 32 * ti + i] * sc;
+            bv = a.Z[r * D + 32 * tj + i] * sc;
         }
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
     }
@@ -484,6 +585,21 @@ int launch_block_pass(const PpArgs& a, size_t n_work, size_t n_long, hipStream_t
     return PDA_OK;
 }
 
+template <int K>
+int launch_block_pass_rowalpha(const PpRowAlphaArgs& ra, size_t n_work, size_t n_long, hipStream_t s) {
+    using C = Cfg<K>;
+    static int set_rows = 0, set_long = 0;
+    if (!pp_lds(&pp_rows_rowalpha_kernel<K>, C::LDS_BYTES, &set_rows) || !pp_lds(&pp_long_rows_rowalpha_kernel<K>, C::LDS_BYTES, &set_long))
+        return PDA_ERR_LAUNCH;
+    hipLaunchKernelGGL(pp_rows_rowalpha_kernel<K>, dim3((unsigned)n_work), dim3(C::NT), C::LDS_BYTES, s, ra);
+    if (n_long != 0) {
+        hipLaunchKernelGGL(pp_long_rows_rowalpha_kernel<K>, dim3((unsigned)n_long), dim3(C::NT), C::LDS_BYTES, s, ra);
+        hipLaunchKernelGGL(pp_chunk_update_kernel<K>, dim3((unsigned)n_work), dim3(C::NT), 0, s, ra.a);
+    }
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
+}
+
 }  // namespace
 
 extern "C" int pda_ialspp_predict_f32(const int64_t* indptr, const int32_t* indices, size_t n_rows, size_t nnz, const float* X, const float* Z,
@@ -532,6 +648,50 @@ extern "C" int pda_ialspp_block_pass_f32(const int64_t* indptr, const int32_t* i
         case 64: return launch_block_pass<64>(a, n_work, n_long, s);
         default: return launch_block_pass<128>(a, n_work, n_long, s);
     }
+}
+
+extern "C" int pda_ialspp_block_pass_rowalpha_f32(const int64_t* indptr, const int32_t* indices, const int64_t* pair_perm, size_t n_rows, size_t nnz,
+                                                  const int64_t* work, size_t n_work, const int64_t* long_rows, size_t n_long, size_t n_slots,
+                                                  const float* Z, size_t n_z, const float* G, int d, int k, int p0, const float* alpha_row,
+                                                  const float* lam_row, float* X, float* e, int32_t* fail_count, float* dbg, float* slots,
+                                                  size_t slot_floats, float* delta_ws, size_t delta_floats, void* stream) {
+    if (!indptr || !work || !Z || !G || !alpha_row || !lam_row || !X || !fail_count) return PDA_ERR_ARG;
+    if (nnz != 0 && (!indices || !e)) return PDA_ERR_ARG;
+    if (n_rows == 0 || n_rows > 0x7FFFFFFFu || n_z == 0 || n_z > 0x7FFFFFFFu || nnz > ((size_t)1 << 40)) return PDA_ERR_ARG;
+    if (n_work == 0 || n_work > 0x7FFFFFFFu) return PDA_ERR_ARG;
+    if (X == Z || X == G || X == alpha_row || (e != nullptr && (e == X || e == Z || e == G || e == alpha_row))) return PDA_ERR_ARG;
+    if (n_long > n_rows || (n_long != 0 && (!long_rows || n_slots < 2 * n_long)) || (n_long == 0 && n_slots != 0)) return PDA_ERR_ARG;
+    if (n_work < n_slots || n_slots > 0x7FFFFFFFu) return PDA_ERR_ARG;      // one entry per chunk of a cut row, at least
+    if (p0 < 0) return PDA_ERR_ARG;
+    if (!pp_d_ok(d) || !pp_k_ok(k)) return PDA_ERR_UNSUPPORTED;
+    if (d % k != 0 || p0 % k != 0 || p0 >= d) return PDA_ERR_ARG;
+    if (n_slots != 0 && (!slots || !delta_ws || slot_floats < n_slots * PDA_IALSPP_SLOT_FLOATS(k) ||
+                         delta_floats < PDA_IALSPP_DELTA_FLOATS(n_slots, k))) return PDA_ERR_ARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const PpRowAlphaArgs ra{PpArgs{indptr, indices, pair_perm, work, long_rows, Z, G, lam_row, X, e, fail_count, dbg, slots, delta_ws,
+                                   n_rows, nnz, n_slots, (unsigned)n_z, d, p0, 0.f},
+                            alpha_row};
+    switch (k) {
+        case 32: return launch_block_pass_rowalpha<32>(ra, n_work, n_long, s);
+        case 64: return launch_block_pass_rowalpha<64>(ra, n_work, n_long, s);
+        default: return launch_block_pass_rowalpha<128>(ra, n_work, n_long, s);
+    }
+}
+
+extern "C" int pda_ialspp_gram256_scaled_f32(const float* Z, const float* scale_row, size_t n_rows, float* G, float* workspace, size_t workspace_floats,
+                                             void* stream) {
+    if (!Z || !scale_row || !G || !workspace) return PDA_ERR_ARG;
+    if (n_rows == 0 || n_rows > 0x7FFFFFFFu) return PDA_ERR_ARG;
+    if (G == Z || G == scale_row) return PDA_ERR_ARG;
+    if (workspace_floats < PDA_IALSPP_GRAM_WS_FLOATS(n_rows, 256)) return PDA_ERR_ARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t n_blocks = (n_rows + PDA_IALS_GRAM_ROWS - 1) / PDA_IALS_GRAM_ROWS;
+    const GramScaledArgs sa{GramArgs{Z, G, workspace, n_rows, n_blocks}, scale_row};
+    constexpr int TN = 256 / 32;
+    hipLaunchKernelGGL(pp_gram_tiles_scaled_kernel<256>, dim3((unsigned)n_blocks, TN * (TN + 1) / 2), dim3(64), 0, s, sa);
+    hipLaunchKernelGGL(pp_gram_sum_kernel<256>, dim3(256 * 256 / 256), dim3(256), 0, s, sa.g);
+    PDA_CHECK_LAUNCH();
+    return PDA_OK;
 }
 
 extern "C" int pda_ialspp_gram_f32(const float* Z, size_t n_rows, int d, float* G, float* workspace, size_t workspace_floats, void* stream) {

@@ -1610,6 +1610,9 @@ def check_ials(args):
     nu = float(getattr(args, "ials_nu", 1.0))
     if not 0.0 <= nu <= 1.0:
         raise ValueError("--ials_nu must lie in 0 .. 1, got %s" % (args.ials_nu,))
+    beta = float(getattr(args, "ials_item_power", 0.0))
+    if not (math.isfinite(beta) and 0.0 <= beta <= ops.IALS_ITEM_POWER_MAX):
+        raise ValueError("--ials_item_power must be a finite number in 0 .. %g, got %s" % (ops.IALS_ITEM_POWER_MAX, args.ials_item_power))
 
 
 class IALSMF(BPRMF):
@@ -1619,7 +1622,9 @@ class IALSMF(BPRMF):
     set_train_pairs: the train pairs -- rebuilt from the data, never stored in a checkpoint; a model that is only restored and evaluated
     needs none.  --ials_solver block (iALS++, DESIGN.md 5v, include/pda_hip_ialspp.h) replaces the two half-sweeps by one exact step per block
     of --ials_block coordinates, users then items, at --embed_size up to 256; the tables keep their usual initialisation, which matters there
-    (a block step starts from x), and the prediction cache is rebuilt every epoch and never checkpointed."""
+    (a block step starts from x), and the prediction cache is rebuilt every epoch and never checkpointed.  --ials_item_power beta > 0 (DESIGN.md
+    5y, include/pda_hip_ials_itemw.h) weighs the unobserved pairs of item i by alpha0 w_i, w_i ~ (c_i + 1)^beta with mean 1, in either solver:
+    the weights are rebuilt from the train pairs with the graph and never checkpointed."""
 
     def __init__(self, args, data_config, use_dataset_api=False, users_api=None, pos_items_api=None, neg_items_api=None, **kw):
         check_ials(args)
@@ -1634,12 +1639,17 @@ class IALSMF(BPRMF):
         self.ials_nu = float(getattr(args, "ials_nu", 1.0))
         self.ials_solver = getattr(args, "ials_solver", "exact")
         self.ials_block = int(getattr(args, "ials_block", 32))
+        self.ials_item_power = float(getattr(args, "ials_item_power", 0.0))
         self.graph = None
         if data_config.get("gcn_train_pairs") is not None:
             self.set_train_pairs(*data_config["gcn_train_pairs"])
 
     def set_train_pairs(self, users, items):
-        self.graph = ops.IalsGraph(users, items, self.n_users, self.n_items, self.device, lam=self.decay, alpha0=self.ials_alpha0, nu=self.ials_nu)
+        self.graph = ops.IalsGraph(users, items, self.n_users, self.n_items, self.device, lam=self.decay, alpha0=self.ials_alpha0, nu=self.ials_nu,
+                                   item_power=self.ials_item_power)
+        iw = self.graph.item_weights
+        if iw is not None:
+            print("||--- ials item_power=%g w_min=%.6g w_max=%.6g" % (self.ials_item_power, float(iw.w.min()), float(iw.w.max())), flush=True)
 
     def train_step(self, *a, **kw):
         raise NotImplementedError("--train ials has no batch step: train_epoch() runs the two half-sweeps")
@@ -1668,4 +1678,6 @@ class IALSMF(BPRMF):
         sd.update(optimizer="ials", ials_alpha0=self.ials_alpha0, ials_nu=self.ials_nu)
         if self.ials_solver == "block":     # (an exact-solver run's state dict stays as it was)
             sd.update(ials_solver="block", ials_block=self.ials_block)
+        if self.ials_item_power != 0.0:     # (an unweighted run's state dict stays as it was)
+            sd.update(ials_item_power=self.ials_item_power)
         return sd

@@ -4029,6 +4029,58 @@ def ials_lam_row(deg, n_other: int, lam: float, alpha0: float, nu: float):
     return (lam * np.power(np.asarray(deg, dtype=np.float64) + alpha0 * float(n_other), nu)).astype(np.float32)
 
 
+# item-weighted iALS (include/pda_hip_ials_itemw.h): --ials_item_power
+IALS_ITEM_POWER_MAX = 4.0
+
+
+def check_ials_item_power(power) -> float:
+    power = float(power)
+    if not (math.isfinite(power) and 0.0 <= power <= IALS_ITEM_POWER_MAX):
+        raise ValueError(f"iALS: the item power must be a finite number in [0, {IALS_ITEM_POWER_MAX:g}], got {power}")
+    return power
+
+
+def ials_item_weight_arrays(counts, power: float, alpha0: float) -> dict:
+    """The per-item inputs of the item-weighted model on the host (numpy; no GPU needed), from the items' distinct train pairs c_i:
+    q = (c + 1)^power / sum (float64, negpop_weights), scale = fl32(sqrt(n_items q)), w = float64(scale)^2 (THE weight of the model, mean 1
+    up to rounding) and alpha_row = fl32(alpha0 w).  power 0: scale = w = 1 exactly and alpha_row = fl32(alpha0)."""
+    import numpy as np
+    power = check_ials_item_power(power)
+    alpha0 = float(alpha0)
+    if not (alpha0 >= 0.0 and math.isfinite(alpha0)):
+        raise ValueError(f"iALS: alpha0 must be a finite number >= 0, got {alpha0}")
+    counts = np.asarray(counts)
+    if counts.ndim != 1 or counts.size < 1 or not (counts >= 0).all():
+        raise ValueError("iALS item weights: one count >= 0 per item, at least one item")
+    p = negpop_weights(counts, power)
+    q = p / p.sum()
+    scale = np.sqrt(float(p.size) * q).astype(np.float32)
+    w = scale.astype(np.float64) ** 2
+    alpha_row = (alpha0 * w).astype(np.float32)
+    if not (np.isfinite(scale).all() and (scale > 0).all() and np.isfinite(alpha_row).all()):
+        raise ValueError("iALS item weights: the weights left the range of float32")
+    return dict(q=q, scale=scale, w=w, alpha_row=alpha_row)
+
+
+class IalsItemWeights:
+    """The per-item weights of an item-weighted iALS graph (ials_item_weight_arrays): `w` float64 [n_items] on the host, `scale` and
+    `alpha_row` float32 [n_items] on the device (host_scale, host_alpha_row: their host copies)."""
+
+    def __init__(self, counts, power: float, alpha0: float, device):
+        h = ials_item_weight_arrays(counts, power, alpha0)
+        self.power, self.alpha0 = float(power), float(alpha0)
+        self.w, self.host_scale, self.host_alpha_row = h["w"], h["scale"], h["alpha_row"]
+        self.scale = torch.from_numpy(h["scale"]).to(device)
+        self.alpha_row = torch.from_numpy(h["alpha_row"]).to(device)
+
+
+def ials_lam_row_items(deg, n_users: int, lam: float, alpha0: float, nu: float, w):
+    """The item side's lam_row of the item-weighted model: fl32(lambda * float64(n_i + alpha0 w_i n_users)^nu); w all 1 is ials_lam_row."""
+    import numpy as np
+    lam, alpha0, nu = check_ials_params(lam, alpha0, nu)
+    return (lam * np.power(np.asarray(deg, dtype=np.float64) + alpha0 * np.asarray(w, dtype=np.float64) * float(n_users), nu)).astype(np.float32)
+
+
 def ials_graph_arrays(users, items, n_users: int, n_items: int, chunk: int = IALS_CHUNK) -> dict:
     """Both CSR directions and both work lists of include/pda_hip_ials.h from the train pairs, on the host (numpy; no GPU needed): what
     gcn_graph_arrays yields for the stacked graph, taken apart into the user side (rows: users, columns: item ids) and the item side (rows:
@@ -4100,16 +4152,25 @@ class IalsGraph:
     """The train pairs of an iALS model on the device, built once (ials_graph_arrays): both CSRs, both work lists, the degrees and lam_row of
     both sides for the given (lambda, alpha0, nu).  Ids and shapes are validated here, on the host, once: the kernels trust the graph.  It also
     owns what the calls write besides the tables: the workspace, the Gram matrix, the per-row loss terms and the failed-pivot counter, one set
-    per row width."""
+    per row width.  item_power > 0 (include/pda_hip_ials_itemw.h): the graph also holds item_weights, an IalsItemWeights from the items' degrees,
+    the item side's lam_row follows from its w, and every call on the graph that is not told otherwise runs the item-weighted model; at 0
+    item_weights is None and nothing else is built or called."""
 
     def __init__(self, users, items, n_users: int, n_items: int, device, *, lam: float, alpha0: float = 0.1, nu: float = 1.0,
-                 chunk: int = IALS_CHUNK):
+                 chunk: int = IALS_CHUNK, item_power: float = 0.0):
         self.lam, self.alpha0, self.nu = check_ials_params(lam, alpha0, nu)
+        self.item_power = check_ials_item_power(item_power)
         h = self.host = ials_graph_arrays(users, items, n_users, n_items, chunk)
         self.n_users, self.n_items, self.nnz, self.chunk = h["n_users"], h["n_items"], h["nnz"], h["chunk"]
         self.device = torch.device(device)
         self.user = IalsSide(h["user"], ials_lam_row(h["user"]["deg"], self.n_items, self.lam, self.alpha0, self.nu), self.device)
-        self.item = IalsSide(h["item"], ials_lam_row(h["item"]["deg"], self.n_users, self.lam, self.alpha0, self.nu), self.device)
+        self.item_weights = None
+        if self.item_power > 0.0:
+            self.item_weights = IalsItemWeights(h["item"]["deg"], self.item_power, self.alpha0, self.device)
+            lam_items = ials_lam_row_items(h["item"]["deg"], self.n_users, self.lam, self.alpha0, self.nu, self.item_weights.w)
+        else:
+            lam_items = ials_lam_row(h["item"]["deg"], self.n_users, self.lam, self.alpha0, self.nu)
+        self.item = IalsSide(h["item"], lam_items, self.device)
         self._bufs = {}
 
     def side(self, side) -> IalsSide:
@@ -4144,6 +4205,22 @@ class IalsGraph:
         return self._bufs[d]
 
 
+def _ials_row_vector(t, n_rows: int, what: str):
+    t = _need(t, torch.float32, what)
+    if t.dim() != 1 or t.numel() != n_rows:
+        raise ValueError(f"iALS: {what} is float32 [{n_rows}], got {tuple(t.shape)}")
+    return t
+
+
+def _ials_graph_inputs(graph: "IalsGraph", side: str, alpha_row):
+    """(scale for the Gram matrix of the table held fixed | None, alpha_row | None) of a call on `side`: what the caller handed over, or on an
+    item-weighted graph the graph's own -- the user side solves against G_w, the item side with its alpha_row."""
+    iw = graph.item_weights
+    if alpha_row is None and iw is not None and side == "item":
+        alpha_row = iw.alpha_row
+    return (iw.scale if iw is not None and side == "user" else None), alpha_row
+
+
 def _ials_table(t, n_rows: int, what: str):
     t = _need(t, torch.float32, what)
     if t.dim() != 2 or t.shape[0] != n_rows or t.shape[1] not in IALS_EMBED_SIZES:
@@ -4151,8 +4228,9 @@ def _ials_table(t, n_rows: int, what: str):
     return t
 
 
-def ials_gram(Z, G=None, workspace=None):
-    """pda_ials_gram_f32: G = Z^T Z, float32 [d, d], partial Gram matrices over blocks of IALS_GRAM_ROWS rows added in block order."""
+def ials_gram(Z, G=None, workspace=None, scale=None):
+    """pda_ials_gram_f32: G = Z^T Z, float32 [d, d], partial Gram matrices over blocks of IALS_GRAM_ROWS rows added in block order.
+    scale float32 [n] (pda_ials_gram_scaled_f32): the row c enters as fl(scale[c] z_c), G = sum (s z)(s z)^T."""
     Z = _need(Z, torch.float32, "Z")
     if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] not in IALS_EMBED_SIZES:
         raise ValueError(f"iALS: Z is float32 [n >= 1, d] with d one of {IALS_EMBED_SIZES}, got {tuple(Z.shape)}")
@@ -4166,15 +4244,24 @@ def ials_gram(Z, G=None, workspace=None):
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=Z.device)
     if _need(workspace, torch.uint8, "workspace").numel() < nbytes:
         raise ValueError(f"iALS: the Gram workspace holds {nbytes} bytes")
+    if scale is not None:
+        scale = _ials_row_vector(scale, n, "scale")
+        check(_lib.load().pda_ials_gram_scaled_f32(ptr(Z), ptr(scale), n, d, ptr(G), ptr(workspace), workspace.numel() // 4, stream_ptr()),
+              "pda_ials_gram_scaled_f32")
+        return G
     check(_lib.load().pda_ials_gram_f32(ptr(Z), n, d, ptr(G), ptr(workspace), workspace.numel(), stream_ptr()), "pda_ials_gram_f32")
     return G
 
 
-def ials_half_sweep(graph: IalsGraph, side: str, Z, X_out, *, G=None, work: Optional[IalsWork] = None, dbg_normal=None, fail_count=None):
+def ials_half_sweep(graph: IalsGraph, side: str, Z, X_out, *, G=None, work: Optional[IalsWork] = None, dbg_normal=None, fail_count=None,
+                    alpha_row=None):
     """pda_ials_half_sweep_f32: X_out[r] = A_r^{-1} b_r for the rows of `work` (default: every row of the side), Z the other table held fixed.
     G: Z^T Z (computed here into the graph's buffer when missing).  dbg_normal float32 [n_rows, d * d + d]: receives (A_r, b_r) as they enter
-    the factorisation.  fail_count int32 [1] (default: the graph's own) is raised once per row with a failed pivot.  Returns X_out."""
+    the factorisation.  fail_count int32 [1] (default: the graph's own) is raised once per row with a failed pivot.  alpha_row float32 [n_rows]
+    (pda_ials_half_sweep_rowalpha_f32): the row's own weight in place of alpha0.  On an item-weighted graph the user side's G defaults to G_w
+    and the item side's alpha_row to the graph's own.  Returns X_out."""
     s = graph.side(side)
+    gram_scale, alpha_row = _ials_graph_inputs(graph, side, alpha_row)
     Z = _ials_table(Z, s.n_other, "Z (the table held fixed)")
     X_out = _ials_table(X_out, s.n_rows, "X_out")
     d = Z.shape[1]
@@ -4182,7 +4269,7 @@ def ials_half_sweep(graph: IalsGraph, side: str, Z, X_out, *, G=None, work: Opti
         raise ValueError("iALS: X_out and Z are two tables of one width")
     b = graph.buffers(d)
     if G is None:
-        G = ials_gram(Z, b["G"], b["ws"])
+        G = ials_gram(Z, b["G"], b["ws"], gram_scale)
     if _need(G, torch.float32, "G").shape != (d, d):
         raise ValueError("iALS: G is float32 [d, d]")
     w = s.all_rows if work is None else work
@@ -4197,6 +4284,15 @@ def ials_half_sweep(graph: IalsGraph, side: str, Z, X_out, *, G=None, work: Opti
     ws = b["ws"]
     if ws.numel() < nbytes:
         ws = b["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=graph.device)
+    if alpha_row is not None:
+        alpha_row = _ials_row_vector(alpha_row, s.n_rows, "alpha_row")
+        check(_lib.load().pda_ials_half_sweep_rowalpha_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(w.work), w.n_work,
+                                                           ptr(w.long_rows) if w.n_long else None, w.n_long, w.n_slots, ptr(Z), s.n_other, ptr(G), d,
+                                                           ptr(alpha_row), ptr(s.lam_row), ptr(X_out), ptr(fail), ptr(dbg_normal),
+                                                           ptr(ws) if w.n_slots else None, ws.numel() if w.n_slots else 0, stream_ptr()),
+              "pda_ials_half_sweep_rowalpha_f32")
+        mark_modified(X_out)
+        return X_out
     check(_lib.load().pda_ials_half_sweep_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(w.work), w.n_work,
                                               ptr(w.long_rows) if w.n_long else None, w.n_long, w.n_slots, ptr(Z), s.n_other, ptr(G), d,
                                               float(graph.alpha0), ptr(s.lam_row), ptr(X_out), ptr(fail), ptr(dbg_normal),
@@ -4210,14 +4306,14 @@ def ials_loss(graph: IalsGraph, X, Y, *, G=None):
     """The objective of include/pda_hip_ials.h at the tables (X, Y) -> float64 [3] on the device, (L, fit, reg): fit = the squared errors of the
     observed pairs + alpha0 x the squared scores of all pairs, reg = the regulariser of both sides, L = fit + reg.  pda_ials_loss_f32 writes the
     three terms of every user row; they are summed here in float64 by torch reductions, as is the item side's regulariser.  G: Y^T Y (computed
-    here when missing).  No host read."""
+    here when missing; G_w on an item-weighted graph, whose objective weighs the scores of item i by alpha0 w_i).  No host read."""
     X, Y = _ials_table(X, graph.n_users, "X"), _ials_table(Y, graph.n_items, "Y")
     d = X.shape[1]
     if Y.shape[1] != d:
         raise ValueError("iALS: X and Y share the embedding width")
     b = graph.buffers(d)
     if G is None:
-        G = ials_gram(Y, b["G"], b["ws"])
+        G = ials_gram(Y, b["G"], b["ws"], _ials_graph_inputs(graph, "user", None)[0])
     s = graph.user
     check(_lib.load().pda_ials_loss_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, s.n_rows, s.nnz, ptr(X), ptr(Y), graph.n_items, ptr(G), d,
                                         ptr(s.lam_row), ptr(b["rows"]), stream_ptr()), "pda_ials_loss_f32")
@@ -4305,9 +4401,9 @@ def _ialspp_table(t, n_rows: int, what: str):
     return t
 
 
-def ialspp_gram(Z, G=None, workspace=None):
+def ialspp_gram(Z, G=None, workspace=None, scale=None):
     """pda_ialspp_gram_f32: G = Z^T Z, float32 [d, d], at the four embedding sizes; workspace float32 of one slot of d * d + d per block of
-    IALS_GRAM_ROWS rows."""
+    IALS_GRAM_ROWS rows.  scale float32 [n] (pda_ials_gram_scaled_f32): the row c enters as fl(scale[c] z_c)."""
     Z = _need(Z, torch.float32, "Z")
     if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] not in IALSPP_EMBED_SIZES:
         raise ValueError(f"iALS++: Z is float32 [n >= 1, d] with d one of {IALSPP_EMBED_SIZES}, got {tuple(Z.shape)}")
@@ -4321,6 +4417,11 @@ def ialspp_gram(Z, G=None, workspace=None):
         workspace = torch.zeros(need, dtype=torch.float32, device=Z.device)
     if _need(workspace, torch.float32, "workspace").numel() < need:
         raise ValueError(f"iALS++: the Gram workspace holds {need} floats")
+    if scale is not None:
+        scale = _ials_row_vector(scale, n, "scale")
+        check(_lib.load().pda_ials_gram_scaled_f32(ptr(Z), ptr(scale), n, d, ptr(G), ptr(workspace), workspace.numel(), stream_ptr()),
+              "pda_ials_gram_scaled_f32")
+        return G
     check(_lib.load().pda_ialspp_gram_f32(ptr(Z), n, d, ptr(G), ptr(workspace), workspace.numel(), stream_ptr()), "pda_ialspp_gram_f32")
     return G
 
@@ -4341,13 +4442,15 @@ def ialspp_predict(graph: IalsGraph, X, Y, e=None):
 
 
 def ialspp_block_pass(graph: IalsGraph, side: str, Z, X, block: int, k: int, *, G=None, e=None, work: Optional[IalsWork] = None, dbg=None,
-                      fail_count=None, slots=None, delta_ws=None):
+                      fail_count=None, slots=None, delta_ws=None, alpha_row=None):
     """pda_ialspp_block_pass_f32: one pass of the coordinate block [block * k, (block + 1) * k) over the rows of `work` (default: every row of
     the side): x_{r,pi} <- the exact minimiser over the block, in place in X, and the rows' entries of the prediction cache e follow.  Z is the
     other table, held fixed; G: Z^T Z (computed here when missing); e: the cache (default: the graph's own, which ialspp_predict fills).
     dbg float32 [n_rows, k * k + k] receives (H, g) as they enter the factorisation.  slots / delta_ws: float32 scratch of n_slots * (k * k + k)
-    and n_slots * k floats (default: the graph's own).  Returns X."""
+    and n_slots * k floats (default: the graph's own).  alpha_row float32 [n_rows] (pda_ialspp_block_pass_rowalpha_f32): the row's own weight in
+    place of alpha0.  On an item-weighted graph the user side's G defaults to G_w and the item side's alpha_row to the graph's own.  Returns X."""
     s = graph.side(side)
+    gram_scale, alpha_row = _ials_graph_inputs(graph, side, alpha_row)
     Z = _ialspp_table(Z, s.n_other, "Z (the table held fixed)")
     X = _ialspp_table(X, s.n_rows, "X")
     d = Z.shape[1]
@@ -4359,7 +4462,7 @@ def ialspp_block_pass(graph: IalsGraph, side: str, Z, X, block: int, k: int, *, 
         raise ValueError(f"iALS++: block {block} is outside the {len(p0s)} blocks of d = {d}, k = {k}")
     b = ialspp_buffers(graph, d, k)
     if G is None:
-        G = ialspp_gram(Z, b["G"], b["gram_ws"])
+        G = ialspp_gram(Z, b["G"], b["gram_ws"], gram_scale)
     if _need(G, torch.float32, "G").shape != (d, d):
         raise ValueError("iALS++: G is float32 [d, d]")
     e = b["e"] if e is None else _need(e, torch.float32, "e")
@@ -4378,6 +4481,17 @@ def ialspp_block_pass(graph: IalsGraph, side: str, Z, X, block: int, k: int, *, 
     if slots.numel() < w.n_slots * (k * k + k) or delta_ws.numel() < w.n_slots * k:
         raise ValueError(f"iALS++: {w.n_slots} slots need {w.n_slots * (k * k + k)} and {w.n_slots * k} floats")
     perm = b["pair_perm"] if side == "item" else None
+    if alpha_row is not None:
+        alpha_row = _ials_row_vector(alpha_row, s.n_rows, "alpha_row")
+        check(_lib.load().pda_ialspp_block_pass_rowalpha_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, ptr(perm), s.n_rows, s.nnz, ptr(w.work),
+                                                             w.n_work, ptr(w.long_rows) if w.n_long else None, w.n_long, w.n_slots, ptr(Z), s.n_other,
+                                                             ptr(G), d, k, p0s[block], ptr(alpha_row), ptr(s.lam_row), ptr(X),
+                                                             ptr(e) if s.nnz else None, ptr(fail), ptr(dbg), ptr(slots) if w.n_slots else None,
+                                                             slots.numel() if w.n_slots else 0, ptr(delta_ws) if w.n_slots else None,
+                                                             delta_ws.numel() if w.n_slots else 0, stream_ptr()),
+              "pda_ialspp_block_pass_rowalpha_f32")
+        mark_modified(X)
+        return X
     check(_lib.load().pda_ialspp_block_pass_f32(ptr(s.indptr), ptr(s.indices) if s.nnz else None, ptr(perm), s.n_rows, s.nnz, ptr(w.work), w.n_work,
                                                 ptr(w.long_rows) if w.n_long else None, w.n_long, w.n_slots, ptr(Z), s.n_other, ptr(G), d, k,
                                                 p0s[block], float(graph.alpha0), ptr(s.lam_row), ptr(X), ptr(e) if s.nnz else None, ptr(fail),
@@ -4397,7 +4511,7 @@ def ialspp_loss(graph: IalsGraph, X, Y, *, G=None, rows=None):
         raise ValueError("iALS++: X and Y share the embedding width")
     b = ialspp_buffers(graph, d)
     if G is None:
-        G = ialspp_gram(Y, b["G"], b["gram_ws"])
+        G = ialspp_gram(Y, b["G"], b["gram_ws"], _ials_graph_inputs(graph, "user", None)[0])
     rows = b["rows"] if rows is None else _need(rows, torch.float32, "rows")
     if tuple(rows.shape) != (graph.n_users, 3):
         raise ValueError(f"iALS++: rows is float32 [{graph.n_users}, 3]")

@@ -93,6 +93,7 @@ _EXTENSION_FLAGS = [
     ("ials_alpha0", float, 0.1, "iALS (--train ials, include/pda_hip_ials.h): weight alpha0 of the unobserved pairs, >= 0.  --regs is lambda (> 0); --lr, --optimizer, --adam_sweep, --sampler and --batch_size (for training) are unused by iALS"),
     ("ials_nu", float, 1.0, "iALS: frequency scaling of the regulariser, lambda (n + alpha0 n_other)^nu per row, 0 .. 1 (0: plain L2)"),
     ("ials_solver", str, "exact", "iALS: exact = every row solved exactly, a d x d system per row (--embed_size 32 | 64 | 128) | block = iALS++ (include/pda_hip_ialspp.h): per epoch one exact step on each block of --ials_block coordinates, users then items, --embed_size 32 | 64 | 128 | 256.  A block step starts from the tables as they stand, so their initialisation matters (the exact solver forgets it after one half-sweep) and an epoch converges more slowly than an exact one"),
+    ("ials_item_power", float, 0.0, "iALS (either solver; include/pda_hip_ials_itemw.h): item-weighted unobserved pairs (the eALS weighting).  The unobserved pairs of item i weigh alpha0 w_i with w_i ~ (c_i + 1)^power of the item's distinct train pairs c_i, normalised to mean 1, 0 .. 4; 0 (default): every w_i is 1, the unweighted model, bit for bit"),
     ("ials_block", int, 32, "iALS (--ials_solver block): the block size k, 32 | 64 | 128; it has to divide --embed_size (k = --embed_size is the exact solve started from the current tables)"),
     ("pcc_gamma", float, 1.0, "PCC (--train pcc, include/pda_hip_pcc.h): weight gamma of the penalty gamma r^2, r the Pearson correlation over the batch between a score and the popularity of the positive, >= 0 (0: the BPR loss, r is still reported).  The default is UNTUNED: nothing here has the data sets"),
     ("pcc_on", str, "pos", "PCC: the score that is correlated with the positive's popularity.  pos = the score of the observed pair (Zhu et al., WSDM'21) | margin = the pairwise margin, positive score minus negative score"),
